@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- DOF/s of the matrix-free sum-factorised Diffusion3D operator apply (hex, order 6) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ne 64] [--order 6]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ne 64] [--order 6] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 N > 1: one process per GPU.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*) this process
 is one rank; typed as above without a launcher it starts its N ranks itself as child processes and relays rank 0's JSON line.
@@ -10,7 +10,13 @@ A "step" is one operator apply Y <- A X (alpha = 1, beta = 0) over the whole mes
 a 64^3-element block of order-6 hexes on [0,1]^3 (228.3 M global dofs on one GPU; 128^3 = BASELINE.json config 3 on
 8 GPUs as 2x2x2 blocks), smoothly perturbed vertices (no affine shortcut), Dirichlet on unknown 0 of all six sides,
 kernel = benchmarks/Diffusion3D.hpp:51-79 (U = 4, E = 7, k = s = 1), x ~ U(-1,1) synthetic, resident in HBM.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and (N = 1) `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement) with a `roofline` object taken from the timed launches.
+
+A plain run sets up, warms up, times the K steps, writes the last step's output if --dump-outputs is given and prints the line.
+--full adds the measurements and checks that take runs of their own, after the timed steps: at order 6 on one GPU LocalAssembly
+(`assembled_path`), the order-4 apply (`order4_apply`) and the apply on the uniform cube (`uniform_mesh_apply`); on one GPU the
+CPU baseline on the same mesh with whole-vector parity against the timed output (`cpu_baseline`, unless --no-cpu-baseline); in
+a rehearsal (L3K_BENCH_REHEARSAL=1) the partitioned result against one rank's apply on the whole mesh (`rehearsal_check`).
 """
 import argparse
 import json
@@ -121,6 +127,28 @@ def cpu_baseline(part, mask, x_owned, p, U, applies=3):
                       f"(affinity mask: {mask_cores} CPUs, CPU quota applied where the container sets one), {' / '.join(f'{t:.2f}' for t in times)} s"}, y
 
 
+DUMP_MAX_ENTRIES = 1 << 21  # 16 MB of float64: a larger output is dumped as a sample of this many positions
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, Y):
+    """--dump-outputs: the output of the last timed step, the vector y a caller of the apply receives (this rank's owned rows,
+    flattened node-major), as float64 .npy files in out_dir.  Up to DUMP_MAX_ENTRIES entries: y.npy, the whole vector.  Larger:
+    y_sample.npy at fixed positions drawn with DUMP_SEED (sorted, duplicates dropped; the positions themselves, exact in float64,
+    in y_sample_index.npy).  Always y_norms.npy = [L2 norm, sum, max |y|] over the whole vector."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = Y.reshape(-1)
+    n = y.numel()
+    if n <= DUMP_MAX_ENTRIES:
+        np.save(os.path.join(out_dir, "y.npy"), y.cpu().numpy())
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ENTRIES))
+        np.save(os.path.join(out_dir, "y_sample.npy"), y[torch.from_numpy(idx).to(y.device)].cpu().numpy())
+        np.save(os.path.join(out_dir, "y_sample_index.npy"), idx.astype(np.float64))
+    norms = torch.stack([torch.linalg.vector_norm(y), y.sum(), y.abs().max()])
+    np.save(os.path.join(out_dir, "y_norms.npy"), norms.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -128,7 +156,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=15, help="untimed applies (the clock of an idle GPU ramps over the first ~10 launches)")
     ap.add_argument("--ne", type=int, default=64, help="elements per edge of each GPU's block")
     ap.add_argument("--order", type=int, default=6)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements and checks (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline and its parity check")
     args = ap.parse_args()
 
     if args.gpus not in PARTS:
@@ -250,6 +280,8 @@ def main():
         kt = torch.tensor(kernel_times, dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(kt, op=dist.ReduceOp.MAX)
         kernel_times = kt.tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Y)
     ms = float(np.median(kernel_times))  # median of the timed steps
     global_dofs = part.n_global_nodes * U
     value = global_dofs * args.steps / elapsed
@@ -289,7 +321,7 @@ def main():
                               "fp64_tflops": None if flop_per_elem is None else flop_per_elem * n_launch_elems / (ms * 1e-3) / 1e12,
                               "fp64_peak_tflops": 78.6,
                               "fp64_frac": None if flop_per_elem is None else flop_per_elem * n_launch_elems / (ms * 1e-3) / 1e12 / 78.6}
-        if world == 1 and op is None and p == 6:
+        if args.full and world == 1 and op is None and p == 6:
             # the second half of BASELINE.json's metric: element matrices/s of LocalAssembly, order 6, streaming mode
             # (checksums instead of 15 MB per matrix); outside the timed region.  Default algorithm: sum-factorised assembly
             # (device/assemble.hpp: ~47 MFLOP per element on the vector pipe); beside it the dense K_e = (W Z)^T Z product on
@@ -390,7 +422,7 @@ def main():
                                             "value": global_dofs / (msu * 1e-3), "unit": "DOF/s", "ms_per_step": msu, "kernel": mfu.route(),
                                             "roofline_frac_hbm_whole_apply": global_dofs / (msu * 1e-3) * bpd / 1e9 / HBM_PEAK_GBS}
             del mfu, Yu, partu
-        if world == 1 and op is None:
+        if args.full and world == 1 and op is None:
             if not args.no_cpu_baseline:
                 # the CPU run doubles as a full-size parity check: the whole output vector of the timed GPU launches
                 # (dynamic XCD-chunked batch distribution included) against the oracle on the same mesh and x
@@ -402,7 +434,7 @@ def main():
                 result["config"]["parity_sample"] = "the whole output vector of the benchmark mesh"
                 if not err < 1e-11:
                     raise SystemExit(f"GPU result differs from the oracle: rel L2 {err}")
-    if rehearsal and use_dist:
+    if args.full and rehearsal and use_dist:
         # the partitioned result against ONE rank's apply on the whole mesh (same global numbering, perturbation and x): x^T A x
         # over the owned rows of all ranks, and the norm of y
         loc = torch.stack([(X * Y).sum(), (Y * Y).sum()]).cpu()

@@ -328,8 +328,8 @@ def test_deterministic_mode_with_derivative_boundary_kernel(ne):
 def test_bench_gpus_2_as_typed():
     """`python bench.py --gpus 2 ...` typed WITHOUT a launcher (it used to exit with "launch with torch.distributed.run"):
     the script starts its two ranks itself as child processes (l3ster_amd/launch.py), relays rank 0's single JSON line and returns 0.
-    On the one-GPU box under L3K_BENCH_REHEARSAL=1 (both ranks on GPU 0, gloo, host-staged messages); the partitioned apply is
-    checked inside against one rank's apply on the whole mesh."""
+    On the one-GPU box under L3K_BENCH_REHEARSAL=1 (both ranks on GPU 0, gloo, host-staged messages); with --full the partitioned
+    apply is checked inside against one rank's apply on the whole mesh."""
     import json
     import os
     import subprocess
@@ -337,8 +337,8 @@ def test_bench_gpus_2_as_typed():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["L3K_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--ne", "8", "--steps", "2", "--warmup", "1"], cwd=root, env=env,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--ne", "8", "--steps", "2", "--warmup", "1", "--full"], cwd=root,
+                       env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.strip() and not ln.startswith("[Gloo]")]  # (gloo announces itself on stdout)
     assert len(lines) == 1, r.stdout
@@ -351,3 +351,47 @@ def test_bench_gpus_2_as_typed():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--ne", "8", "--steps", "2", "--warmup", "1"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "rank 1 of 2" in (r.stdout + r.stderr)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_full_run_and_dumped_outputs(tmp_path):
+    """`python bench.py` as the measurements run it: a plain run times exactly --steps steps and prints the headline fields and
+    none of the --full blocks; --dump-outputs writes the last timed step's y, which equals the oracle's apply on the same mesh
+    and x; --full adds the secondary measurements and the CPU baseline with its whole-vector parity."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import oracle_lib as O
+    from l3ster_amd import system
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    full_only = {"assembled_path", "order4_apply", "uniform_mesh_apply", "cpu_baseline"}
+
+    def bench(ne, *extra):
+        r = subprocess.run([sys.executable, "bench.py", "--ne", str(ne), "--steps", "3", "--warmup", "1", *extra], cwd=root, env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0])
+
+    out = bench(4, "--dump-outputs", str(tmp_path / "dump"))
+    assert out["steps"] == 3 and out["n_gpus"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "DOF/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert not full_only & set(out) and "parity_vs_oracle_rel_l2" not in out["config"]
+    U, p = 4, 6
+    part = system.CubePartition(4, p, perturb=0.1)
+    mask = part.dirichlet_mask(U)
+    y_ref = O.mf_apply(helpers.oracle_mesh(part, p + 1, U, np.arange(U), mask), 0, part.synthetic_vector(U).T)[:, 0]
+    y = np.load(tmp_path / "dump" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == y_ref.shape
+    assert helpers.rel_err(y, y_ref) < 1e-11
+    norms = np.load(tmp_path / "dump" / "y_norms.npy")
+    assert abs(norms[0] - np.linalg.norm(y)) <= 1e-12 * norms[0] and norms[2] == np.abs(y).max()
+    assert abs(norms[1] - y.sum()) <= 1e-12 * np.abs(y).sum()
+
+    out = bench(13, "--full")  # (LocalAssembly of --full streams batches of 2048 elements: 13^3 = 2197)
+    assert out["steps"] == 3 and full_only <= set(out)
+    assert out["config"]["parity_vs_oracle_rel_l2"] < 1e-11
