@@ -2,6 +2,7 @@
 // kernels (scale, Dirichlet rows, pack / unpack-add).  No CPU fallback: without a usable HIP device every device entry
 // point fails with an error.
 #include "objects.hpp"
+#include "device/launch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -194,7 +195,8 @@ double* contextScratch(void* owner, size_t bytes)
     return ctx->scratch;
 }
 
-int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a)
+// `energy` (applies): where a single-column launch adds x^T A x, l3k_mf_energy_begin's target; only the apply kernel reads it
+int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* energy = nullptr)
 {
     const l3k_mesh* m = mf->mesh;
     a                 = {};
@@ -211,7 +213,7 @@ int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a)
     a.scratch_owner        = mf->ctx;
     // dynamic batch distribution of the single-wave kernel (l3k_tuning::static_deal: the static deal)
     a.work_counters        = mf->ctx->tune.static_deal ? nullptr : mf->ctx->work_counters;
-    a.energy        = ncols == 1 ? mf->energy_target : nullptr;
+    a.energy        = ncols == 1 ? energy : nullptr;
     a.energy_done   = &mf->energy_done;
     a.n_shell              = m->n_shell;
     a.tables          = mf->tables.ptr;
@@ -282,6 +284,27 @@ const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols)
         setError("no device instantiation for kernel %d, order %d, nq %d, ncols %d: add it to L3K_FOR_EACH_INSTANCE "
                  "(l3ster_amd/csrc/user_kernels.hpp) and rebuild",
                  mf->kernel_id, mf->mesh->order, mf->nq, ncols);
+    return inst;
+}
+// How an apply of `ncols` columns is launched (l3k_mf_apply_elems launches the plan, l3k_mf_route describes it): through the
+// ncols-column instance; else, as the reference does when fewer columns than n_rhs are passed
+// (algsys/MatrixFreeSystem.hpp:1124-1138), through the single-column one -- for a dense dof layout all columns in one pass over
+// the elements (node ids, flags and the work ticket once per element, MatrixFreeSystem.hpp:678-688; l3k_tuning::column_by_column
+// switches it off for cross-checks), otherwise column by column.
+enum class ColumnPlan
+{
+    instance,
+    one_pass,
+    per_column
+};
+const l3k::dev::Instance* planColumns(const l3k_mf* mf, int ncols, ColumnPlan& plan)
+{
+    plan = ColumnPlan::instance;
+    if (const auto* inst = l3k::dev::findInstance(mf->kernel_id, mf->mesh->order, mf->nq, ncols))
+        return inst;
+    const auto* inst = instanceFor(mf, 1);
+    plan = inst && inst->apply_cols && mf->dense && !mf->ctx->deterministic && !mf->ctx->tune.column_by_column ? ColumnPlan::one_pass
+                                                                                                            : ColumnPlan::per_column;
     return inst;
 }
 } // namespace
@@ -1057,13 +1080,9 @@ int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, s
         return -1;
     }
     buf[0] = '\0';
+    // (with_energy: any non-null device pointer, nothing is launched)
     l3k::dev::ElemArgs a;
-    double* const      saved = mf->energy_target;
-    if (with_energy)
-        mf->energy_target = reinterpret_cast< double* >(mf->ctx->red_ws); // (any non-null device pointer: nothing is launched)
-    const int rc      = fillArgs(mf, which, ncols, a);
-    mf->energy_target = saved;
-    if (rc)
+    if (int rc = fillArgs(mf, which, ncols, a, with_energy ? reinterpret_cast< double* >(mf->ctx->red_ws) : mf->energy_target))
         return rc;
     if (mf->ctx->deterministic)
         a.energy = nullptr; // (forEachLaunchRange)
@@ -1074,18 +1093,12 @@ int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, s
     a.x = a.y = nullptr;
     a.xg = a.yg = (m->n_ghost_nodes > 0 && (which == 1 || which == 2)) ? const_cast< double* >(dummy) : nullptr;
     a.fuse_beta = mf->fuse;
-    const auto* inst = l3k::dev::findInstance(mf->kernel_id, m->order, mf->nq, ncols);
-    bool        looped = false;
+    ColumnPlan  plan;
+    const auto* inst = planColumns(mf, ncols, plan);
     if (!inst)
-    {
-        inst = instanceFor(mf, 1);
-        if (!inst)
-            return -4;
-        if (inst->apply_cols && mf->dense && !mf->ctx->deterministic && !mf->ctx->tune.column_by_column)
-            a.n_cols = ncols;
-        else
-            looped = ncols > 1;
-    }
+        return -4;
+    if (plan == ColumnPlan::one_pass)
+        a.n_cols = ncols;
     if (!inst->route)
     {
         setError("this instance carries no route description");
@@ -1095,7 +1108,8 @@ int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, s
         return rc2;
     const size_t len = std::strlen(buf);
     if (const auto* meta = l3k::api::findKernel(mf->kernel_id))
-        std::snprintf(buf + len, n - len, " [kernel %d \"%s\"%s%s%s]", mf->kernel_id, meta->name, looped ? ", column by column" : "",
+        std::snprintf(buf + len, n - len, " [kernel %d \"%s\"%s%s%s]", mf->kernel_id, meta->name,
+                      plan == ColumnPlan::per_column ? ", column by column" : "",
                       mf->ctx->deterministic ? ", deterministic: one launch per colour" : "", mf->ctx->reference_z0 ? ", reference z=0" : "");
     return 0;
 }
@@ -1135,7 +1149,7 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev != mf->ctx->device) // (several contexts in one process)
         L3K_HIP(hipSetDevice(mf->ctx->device));
     l3k::dev::ElemArgs a;
-    if (int rc = fillArgs(mf, which, ncols, a))
+    if (int rc = fillArgs(mf, which, ncols, a, mf->energy_target))
         return rc;
     if (a.elem_count > 0 && (a.energy || mf->energy_target)) // (armed but ncols > 1: a.energy is null, never "fused")
         ++mf->energy_expected;
@@ -1176,42 +1190,27 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     a.alpha     = alpha;
     a.beta      = beta;
     a.fuse_beta = mf->fuse;
-    const void* blob = mf->blob.empty() ? nullptr : mf->blob.data();
-    const auto* inst = l3k::dev::findInstance(mf->kernel_id, mf->mesh->order, mf->nq, ncols);
-    if (inst)
+    const void* blob   = mf->blob.empty() ? nullptr : mf->blob.data();
+    const auto  launch = [&](const l3k::dev::Instance* inst, l3k::dev::ElemArgs& ac) {
+        return forEachLaunchRange(mf, which, ac, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, blob, mf->ctx->stream); });
+    };
+    ColumnPlan  plan;
+    const auto* inst = planColumns(mf, ncols, plan);
+    if (!inst)
+        return -4;
+    int rc = 0;
+    if (plan == ColumnPlan::instance)
+        rc = launch(inst, a);
+    else if (plan == ColumnPlan::one_pass)
     {
-        if (int rc = forEachLaunchRange(mf, which, a, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, blob, mf->ctx->stream); }))
-            return rc;
+        a.n_cols = ncols;
+        a.energy = nullptr;
+        rc       = inst->apply_cols(a, blob, mf->ctx->stream);
     }
     else
-    {
-        // no ncols-column instantiation: column by column with the single-column one, as the reference does when
-        // fewer columns than n_rhs are passed (algsys/MatrixFreeSystem.hpp:1124-1138)
-        inst = instanceFor(mf, 1);
-        if (!inst)
-            return -4;
-        if (inst->apply_cols && mf->dense && !mf->ctx->deterministic && !mf->ctx->tune.column_by_column) // (the switch: cross-check)
-        {
-            // dense dof layout: all columns in one pass over the elements (node ids, flags and the work ticket once per
-            // element), MatrixFreeSystem.hpp:678-688
-            l3k::dev::ElemArgs ac = a;
-            ac.n_cols             = ncols;
-            ac.energy             = nullptr;
-            if (int rc = inst->apply_cols(ac, blob, mf->ctx->stream))
-                return rc;
-        }
-        else
-        for (int c = 0; c < ncols; ++c)
-        {
-            l3k::dev::ElemArgs ac = a;
-            ac.x  = d_x + ldx * c;
-            ac.xg = d_xghost ? d_xghost + ldxg * c : nullptr;
-            ac.y  = d_y + ldy * c;
-            ac.yg = d_yghost ? d_yghost + ldyg * c : nullptr;
-            if (int rc = forEachLaunchRange(mf, which, ac, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, blob, mf->ctx->stream); }))
-                return rc;
-        }
-    }
+        rc = l3k::dev::forEachColumn(a, ncols, [&](l3k::dev::ElemArgs& ac) { return launch(inst, ac); });
+    if (rc)
+        return rc;
     // boundary equation kernels registered on this system act on the sides of the same element range
     // (the halves of the interior: all sides of interior elements go with the first half)
     if (which != 4)

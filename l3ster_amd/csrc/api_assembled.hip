@@ -409,8 +409,8 @@ template < int U, int N1 >
 int launchTiledXOne(int64_t count, const double* Kt, double* K, hipStream_t s)
 {
     constexpr size_t lds    = sizeof(double) * size_t(N1) * U * (N1 * N1 * U + 1);
-    if constexpr (lds > 64 * 1024) // (order 7 with 4 unknowns; an attribute of the function on the CURRENT device: set per launch)
-        if (hipFuncSetAttribute(reinterpret_cast< const void* >(&tiledXToRowMajorSymKernel< U, N1 >), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess)
+    if constexpr (lds > 64 * 1024) // (order 7 with 4 unknowns)
+        if (!l3k::dev::allowDynamicLds(reinterpret_cast< const void* >(&tiledXToRowMajorSymKernel< U, N1 >), lds))
             return 1;
     const int64_t blocks = ((count + 7) / 8) * 8 * N1 * N1;
     hipLaunchKernelGGL((tiledXToRowMajorSymKernel< U, N1 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K, count);

@@ -17,7 +17,6 @@
 
 #include "sumfact_apply.hpp"
 
-#include <mutex>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -1223,66 +1222,27 @@ int launchAssemble(const ElemArgs& a, const void* kparam_blob, hipStream_t strea
     using C = GemmCfg< P, NQ, U, E >;
     if (a.elem_count <= 0)
         return 0;
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-    constexpr size_t ldc    = coeffLdsBytes< K, P, NQ >();
+    const K          kern    = functorFrom< K >(kparam_blob);
+    constexpr size_t ldc     = coeffLdsBytes< K, P, NQ >();
     constexpr bool   coef_gs = ldc > lds_limit_bytes; // the field buffers of the coefficient kernel exceed the LDS: global scratch
-    auto             kc  = assembleCoeffKernel< K, P, NQ, coef_gs >;
-    auto             kg  = assembleGemmKernel< K, P, NQ >;
-    // the dynamic-LDS attributes of the three kernels are set once PER DEVICE, under a lock (several contexts of one
-    // process may sit on different GPUs)
-    using S = SfAsmCfg< P, NQ >;
-    {
-        static bool       attr_set[64] = {};
-        static std::mutex attr_mutex;
-        int               dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64)
-        {
-            setError("device index %d not supported", dev);
-            return -3;
-        }
-        std::lock_guard< std::mutex > lock{attr_mutex};
-        if (!attr_set[dev])
-        {
-            bool ok = (coef_gs || hipFuncSetAttribute(reinterpret_cast< const void* >(kc), hipFuncAttributeMaxDynamicSharedMemorySize, int(ldc)) == hipSuccess) &&
-                      hipFuncSetAttribute(reinterpret_cast< const void* >(kg), hipFuncAttributeMaxDynamicSharedMemorySize, int(C::lds)) == hipSuccess;
-            if constexpr (S::feasible)
-                ok = ok && hipFuncSetAttribute(reinterpret_cast< const void* >(assembleSumfactKernel< K, P, NQ >),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, int(S::ldsFor(false, 0))) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast< const void* >(assembleSumfactKernel< K, P, NQ, 1 >),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(S::ldsFor(true, 0))) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast< const void* >(assembleSumfactKernel< K, P, NQ, 2 >),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(S::ldsFor(true, 0))) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast< const void* >(assembleSumfactKernel< K, P, NQ, 0, 1 >),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(S::ldsFor(false, 1))) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast< const void* >(assembleSumfactKernel< K, P, NQ, 0, 2 >),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, int(S::ldsFor(false, 2))) == hipSuccess;
-            if (!ok)
-            {
-                setError("hipFuncSetAttribute failed for the assembly kernels");
-                return -3;
-            }
-            attr_set[dev] = true;
-        }
-    }
-    double* cbuf = a.workspace; // coeffStride * nq^3 doubles per element, + 1 flag
+    auto             kc      = assembleCoeffKernel< K, P, NQ, coef_gs >;
+    using S                  = SfAsmCfg< P, NQ >;
+    double* cbuf             = a.workspace; // coeffStride * nq^3 doubles per element, + 1 flag
     if constexpr (coef_gs)
     {
-        const int64_t  max_wgs = 2 * int64_t(deviceComputeUnits());
-        const unsigned grid    = static_cast< unsigned >(a.elem_count < max_wgs ? a.elem_count : max_wgs);
-        ElemArgs       ag      = a;
-        ag.scratch             = a.scratch_alloc ? a.scratch_alloc(a.scratch_owner, ldc * grid) : nullptr;
+        ElemArgs       ag   = a;
+        const unsigned grid = scratchGrid(ag, ldc);
         if (!ag.scratch)
         {
             setError("could not obtain %zu bytes of global scratch for the assembly coefficient kernel", ldc * grid);
             return -3;
         }
-        hipLaunchKernelGGL(kc, dim3(grid), dim3(applyThreads< P, NQ >()), 0, stream, ag, kern, cbuf);
+        if (int rc = launchKernel("assembly kernel", kc, dim3(grid), dim3(applyThreads< P, NQ >()), 0, stream, ag, kern, cbuf))
+            return rc;
     }
-    else
-        hipLaunchKernelGGL(kc, dim3(static_cast< unsigned >(a.elem_count)), dim3(applyThreads< P, NQ >()), ldc, stream, a, kern, cbuf);
+    else if (int rc = launchKernel("assembly kernel", kc, dim3(static_cast< unsigned >(a.elem_count)), dim3(applyThreads< P, NQ >()), ldc,
+                                   stream, a, kern, cbuf))
+        return rc;
     // the sum-factorised kernel unless it does not fit or l3k_tuning::assemble_dense asks for the dense MFMA product (cross-check)
     const l3k_tuning& tune  = tuneOf(a);
     const bool        dense = !S::feasible || (tune.assemble_dense && !a.K_tiled);
@@ -1304,10 +1264,9 @@ int launchAssemble(const ElemArgs& a, const void* kparam_blob, hipStream_t strea
                     setError("assembly batch too large: %lld workgroups", (long long)n_blocks);
                     return -1;
                 }
-                if (n_blocks > 0)
-                    hipLaunchKernelGGL(ks, dim3(static_cast< unsigned >(n_blocks)), dim3(threads), lds_bytes, stream, a, cbuf,
-                                       int64_t(a.elem_begin_out), xcd_group);
-                return 0;
+                return n_blocks > 0 ? launchKernel("assembly kernel", ks, dim3(static_cast< unsigned >(n_blocks)), dim3(threads), lds_bytes,
+                                                   stream, a, cbuf, int64_t(a.elem_begin_out), xcd_group)
+                                    : 0;
             };
             // the diagonal and the off-diagonal blocks as two launches (a register allocation each); one launch over all pairs
             // where the workgroups of an element should meet in one L2 (stored row-major matrices) or on request
@@ -1329,14 +1288,8 @@ int launchAssemble(const ElemArgs& a, const void* kparam_blob, hipStream_t strea
                 return rc;
         }
     if (dense)
-        hipLaunchKernelGGL(kg, dim3(C::NLT, static_cast< unsigned >(a.elem_count)), dim3(256), C::lds, stream, a, cbuf,
-                           int64_t(a.elem_begin_out));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("assembly kernel launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
+        return launchKernel("assembly kernel", assembleGemmKernel< K, P, NQ >, dim3(C::NLT, static_cast< unsigned >(a.elem_count)), dim3(256),
+                            C::lds, stream, a, cbuf, int64_t(a.elem_begin_out));
     return 0;
 }
 template < typename K, int P, int NQ >

@@ -372,29 +372,8 @@ int launchFace(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)
         return 0;
     constexpr size_t lds = sizeof(double) * faceLdsDoubles< K, P, NQ, R, RHS_MODE >();
     static_assert(lds <= lds_limit_bytes, "side working set exceeds 160 KiB of LDS");
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-    auto        kernel   = faceKernel< K, P, NQ, R, RHS_MODE >;
-    static bool attr_set = false;
-    if (!attr_set)
-    {
-        if (hipFuncSetAttribute(reinterpret_cast< const void* >(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(lds)) != hipSuccess)
-        {
-            setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
-            return -3;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3(static_cast< unsigned >(a.face_count)), dim3(256), lds, stream, a, kern);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("faceKernel launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
-    return 0;
+    return launchKernel("faceKernel", faceKernel< K, P, NQ, R, RHS_MODE >, dim3(static_cast< unsigned >(a.face_count)), dim3(256), lds, stream,
+                        a, functorFrom< K >(kparam_blob));
 }
 } // namespace l3k::dev
 #endif

@@ -182,5 +182,7 @@ struct ResidualId;
 void setError(const char* fmt, ...);
 // compute units of the current device (cached per device)
 int deviceComputeUnits();
+// lets `fn` take `bytes` of dynamic LDS on the current device (hipFuncSetAttribute, once per function and device; thread-safe)
+bool allowDynamicLds(const void* fn, size_t bytes);
 } // namespace l3k::dev
 #endif

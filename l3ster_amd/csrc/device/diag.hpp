@@ -191,53 +191,22 @@ int launchDiagRhs(const ElemArgs& a, const void* kparam_blob, hipStream_t stream
             return rc;
     if (!a.diag)
         return 0;
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
     constexpr size_t lds = diagLdsBytes< K, P, NQ >();
     if constexpr (lds > lds_limit_bytes)
     {
-        const int64_t  max_wgs = 2 * int64_t(deviceComputeUnits());
-        const unsigned grid    = static_cast< unsigned >(a.elem_count < max_wgs ? a.elem_count : max_wgs);
-        ElemArgs       ag      = a;
-        ag.scratch             = a.scratch_alloc ? a.scratch_alloc(a.scratch_owner, lds * grid) : nullptr;
+        ElemArgs       ag   = a;
+        const unsigned grid = scratchGrid(ag, lds);
         if (!ag.scratch)
         {
             setError("could not obtain %zu bytes of global scratch for the diagonal kernel", lds * grid);
             return -3;
         }
-        hipLaunchKernelGGL((diagKernel< K, P, NQ, true >), dim3(grid), dim3(applyThreads< P, NQ >()), 0, stream, ag, kern);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess)
-        {
-            setError("diagKernel (global scratch) launch failed: %s", hipGetErrorString(err));
-            return -3;
-        }
-        return 0;
+        return launchKernel("diagKernel (global scratch)", diagKernel< K, P, NQ, true >, dim3(grid), dim3(applyThreads< P, NQ >()), 0,
+                            stream, ag, functorFrom< K >(kparam_blob));
     }
     else
-    {
-    auto        kernel   = diagKernel< K, P, NQ >;
-    static bool attr_set = false;
-    if (!attr_set)
-    {
-        if (hipFuncSetAttribute(reinterpret_cast< const void* >(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) !=
-            hipSuccess)
-        {
-            setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
-            return -3;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3(static_cast< unsigned >(a.elem_count)), dim3(applyThreads< P, NQ >()), lds, stream, a, kern);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("diagKernel launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
-    return 0;
-    }
+        return launchKernel("diagKernel", diagKernel< K, P, NQ >, dim3(static_cast< unsigned >(a.elem_count)), dim3(applyThreads< P, NQ >()),
+                            lds, stream, a, functorFrom< K >(kparam_blob));
 }
 } // namespace l3k::dev
 #endif

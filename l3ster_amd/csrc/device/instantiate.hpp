@@ -37,33 +37,27 @@ L3K_FOR_EACH_RESIDUAL_KERNEL(L3K_X)
 
 namespace l3k::dev
 {
-// R columns through the one-wave-per-element kernel, one column per launch: at order 6 it is ~3x faster per column than
-// the generic LDS kernel, so R launches beat one R-column launch (the apply never reads the kernel's rhs, so the
-// single-column instantiation of the functor gives the same operator); unknowns on a subset of the node's dofs: column by
-// column through the strided-dof variant
+// R columns through the one-wave-per-element kernel: all R in one pass of its multi-column variant (dense dof layouts), else one
+// launch of the single-column kernel per column -- at order 6 it is ~3x faster per column than the generic LDS kernel, so R
+// launches beat one R-column launch (the apply never reads the kernel's rhs, so the single-column instantiation of the functor
+// gives the same operator); unknowns on a subset of the node's dofs: column by column through the strided-dof variant.
+// launchColumnsFast launches it, selectRoute describes it.
+template < typename T, int P, int NQ >
+bool fastColumnsInOnePass(const ElemArgs& a)
+{
+    return FastCfg< T, P, NQ >::multi_column && a.dense;
+}
 template < typename T, int P, int NQ, int R >
 int launchColumnsFast(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)
 {
     if constexpr (FastCfg< T, P, NQ >::multi_column)
-        if (a.dense)
+        if (fastColumnsInOnePass< T, P, NQ >(a))
         {
-            ElemArgs ac = a; // all R columns in one pass over the elements (the multi-column variant of the single-wave kernel)
+            ElemArgs ac = a;
             ac.n_cols   = R;
             return launchSumfactFastCols< T, P, NQ >(ac, kparam_blob, stream);
         }
-    {
-        for (int c = 0; c < R; ++c)
-        {
-            ElemArgs ac = a;
-            ac.x        = a.x + a.ldx * c;
-            ac.xg       = a.xg ? a.xg + a.ldxg * c : nullptr;
-            ac.y        = a.y + a.ldy * c;
-            ac.yg       = a.yg ? a.yg + a.ldyg * c : nullptr;
-            if (int rc = launchSumfactFast< T, P, NQ >(ac, kparam_blob, stream))
-                return rc;
-        }
-        return 0;
-    }
+    return forEachColumn(a, R, [&](const ElemArgs& ac) { return launchSumfactFast< T, P, NQ >(ac, kparam_blob, stream); });
 }
 // the column-loop entry of a single-column instance (Instance::apply_cols), or nullptr where the single-wave kernel does not fit
 template < typename T, int P, int NQ, int R >
@@ -91,10 +85,11 @@ constexpr RouteFn selectRoute()
         return &describeSumfactFast< T, P, NQ >;
     else if constexpr (FastCfg< T, P, NQ >::feasible)
         return +[](const ElemArgs& a, char* buf, size_t n) {
-            ElemArgs ac = a; // launchColumnsFast: one multi-column pass, or R launches of the single-column kernel
-            ac.n_cols   = a.dense ? R : 1;
-            const int rc = describeSumfactFast< T, P, NQ >(ac, buf, n);
-            if (rc == 0 && (!FastCfg< T, P, NQ >::multi_column || !a.dense))
+            const bool one_pass = fastColumnsInOnePass< T, P, NQ >(a);
+            ElemArgs   ac       = a;
+            ac.n_cols           = one_pass ? R : 1;
+            const int rc        = describeSumfactFast< T, P, NQ >(ac, buf, n);
+            if (rc == 0 && !one_pass)
                 std::snprintf(buf + std::strlen(buf), n - std::strlen(buf), "; %d launches, one per column", R);
             return rc;
         };

@@ -359,18 +359,8 @@ int launchValuesAtNodes(const ElemArgs& a, const void* kparam_blob, hipStream_t 
         return 0;
     constexpr int    FA  = K::params.n_fields > 0 ? K::params.n_fields : 1;
     constexpr size_t lds = sizeof(double) * (size_t(FA) * (P + 1) * (P + 1) * (P + 1) + 24);
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-    hipLaunchKernelGGL((valuesAtNodesKernel< K, P, NQ, SIDE >), dim3(static_cast< unsigned >(count)), dim3(integral_threads), lds,
-                       stream, a, kern);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("valuesAtNodesKernel launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
-    return 0;
+    return launchKernel("valuesAtNodesKernel", valuesAtNodesKernel< K, P, NQ, SIDE >, dim3(static_cast< unsigned >(count)),
+                        dim3(integral_threads), lds, stream, a, functorFrom< K >(kparam_blob));
 }
 // side = a.face_count > 0 selects the boundary form
 template < typename K, int P, int NQ >
@@ -388,34 +378,14 @@ int launchIntegral(const ElemArgs& a, const void* kparam_blob, hipStream_t strea
         return 0;
     constexpr size_t lds = sizeof(double) * (SIDE ? integralSideLdsDoubles< K, P, NQ >() : integralLdsDoubles< K, P, NQ >());
     static_assert(lds <= lds_limit_bytes, "integral working set exceeds 160 KiB of LDS");
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
     auto kernel = [] {
         if constexpr (SIDE)
             return integralSideKernel< K, P, NQ >;
         else
             return integralDomainKernel< K, P, NQ >;
     }();
-    static bool attr_set = false;
-    if (!attr_set)
-    {
-        if (hipFuncSetAttribute(reinterpret_cast< const void* >(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(lds)) != hipSuccess)
-        {
-            setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
-            return -3;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3(static_cast< unsigned >(count)), dim3(integral_threads), lds, stream, a, kern);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("integral kernel launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
-    return 0;
+    return launchKernel("integral kernel", kernel, dim3(static_cast< unsigned >(count)), dim3(integral_threads), lds, stream, a,
+                        functorFrom< K >(kparam_blob));
 }
 } // namespace l3k::dev
 #endif

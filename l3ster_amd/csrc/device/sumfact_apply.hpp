@@ -12,7 +12,7 @@
 #ifndef L3K_DEVICE_SUMFACT_APPLY_HPP
 #define L3K_DEVICE_SUMFACT_APPLY_HPP
 
-#include "common.hpp"
+#include "launch.hpp"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
@@ -492,63 +492,26 @@ int launchSumfactApply(const ElemArgs& a, const void* kparam_blob, hipStream_t s
     }
     else if constexpr (applyLdsBytes< K, P, NQ, R >() > lds_limit_bytes)
     {
-        // one column and still too large for the LDS: the global-scratch variant, persistent workgroups (two per CU: no LDS, the
-        // registers admit them), each on its own slice of the context's scratch arena
-        K kern{};
-        if (kparam_blob)
-            __builtin_memcpy(&kern, kparam_blob, sizeof(K));
+        // one column and still too large for the LDS: the global-scratch variant (scratchGrid)
         constexpr size_t ws = applyLdsBytes< K, P, NQ, R >();
-        const int64_t    max_wgs = 2 * int64_t(deviceComputeUnits());
-        const unsigned   grid = static_cast< unsigned >(a.elem_count < max_wgs ? a.elem_count : max_wgs);
         if (!a.scratch_alloc)
         {
             setError("this shape needs %zu bytes per element in global scratch (its buffers exceed the LDS) and the caller gave no arena", ws);
             return -3;
         }
-        ElemArgs ag = a;
-        ag.scratch  = a.scratch_alloc(a.scratch_owner, ws * grid);
+        ElemArgs       ag   = a;
+        const unsigned grid = scratchGrid(ag, ws);
         if (!ag.scratch)
         {
             setError("could not allocate %zu bytes of global scratch for the element kernel", ws * grid);
             return -3;
         }
-        hipLaunchKernelGGL((sumfactApplyKernel< K, P, NQ, R, RHS_MODE, RT, C0, true >), dim3(grid), dim3(applyThreads< P, NQ >()), 0, stream, ag, kern);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess)
-        {
-            setError("sumfactApplyKernel (global scratch) launch failed: %s", hipGetErrorString(err));
-            return -3;
-        }
-        return 0;
+        return launchKernel("sumfactApplyKernel (global scratch)", sumfactApplyKernel< K, P, NQ, R, RHS_MODE, RT, C0, true >, dim3(grid),
+                            dim3(applyThreads< P, NQ >()), 0, stream, ag, functorFrom< K >(kparam_blob));
     }
     else
-    {
-        K kern{};
-        if (kparam_blob)
-            __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-        constexpr size_t lds      = applyLdsBytes< K, P, NQ, R >();
-        auto             kernel   = sumfactApplyKernel< K, P, NQ, R, RHS_MODE, RT, C0 >;
-        static bool      attr_set = false;
-        if (!attr_set)
-        {
-            if (hipFuncSetAttribute(reinterpret_cast< const void* >(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    int(lds)) != hipSuccess)
-            {
-                setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
-                return -3;
-            }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(static_cast< unsigned >(a.elem_count)), dim3(applyThreads< P, NQ >()), lds, stream,
-                           a, kern);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess)
-        {
-            setError("sumfactApplyKernel launch failed: %s", hipGetErrorString(err));
-            return -3;
-        }
-        return 0;
-    }
+        return launchKernel("sumfactApplyKernel", sumfactApplyKernel< K, P, NQ, R, RHS_MODE, RT, C0 >, dim3(static_cast< unsigned >(a.elem_count)),
+                            dim3(applyThreads< P, NQ >()), applyLdsBytes< K, P, NQ, R >(), stream, a, functorFrom< K >(kparam_blob));
 }
 } // namespace l3k::dev
 #endif

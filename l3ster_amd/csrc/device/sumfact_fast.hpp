@@ -26,8 +26,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
-#include <vector>
 #include <type_traits>
 
 namespace l3k::dev
@@ -1337,11 +1335,11 @@ struct FastRoute
     int64_t  n_batches = 0;
 };
 template < typename K, int P, int NQ, bool MULTI >
-int planSumfactFast(const ElemArgs& a, FastRoute& r)
+FastRoute planSumfactFast(const ElemArgs& a)
 {
     using Cfg = FastCfg< K, P, NQ >;
     const l3k_tuning& tune = tuneOf(a);
-    r       = FastRoute{};
+    FastRoute         r;
     r.multi = MULTI;
     // Small launches are latency-bound: one element takes ~23 us through a single wave here, ~15 us through the 6-wave
     // workgroup of the generic kernel; below ~3 elements per CU the generic kernel wins (profiles/r01_kbench_small_meshes.log:
@@ -1352,7 +1350,7 @@ int planSumfactFast(const ElemArgs& a, FastRoute& r)
     if ((!a.dense && (MULTI || a.fuse_beta)) || (generic_fits && a.elem_count < tune.generic_below))
     {
         r.generic = true;
-        return 0;
+        return r;
     }
     r.strided = !a.dense;
     // (ghost rows directly behind the owned rows of every column: one base pointer per column serves both)
@@ -1362,63 +1360,10 @@ int planSumfactFast(const ElemArgs& a, FastRoute& r)
     // (the affine variant exists for the plain apply: no ghost buffers, no fused energy)
     r.affine = !MULTI && a.all_affine && !r.split && !a.energy && !tune.no_affine && !r.strided;
     r.energy = !MULTI && a.energy != nullptr && !r.strided;
-    // launch configuration per device (several contexts of one process may sit on different GPUs): the dynamic-LDS
-    // attribute of the variants is set once on each device, under a lock
-    struct PerDevice
-    {
-        bool ready = false;
-        int  n_cus = 0, waves_cu = 0;
-    };
-    static PerDevice  per_device[64];
-    static std::mutex per_device_mutex;
-    int               dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64)
-    {
-        setError("device index %d not supported", dev);
-        return -3;
-    }
-    {
-        std::lock_guard< std::mutex > lock{per_device_mutex};
-        PerDevice&                    pd = per_device[dev];
-        if (!pd.ready)
-        {
-            std::vector< const void* > variants;
-            if constexpr (MULTI)
-                variants = {reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, true, false, false, true >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, false, false, true >)};
-            else
-                variants = {reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, true, true >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, true >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, true, false >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, false >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, false, true >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, true, false, false, false, true >),
-                            reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, false, false, false, true >)};
-            bool ok = true;
-            for (const void* f : variants)
-                ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(Cfg::lds)) == hipSuccess;
-            if (!ok)
-            {
-                setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", Cfg::lds);
-                return -3;
-            }
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, dev) != hipSuccess)
-            {
-                setError("hipGetDeviceProperties failed");
-                return -3;
-            }
-            pd.n_cus = prop.multiProcessorCount;
-            // resident single-wave workgroups per CU: limited by LDS (160 KiB) and by the VGPR budget (min_waves per SIMD)
-            const int by_lds = int((160 * 1024) / Cfg::lds);
-            pd.waves_cu      = by_lds < 1 ? 1 : (by_lds > 4 * Cfg::wavesPerSimd(MULTI) ? 4 * Cfg::wavesPerSimd(MULTI) : by_lds);
-            pd.ready         = true;
-        }
-        r.n_cus = pd.n_cus, r.waves_cu = pd.waves_cu;
-    }
-    if (tune.waves_per_cu > 0)
-        r.waves_cu = tune.waves_per_cu;
+    // resident single-wave workgroups per CU: limited by LDS (160 KiB) and by the VGPR budget (min_waves per SIMD)
+    constexpr int by_lds = int((160 * 1024) / Cfg::lds), by_vgprs = 4 * Cfg::wavesPerSimd(MULTI);
+    r.n_cus              = deviceComputeUnits();
+    r.waves_cu           = tune.waves_per_cu > 0 ? tune.waves_per_cu : (by_lds < 1 ? 1 : (by_lds > by_vgprs ? by_vgprs : by_lds));
     r.n_batches              = (a.elem_count + Cfg::EW - 1) / Cfg::EW;
     const int64_t max_blocks = int64_t(r.n_cus) * r.waves_cu;
     r.grid                   = static_cast< unsigned >(r.n_batches < max_blocks ? r.n_batches : max_blocks);
@@ -1427,55 +1372,33 @@ int planSumfactFast(const ElemArgs& a, FastRoute& r)
     // one XCD are neighbours: their atomics meet on the same lines) -- hence orders >= 6 only
     r.xcd_chunk = (P >= 6 && r.grid % 8 == 0 && r.n_batches >= int64_t(r.grid) && r.n_batches < (int64_t(1) << 30)) ? int((r.n_batches + 7) / 8) : 0;
     r.dynamic   = a.work_counters != nullptr;
-    return 0;
+    return r;
 }
 
-template < typename K, int P, int NQ, bool MULTI >
-int launchSumfactFastImpl(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)
+// the variant of the single-wave kernel a planned launch runs (RHS: the right-hand side with Dirichlet lifting)
+template < typename K, int P, int NQ, bool RHS >
+auto fastKernel(const FastRoute& r) -> decltype(&sumfactFastKernel< K, P, NQ, false, false >)
 {
-    using Cfg = FastCfg< K, P, NQ >;
-    if (a.elem_count <= 0)
-        return 0;
-    if (MULTI && a.n_cols < 1)
-    {
-        setError("multi-column element launch without a column count");
-        return -1;
-    }
-    FastRoute r;
-    if (int rc = planSumfactFast< K, P, NQ, MULTI >(a, r))
-        return rc;
-    if (r.generic)
-    {
-        if constexpr (!MULTI)
-            return launchSumfactApply< K, P, NQ, 1, false >(a, kparam_blob, stream);
-        else
-        {
-            for (int c = 0; c < a.n_cols; ++c) // column by column through the generic single-column kernel
-            {
-                ElemArgs ac = a;
-                ac.n_cols   = 1;
-                ac.x        = a.x + a.ldx * c;
-                ac.xg       = a.xg ? a.xg + a.ldxg * c : nullptr;
-                ac.y        = a.y + a.ldy * c;
-                ac.yg       = a.yg ? a.yg + a.ldyg * c : nullptr;
-                if (int rc = launchSumfactApply< K, P, NQ, 1, false >(ac, kparam_blob, stream))
-                    return rc;
-            }
-            return 0;
-        }
-    }
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-    decltype(&sumfactFastKernel< K, P, NQ, false, false >) kernel;
-    if constexpr (MULTI) // (no fused energy, no affine variant: plain applies of several columns)
-        kernel = r.split ? sumfactFastKernel< K, P, NQ, true, false, false, true > : sumfactFastKernel< K, P, NQ, false, false, false, true >;
-    else if (r.strided)
-        kernel = r.split ? sumfactFastKernel< K, P, NQ, true, false, false, false, true > : sumfactFastKernel< K, P, NQ, false, false, false, false, true >;
+    if constexpr (RHS)
+        return r.split ? sumfactFastKernel< K, P, NQ, true, false, false, false, false, true >
+                       : sumfactFastKernel< K, P, NQ, false, false, false, false, false, true >;
     else
-        kernel = r.affine ? sumfactFastKernel< K, P, NQ, false, false, true >
-                 : r.energy ? (r.split ? sumfactFastKernel< K, P, NQ, true, true > : sumfactFastKernel< K, P, NQ, false, true >)
-                            : (r.split ? sumfactFastKernel< K, P, NQ, true, false > : sumfactFastKernel< K, P, NQ, false, false >);
+    {
+        if constexpr (FastCfg< K, P, NQ >::multi_column)
+            if (r.multi) // (no fused energy, no affine variant: plain applies of several columns)
+                return r.split ? sumfactFastKernel< K, P, NQ, true, false, false, true > : sumfactFastKernel< K, P, NQ, false, false, false, true >;
+        if (r.strided)
+            return r.split ? sumfactFastKernel< K, P, NQ, true, false, false, false, true > : sumfactFastKernel< K, P, NQ, false, false, false, false, true >;
+        return r.affine ? sumfactFastKernel< K, P, NQ, false, false, true >
+               : r.energy ? (r.split ? sumfactFastKernel< K, P, NQ, true, true > : sumfactFastKernel< K, P, NQ, false, true >)
+                          : (r.split ? sumfactFastKernel< K, P, NQ, true, false > : sumfactFastKernel< K, P, NQ, false, false >);
+    }
+}
+
+// one planned launch of the single-wave kernel: the 1-D tables into the kernel arguments, the work counters reset, the launch
+template < typename K, int P, int NQ, bool RHS >
+int launchFastKernel(const ElemArgs& a, const FastRoute& r, const void* kparam_blob, hipStream_t stream)
+{
     constexpr TableLayout   TL{P + 1, NQ};
     FastTables< P + 1, NQ > tab;
     const double*           th = a.tables_host;
@@ -1490,26 +1413,44 @@ int launchSumfactFastImpl(const ElemArgs& a, const void* kparam_blob, hipStream_
         setError("hipMemsetAsync(work counters) failed");
         return -3;
     }
-    hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(64), Cfg::lds, stream, a, kern, r.n_batches, r.xcd_chunk, tab);
-    if (r.energy && a.energy_done)
-        ++*a.energy_done;
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
+    return launchKernel(RHS ? "sumfactFastKernel (rhs)" : "sumfactFastKernel", fastKernel< K, P, NQ, RHS >(r), dim3(r.grid), dim3(64),
+                        FastCfg< K, P, NQ >::lds, stream, a, functorFrom< K >(kparam_blob), r.n_batches, r.xcd_chunk, tab);
+}
+
+template < typename K, int P, int NQ, bool MULTI >
+int launchSumfactFastImpl(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)
+{
+    if (a.elem_count <= 0)
+        return 0;
+    if (MULTI && a.n_cols < 1)
     {
-        setError("sumfactFastKernel launch failed: %s", hipGetErrorString(err));
-        return -3;
+        setError("multi-column element launch without a column count");
+        return -1;
     }
-    return 0;
+    const FastRoute r = planSumfactFast< K, P, NQ, MULTI >(a);
+    if (r.generic)
+    {
+        if constexpr (!MULTI)
+            return launchSumfactApply< K, P, NQ, 1, false >(a, kparam_blob, stream);
+        else
+        {
+            ElemArgs a1 = a; // column by column through the generic single-column kernel
+            a1.n_cols   = 1;
+            return forEachColumn(a1, a.n_cols, [&](const ElemArgs& ac) { return launchSumfactApply< K, P, NQ, 1, false >(ac, kparam_blob, stream); });
+        }
+    }
+    const int rc = launchFastKernel< K, P, NQ, false >(a, r, kparam_blob, stream);
+    if (rc == 0 && r.energy && a.energy_done)
+        ++*a.energy_done;
+    return rc;
 }
 // the route of an apply launch as text (l3k_mf_route): which kernel template, which variant, how it is launched
 template < typename K, int P, int NQ >
 int describeSumfactFast(const ElemArgs& a, char* buf, size_t n)
 {
     using Cfg = FastCfg< K, P, NQ >;
-    FastRoute r;
-    const bool multi = Cfg::multi_column && a.n_cols > 1;
-    if (int rc = multi ? planSumfactFast< K, P, NQ, Cfg::multi_column >(a, r) : planSumfactFast< K, P, NQ, false >(a, r))
-        return rc;
+    const bool      multi = Cfg::multi_column && a.n_cols > 1;
+    const FastRoute r     = multi ? planSumfactFast< K, P, NQ, Cfg::multi_column >(a) : planSumfactFast< K, P, NQ, false >(a);
     if (r.generic)
         return describeSumfactApply< K, P, NQ, 1 >(a, buf, n);
     std::snprintf(buf, n,
@@ -1525,7 +1466,6 @@ int describeSumfactFast(const ElemArgs& a, char* buf, size_t n)
 template < typename K, int P, int NQ >
 int launchSumfactFastRhs(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)
 {
-    using Cfg = FastCfg< K, P, NQ >;
     if (a.elem_count <= 0)
         return 0;
     if (!a.dense || a.local_out || a.n_cols > 1)
@@ -1537,57 +1477,10 @@ int launchSumfactFastRhs(const ElemArgs& a, const void* kparam_blob, hipStream_t
     ar.beta      = 1.;
     ar.x         = a.y; // (unused by the gather; the pointer relations below decide the ghost-buffer variant)
     ar.xg        = a.yg;
-    FastRoute r;
-    if (int rc = planSumfactFast< K, P, NQ, false >(ar, r))
-        return rc;
+    const FastRoute r = planSumfactFast< K, P, NQ, false >(ar);
     if (r.generic)
         return 1;
-    {
-        static std::mutex attr_mutex;
-        static bool       attr_set[64] = {};
-        int               dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard< std::mutex > lock{attr_mutex};
-        if (dev >= 0 && dev < 64 && !attr_set[dev])
-        {
-            if (hipFuncSetAttribute(reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, true, false, false, false, false, true >),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(Cfg::lds)) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast< const void* >(sumfactFastKernel< K, P, NQ, false, false, false, false, false, true >),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(Cfg::lds)) != hipSuccess)
-            {
-                setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", Cfg::lds);
-                return -3;
-            }
-            attr_set[dev] = true;
-        }
-    }
-    K kern{};
-    if (kparam_blob)
-        __builtin_memcpy(&kern, kparam_blob, sizeof(K));
-    auto kernel = r.split ? sumfactFastKernel< K, P, NQ, true, false, false, false, false, true >
-                          : sumfactFastKernel< K, P, NQ, false, false, false, false, false, true >;
-    constexpr TableLayout   TL{P + 1, NQ};
-    FastTables< P + 1, NQ > tab;
-    const double*           th = a.tables_host;
-    __builtin_memcpy(tab.eoI, th + TL.offEoI(), sizeof tab.eoI);
-    __builtin_memcpy(tab.eoC, th + TL.offEoC(), sizeof tab.eoC);
-    __builtin_memcpy(tab.eoIt, th + TL.offEoIt(), sizeof tab.eoIt);
-    __builtin_memcpy(tab.eoCt, th + TL.offEoCt(), sizeof tab.eoCt);
-    __builtin_memcpy(tab.qw, th + TL.offW(), sizeof tab.qw);
-    __builtin_memcpy(tab.qx, th + TL.offX(), sizeof tab.qx);
-    if (ar.work_counters && hipMemsetAsync(ar.work_counters, 0, 8 * 128, stream) != hipSuccess)
-    {
-        setError("hipMemsetAsync(work counters) failed");
-        return -3;
-    }
-    hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(64), Cfg::lds, stream, ar, kern, r.n_batches, r.xcd_chunk, tab);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-    {
-        setError("sumfactFastKernel (rhs) launch failed: %s", hipGetErrorString(err));
-        return -3;
-    }
-    return 0;
+    return launchFastKernel< K, P, NQ, true >(ar, r, kparam_blob, stream);
 }
 template < typename K, int P, int NQ >
 int launchSumfactFast(const ElemArgs& a, const void* kparam_blob, hipStream_t stream)

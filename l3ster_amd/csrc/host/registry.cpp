@@ -2,6 +2,7 @@
 #include "../device/common.hpp"
 
 #include <cstdarg>
+#include <map>
 #include <mutex>
 #include <cstdio>
 #include <string>
@@ -51,6 +52,21 @@ int deviceComputeUnits()
         cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     return cus[dev];
+}
+bool allowDynamicLds(const void* fn, size_t bytes)
+{
+    static std::map< std::pair< const void*, int >, size_t > allowed; // (function, device) -> bytes
+    static std::mutex                                        m;
+    int                                                      dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard< std::mutex > lock{m};
+    size_t&                       have = allowed[{fn, dev}];
+    if (bytes <= have)
+        return true;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)) != hipSuccess)
+        return false;
+    have = bytes;
+    return true;
 }
 const l3k_tuning& defaultTuning()
 {
