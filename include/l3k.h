@@ -24,6 +24,9 @@ extern "C" {
 
 /* 101 (round 4): l3k_cg_update_xr / _update_p replaced by l3k_cg_update_z / _update_px (the iteration keeps z = M^-1 r; d_r holds z),
  * new: l3k_ctx_set_reference_z0, l3k_ctx_get/set_tuning, l3k_mf_route, l3k_update_solution, l3k_pcg_solve_cols */
+/* Quadrilateral meshes (dim = 2) on the device -- l3k_mesh_create, the matrix-free apply and l3k_mf_diag_rhs, kernels
+ * L3K_KERNEL_DIFFUSION2D / _VAR, l3k_square_mesh_create -- are additions only: no existing entry point changed, so the
+ * version stays (tests/test_cabi_cpu.py pins it). */
 #define L3K_VERSION 101
 
 typedef struct l3k_ctx      l3k_ctx;
@@ -71,6 +74,8 @@ enum
 {
     L3K_KERNEL_DIFFUSION3D     = 0, /* benchmarks/Diffusion3D.hpp:51-79; params {double k, s}                        */
     L3K_KERNEL_DIFFUSION3D_VAR = 1, /* tests/Kernels.hpp:84-118, n_fields = 1                                          */
+    L3K_KERNEL_DIFFUSION2D     = 2, /* tests/Kernels.hpp:5-24: quads, E = 4, U = 3 (T, qx, qy), zero rhs              */
+    L3K_KERNEL_DIFFUSION2D_VAR = 3, /* tests/Kernels.hpp:27-52: quads, n_fields = 1 (diffusivity, value + derivatives) */
     L3K_KERNEL_ADVDIFF3D       = 4, /* config-5 synthetic; params {double k, sigma, s}, n_fields = 3 */
     /* boundary equation kernels (wrapBoundaryEquationKernel: the input carries the outward normal); l3k_bnd_create */
     L3K_KERNEL_ADIABATIC3D     = 6, /* 3-D twin of tests/Kernels.hpp:120-128: q.n = 0                                 */
@@ -150,12 +155,14 @@ int l3k_ctx_destroy(l3k_ctx* ctx);
  * (dofs/NodeToDofMap.hpp:84-109) and LocalDirichletBC (bcs/LocalDirichletBC.hpp:13-32), flattened.  Uploaded once. */
 typedef struct
 {
-    int             dim;            /* 3 (hex)                                                                      */
+    int             dim;            /* 3 (hex) or 2 (quad: apply and diag / rhs only; no LocalAssembly, boundary
+                                       kernels, integrals or values at nodes on quads)                                 */
     int             order;          /* p; nodes per element N = (p+1)^dim, lexicographic, xi fastest               */
     int64_t         n_elems;        /* elements [0, n_interior_elems) touch owned dofs only, the rest are "border" */
     int64_t         n_interior_elems; /* splitBorderAndInterior, algsys/MatrixFreeSystem.hpp:969-981              */
     const uint32_t* elem_nodes;     /* [n_elems][N] local node ids (n_loc_id_t, common/Typedefs.h:14)              */
-    const double*   elem_verts;     /* [n_elems][2^dim][3], vertex v = i + 2j + 4k (mesh/primitives/CubeMesh.hpp)  */
+    const double*   elem_verts;     /* [n_elems][2^dim][3], vertex v = i + 2j + 4k (mesh/primitives/CubeMesh.hpp);
+                                       quads: [n_elems][4][3], v = i + 2j, z ignored                                   */
     int64_t         n_owned_nodes;  /* local node numbering: owned first, then ghosts (LocalMeshView.hpp:425-458)  */
     int64_t         n_ghost_nodes;
     int             dofs_per_node;  /* dof(node,k) = node*dofs_per_node + k (dofs/NodeToDofMap.hpp:250-264)        */
@@ -455,6 +462,12 @@ int     l3k_mf_apply_dist(l3k_mf* mf, l3k_halo* halo, const double* d_x, size_t 
  * perturb: vertices moved by perturb*h*sin(2 pi x)sin(2 pi y)sin(2 pi z).  Host only, no GPU. */
 int l3k_cube_partition_create(const int ne[3], int order, const int parts[3], int rank, double perturb,
                               l3k_hostmesh** out);
+/* The quad counterpart (makeSquareMesh, mesh/primitives/SquareMesh.hpp, + convertMeshToOrder): ne[2] elements per edge on
+ * [0,1]^2, order p, a single part without ghosts, numbered [non-internal nodes | element-internal nodes, contiguous per element
+ * and lexicographic].  dim = 2, elem_verts [n][4][3] with z = 0, node_grid_id = gx + NX*gy, boundary bits in the quad side
+ * order 0 y=0, 1 y=1, 2 x=0, 3 x=1 (mesh/ElementTraits.hpp:84-95).  perturb: interior vertices moved by
+ * perturb*h*sin(2 pi x)sin(2 pi y) in x and y (detJ > 0 for |perturb| < 1/4).  Host only, no GPU. */
+int l3k_square_mesh_create(const int ne[2], int order, double perturb, l3k_hostmesh** out);
 int l3k_hostmesh_destroy(l3k_hostmesh* hm);
 typedef struct
 {
@@ -464,7 +477,7 @@ typedef struct
     int64_t         global_node_base;      /* first global node id owned by this rank (contiguous ownership)        */
     int64_t         n_global_nodes;
     const uint32_t* elem_nodes;            /* [n_elems][N], interior elements first                                  */
-    const double*   elem_verts;            /* [n_elems][8][3]                                                        */
+    const double*   elem_verts;            /* [n_elems][2^dim][3]                                                    */
     const int64_t*  node_grid_id;          /* [n_owned+n_ghost] partition-independent id gx + NX*(gy + NY*gz)        */
     const uint8_t*  node_boundary;         /* [n_owned+n_ghost] bit s set if the node lies on cube side s            */
                                            /* sides: 0 z=0, 1 z=1, 2 y=0, 3 y=1, 4 x=0, 5 x=1 (ElementTraits.hpp:84-95) */

@@ -172,6 +172,7 @@ SIGNATURES = {
     "l3k_cg_update_z": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_px": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
+    "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),
     "l3k_hostmesh_view_get": (C.c_int, [_vp, C.POINTER(HostMeshView)]),
     "l3k_elevate_order": (C.c_int, [_vp, C.c_int64, c_uint32_p, C.c_int64, C.c_int, c_uint32_p, c_int64_p, c_int64_p]),

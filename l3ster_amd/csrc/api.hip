@@ -448,10 +448,10 @@ namespace
 // one class adds at most once to any row, so the order of the additions to a row is the order of the launches.
 int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vector< uint8_t >& flags)
 {
-    const int     n1 = d->order + 1;
-    const int64_t N  = int64_t(n1) * n1 * n1;
+    const int     n1 = d->order + 1, nv = 1 << d->dim; // (quads: the 4 corners, v = i + 2j)
+    const int64_t N  = d->dim == 2 ? int64_t(n1) * n1 : int64_t(n1) * n1 * n1;
     int           corner[8];
-    for (int v = 0; v < 8; ++v)
+    for (int v = 0; v < nv; ++v)
         corner[v] = ((v & 1) ? n1 - 1 : 0) + n1 * (((v >> 1) & 1) ? n1 - 1 : 0) + n1 * n1 * (((v >> 2) & 1) ? n1 - 1 : 0);
     std::unordered_map< uint32_t, uint64_t > used; // corner node -> colours taken by the elements around it
     used.reserve(static_cast< size_t >(d->n_elems) * 2);
@@ -460,7 +460,7 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
     for (int64_t e = 0; e < d->n_elems; ++e)
     {
         uint64_t taken = 0;
-        for (int v = 0; v < 8; ++v)
+        for (int v = 0; v < nv; ++v)
         {
             const auto it = used.find(d->elem_nodes[e * N + corner[v]]);
             if (it != used.end())
@@ -476,13 +476,16 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
         }
         colour[e] = uint8_t(c);
         n_colours = std::max(n_colours, c + 1);
-        for (int v = 0; v < 8; ++v)
+        for (int v = 0; v < nv; ++v)
             used[d->elem_nodes[e * N + corner[v]]] |= uint64_t(1) << c;
     }
-    m.det_corner_nodes.resize(static_cast< size_t >(d->n_elems) * 8);
-    for (int64_t e = 0; e < d->n_elems; ++e)
-        for (int v = 0; v < 8; ++v)
-            m.det_corner_nodes[size_t(e) * 8 + v] = d->elem_nodes[e * N + corner[v]];
+    if (d->dim == 3) // (the colouring of boundary sides; quads have no boundary terms on the device)
+    {
+        m.det_corner_nodes.resize(static_cast< size_t >(d->n_elems) * 8);
+        for (int64_t e = 0; e < d->n_elems; ++e)
+            for (int v = 0; v < 8; ++v)
+                m.det_corner_nodes[size_t(e) * 8 + v] = d->elem_nodes[e * N + corner[v]];
+    }
     std::vector< int64_t > order(static_cast< size_t >(d->n_elems));
     for (int64_t e = 0; e < d->n_elems; ++e)
         order[e] = e;
@@ -503,13 +506,14 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
         }
     }
     std::vector< uint32_t > nodes(static_cast< size_t >(d->n_elems * N));
-    std::vector< double >   verts(static_cast< size_t >(d->n_elems) * 24);
+    const int               nvd = nv * 3; // vertex doubles per element
+    std::vector< double >   verts(static_cast< size_t >(d->n_elems) * nvd);
     std::vector< uint8_t >  fl(flags.empty() ? 0 : static_cast< size_t >(d->n_elems));
     for (int64_t i = 0; i < d->n_elems; ++i)
     {
         const int64_t e = order[i];
         std::copy_n(d->elem_nodes + e * N, N, nodes.begin() + i * N);
-        std::copy_n(d->elem_verts + e * 24, 24, verts.begin() + i * 24);
+        std::copy_n(d->elem_verts + e * nvd, nvd, verts.begin() + i * nvd);
         if (!fl.empty())
             fl[i] = flags[e];
     }
@@ -801,9 +805,9 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
         setError("l3k_mesh_create: null argument");
         return -1;
     }
-    if (d->dim != 3)
+    if (d->dim != 2 && d->dim != 3)
     {
-        setError("device kernels exist for hex elements only (dim = 3); quads are covered by the CPU oracle");
+        setError("l3k_mesh_create: dim must be 2 (quads) or 3 (hexes), got %d", d->dim);
         return -1;
     }
     if (d->order < 1 || d->n_elems < 0 || d->n_interior_elems < 0 || d->n_interior_elems > d->n_elems ||
@@ -812,7 +816,9 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
         setError("l3k_mesh_create: inconsistent descriptor");
         return -1;
     }
-    const int64_t N       = int64_t(d->order + 1) * (d->order + 1) * (d->order + 1);
+    const int     dim     = d->dim;
+    const int64_t N       = dim == 2 ? int64_t(d->order + 1) * (d->order + 1) : int64_t(d->order + 1) * (d->order + 1) * (d->order + 1);
+    const int     nvd     = (1 << dim) * 3; // vertex coordinates per element: [2^dim][3]
     const int64_t n_nodes = d->n_owned_nodes + d->n_ghost_nodes;
     if (n_nodes * d->dofs_per_node >= (int64_t(1) << 31) * 8)
     {
@@ -839,7 +845,7 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
     m->n_ghost_nodes = d->n_ghost_nodes;
     if (int rc = m->elem_nodes.upload(d->elem_nodes, size_t(d->n_elems * N), ctx->stream))
         return rc;
-    if (int rc = m->elem_verts.upload(d->elem_verts, size_t(d->n_elems) * 24, ctx->stream))
+    if (int rc = m->elem_verts.upload(d->elem_verts, size_t(d->n_elems) * nvd, ctx->stream))
         return rc;
     // nodes referenced by exactly one element (the element-internal nodes of the reference's numbering,
     // mesh/LocalMeshView.hpp:425-458) can be scattered with plain stores: find the maximal owned tail range
@@ -859,6 +865,8 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
         const int n1 = d->order + 1;
         auto      internal = [&](int64_t i) {
             const int ix = int(i % n1), iy = int((i / n1) % n1), iz = int(i / (n1 * n1));
+            if (dim == 2)
+                return ix > 0 && ix < n1 - 1 && iy > 0 && iy < n1 - 1;
             return ix > 0 && ix < n1 - 1 && iy > 0 && iy < n1 - 1 && iz > 0 && iz < n1 - 1;
         };
         int64_t max_shell = -1, min_internal = n_nodes;
@@ -875,8 +883,9 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
         if (d->n_elems == 0 || d->order < 2 || min_internal < m->exclusive_begin)
             m->exclusive_begin = m->exclusive_end; // empty: every node is scattered with atomics
         // scatter slots: local nodes of a typical element (the middle one of the traversal) in ascending id order --
-        // rows that are contiguous in y become contiguous slots; internal positions last
-        if (d->n_elems > 0 && n1 <= 8)
+        // rows that are contiguous in y become contiguous slots; internal positions last.  Hexes only: the quad kernel
+        // scatters in lexicographic order
+        if (dim == 3 && d->n_elems > 0 && n1 <= 8)
         {
             const uint32_t*        ids = d->elem_nodes + (d->n_elems / 2) * N;
             std::vector< int32_t > order(static_cast< size_t >(N));
@@ -907,8 +916,22 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
     std::vector< uint8_t > flags(static_cast< size_t >(d->n_elems), 0); // (host staging: outlives the synchronisation below)
     for (int64_t e = 0; e < d->n_elems; ++e)
     {
-        const double* v = d->elem_verts + e * 24;
+        const double* v = d->elem_verts + e * nvd;
         double        scale = 0., dev = 0.;
+        if (dim == 2) // bilinear quad: a parallelogram when the coefficient of xi*eta vanishes
+        {
+            for (int s = 0; s < 2; ++s)
+            {
+                const double c10 = -v[0 * 3 + s] + v[1 * 3 + s] - v[2 * 3 + s] + v[3 * 3 + s];
+                const double c01 = -v[0 * 3 + s] - v[1 * 3 + s] + v[2 * 3 + s] + v[3 * 3 + s];
+                const double c11 = v[0 * 3 + s] - v[1 * 3 + s] - v[2 * 3 + s] + v[3 * 3 + s];
+                scale            = std::max({scale, std::fabs(c10), std::fabs(c01)});
+                dev              = std::max(dev, std::fabs(c11));
+            }
+            if (dev <= 1e-14 * scale)
+                flags[e] |= 2;
+            continue;
+        }
         for (int s = 0; s < 3; ++s)
         {
             auto c = [&](int sx, int sy, int sz) { // coefficient of xi^sx eta^sy zeta^sz (x 8)
@@ -1511,6 +1534,8 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
         return -1;
     }
     const l3k_mesh* m = mf->mesh;
+    if (int rc = refuseQuads(m, "l3k_local_assemble"))
+        return rc;
     if (first < 0 || count < 0 || first + count > m->n_elems)
     {
         setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
@@ -1596,6 +1621,8 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
         return -1;
     }
     const l3k_mesh* m = mf->mesh;
+    if (int rc = refuseQuads(m, "l3k_local_assemble_tiled"))
+        return rc;
     if (first < 0 || count < 0 || first + count > m->n_elems)
     {
         setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
@@ -1657,6 +1684,8 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
         return -1;
     }
     const l3k_mesh* m = mf->mesh;
+    if (int rc = refuseQuads(m, "l3k_assemble_global"))
+        return rc;
     if (first < 0 || count < 0 || first + count > m->n_elems)
     {
         setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
@@ -1804,6 +1833,8 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
         setError("l3k_bnd_create: bad argument");
         return -1;
     }
+    if (int rc = refuseQuads(mesh, "l3k_bnd_create"))
+        return rc;
     const auto* k = findKernel(kernel_id);
     if (!k || !k->boundary)
     {

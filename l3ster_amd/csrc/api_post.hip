@@ -65,6 +65,8 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
         setError("l3k_integrate: bad argument");
         return -1;
     }
+    if (int rc = refuseQuads(mesh, "l3k_integrate"))
+        return rc;
     const auto* k = findResidual(residual_id);
     if (!k)
     {
@@ -163,6 +165,8 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
         setError("l3k_values_at_nodes: bad argument");
         return -1;
     }
+    if (int rc = refuseQuads(mesh, "l3k_values_at_nodes"))
+        return rc;
     const auto* k = findResidual(residual_id);
     if (!k)
     {

@@ -13,6 +13,7 @@
 #include "assemble.hpp"
 #include "boundary.hpp"
 #include "integral.hpp"
+#include "quad.hpp"
 
 namespace l3k::dev
 {
@@ -98,6 +99,24 @@ constexpr RouteFn selectRoute()
 }
 } // namespace l3k::dev
 
+namespace l3k::dev
+{
+// The registry entry of one (functor, order, nq, columns) shape: quads (dimension 2) take the kernels of quad.hpp and have no
+// LocalAssembly (assemble = nullptr); hexes the sum-factorised hex kernels.  `if constexpr` keeps the templates of the other
+// dimension uninstantiated.
+template < typename T, int P, int NQ, int R >
+Instance makeInstance()
+{
+    if constexpr (T::params.dimension == 2)
+        return {KernelId< T >::value, P, NQ, R, &launchQuadApply< T, P, NQ, R >, &launchQuadDiagRhs< T, P, NQ, R >, nullptr, 0, nullptr,
+                false, &describeQuadApply< T, P, NQ, R >};
+    else
+        return {KernelId< T >::value, P, NQ, R, selectApply< T, P, NQ, R >(), &launchDiagRhs< T, P, NQ, R >, &launchAssemble< T, P, NQ >,
+                assembleWorkspaceDoublesPerElem< T, P, NQ >(), selectApplyCols< T, P, NQ, R >(), SfAsmCfg< P, NQ >::feasible,
+                selectRoute< T, P, NQ, R >()};
+}
+} // namespace l3k::dev
+
 #define L3K_CAT2(a, b) a##b
 #define L3K_CAT(a, b) L3K_CAT2(a, b)
 #define L3K_INSTANTIATE(T, P, NQ, R)                                                                                   \
@@ -107,14 +126,7 @@ constexpr RouteFn selectRoute()
     {                                                                                                                  \
         L3K_CAT(Registrar_, __LINE__)()                                                                                \
         {                                                                                                              \
-            ::l3k::dev::registerInstance({::l3k::dev::KernelId< T >::value, P, NQ, R,                                  \
-                                          ::l3k::dev::selectApply< T, P, NQ, R >(),                                  \
-                                          &::l3k::dev::launchDiagRhs< T, P, NQ, R >,                               \
-                                          &::l3k::dev::launchAssemble< T, P, NQ >,                                 \
-                                          ::l3k::dev::assembleWorkspaceDoublesPerElem< T, P, NQ >(),               \
-                                          ::l3k::dev::selectApplyCols< T, P, NQ, R >(),                              \
-                                          ::l3k::dev::SfAsmCfg< P, NQ >::feasible,                                   \
-                                          ::l3k::dev::selectRoute< T, P, NQ, R >()});                                \
+            ::l3k::dev::registerInstance(::l3k::dev::makeInstance< T, P, NQ, R >());                                   \
         }                                                                                                              \
     } L3K_CAT(registrar_, __LINE__);                                                                                   \
     }

@@ -219,6 +219,7 @@ i64 ownedCount(const Layout& L, int rank)
 
 struct l3k_hostmesh
 {
+    int                     dim = 3;
     int                     order;
     i64                     n_elems = 0, n_interior = 0, n_owned = 0, n_ghost = 0, base = 0, n_global = 0;
     std::vector< uint32_t > elem_nodes;
@@ -479,6 +480,89 @@ extern "C" int l3k_cube_partition_create(const int ne[3], int order, const int p
     return 0;
 }
 
+// makeSquareMesh (mesh/primitives/SquareMesh.hpp) + convertMeshToOrder on one part: grid nodes on element edges first (grid
+// order, y slowest), then the (p-1)^2 internal nodes of every element, contiguous per element and lexicographic; elements
+// lexicographic (x fastest)
+extern "C" int l3k_square_mesh_create(const int ne[2], int order, double perturb, l3k_hostmesh** out)
+{
+    using l3k::dev::setError;
+    if (!ne || !out || order < 1 || order > 15 || ne[0] < 1 || ne[1] < 1)
+    {
+        setError("l3k_square_mesh_create: bad arguments (need ne[d] >= 1, 1 <= order <= 15)");
+        return -1;
+    }
+    const int p = order, n = p + 1, N = n * n;
+    const i64 NX = i64(p) * ne[0] + 1, NY = i64(p) * ne[1] + 1, n_elems = i64(ne[0]) * ne[1];
+    const i64 n_nodes = NX * NY;
+    if (n_nodes >= (i64(1) << 32))
+    {
+        setError("l3k_square_mesh_create: %lld nodes exceed the 32-bit local node ids", (long long)n_nodes);
+        return -1;
+    }
+    auto hm      = std::make_unique< l3k_hostmesh >();
+    hm->dim      = 2;
+    hm->order    = order;
+    hm->n_elems  = hm->n_interior = n_elems;
+    hm->n_owned  = hm->n_global = n_nodes;
+    hm->elem_nodes.resize(size_t(n_elems) * N);
+    hm->elem_verts.resize(size_t(n_elems) * 12);
+    hm->node_grid_id.assign(size_t(n_nodes), -1);
+    hm->node_boundary.assign(size_t(n_nodes), 0);
+    hm->elem_boundary.assign(size_t(n_elems), 0);
+    hm->send_offsets.push_back(0);
+    hm->ghost_offsets.push_back(0);
+    // non-internal grid nodes: those on a grid line of the element edges
+    const auto on_edge = [&](i64 g) { return g % p == 0; };
+    std::vector< i64 > shell_id(size_t(n_nodes), -1);
+    i64                next = 0;
+    for (i64 gy = 0; gy < NY; ++gy)
+        for (i64 gx = 0; gx < NX; ++gx)
+            if (on_edge(gx) || on_edge(gy))
+                shell_id[gy * NX + gx] = next++;
+    const i64    n_internal = i64(p - 1) * (p - 1);
+    const double h[2] = {1. / ne[0], 1. / ne[1]}, hmin = std::min(h[0], h[1]);
+    constexpr double twopi = 6.283185307179586476925286766559;
+    for (i64 ey = 0; ey < ne[1]; ++ey)
+        for (i64 ex = 0; ex < ne[0]; ++ex)
+        {
+            const i64 e    = ey * ne[0] + ex;
+            uint32_t* en   = hm->elem_nodes.data() + e * N;
+            int       c    = 0;
+            for (int j = 0; j < n; ++j)
+                for (int i = 0; i < n; ++i)
+                {
+                    const i64  gx = ex * p + i, gy = ey * p + j;
+                    const bool internal = i > 0 && i < p && j > 0 && j < p;
+                    const i64  id       = internal ? next + e * n_internal + c++ : shell_id[gy * NX + gx];
+                    en[i + n * j]       = static_cast< uint32_t >(id);
+                    hm->node_grid_id[id]  = gx + NX * gy;
+                    hm->node_boundary[id] = static_cast< uint8_t >((gy == 0) | ((gy == NY - 1) << 1) | ((gx == 0) << 2) | ((gx == NX - 1) << 3));
+                }
+            hm->elem_boundary[e] = static_cast< uint8_t >((ey == 0) | ((ey == ne[1] - 1) << 1) | ((ex == 0) << 2) | ((ex == ne[0] - 1) << 3));
+            double* ev = hm->elem_verts.data() + e * 12;
+            for (int v = 0; v < 4; ++v)
+            {
+                double x[2] = {(ex + (v & 1)) * h[0], (ey + (v >> 1)) * h[1]};
+                if (perturb != 0.)
+                {
+                    const double d = perturb * hmin * std::sin(twopi * x[0]) * std::sin(twopi * x[1]);
+                    x[0] += d;
+                    x[1] += d;
+                }
+                ev[v * 3 + 0] = x[0];
+                ev[v * 3 + 1] = x[1];
+                ev[v * 3 + 2] = 0.;
+            }
+        }
+    if (next + n_elems * n_internal != n_nodes)
+    {
+        setError("internal error: square mesh node count mismatch");
+        return -9;
+    }
+    *out = hm.release();
+    return 0;
+}
+
 extern "C" int l3k_hostmesh_destroy(l3k_hostmesh* hm)
 {
     delete hm;
@@ -492,7 +576,7 @@ extern "C" int l3k_hostmesh_view_get(const l3k_hostmesh* hm, l3k_hostmesh_view* 
         l3k::dev::setError("l3k_hostmesh_view_get: null argument");
         return -1;
     }
-    v->dim              = 3;
+    v->dim              = hm->dim;
     v->order            = hm->order;
     v->n_elems          = hm->n_elems;
     v->n_interior_elems = hm->n_interior;

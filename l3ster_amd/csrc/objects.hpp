@@ -159,6 +159,17 @@ struct l3k_mesh
     int64_t nOwnedDofs() const { return n_owned_nodes * dofs_per_node; }
     int64_t nLocalDofs() const { return (n_owned_nodes + n_ghost_nodes) * dofs_per_node; }
 };
+// Entry points without quad kernels (LocalAssembly, the assembled path, boundary terms, integrals, values at nodes) refuse quad
+// meshes up front: -1 and the reason, and no hex kernel ever sees quad data
+inline int refuseQuads(const l3k_mesh* m, const char* what)
+{
+    if (m && m->dim == 2)
+    {
+        setError("%s: quads (dim = 2) are not supported here; the device runs the matrix-free apply and diag / rhs on quads only", what);
+        return -1;
+    }
+    return 0;
+}
 struct l3k_bnd;
 struct l3k_mf
 {

@@ -375,12 +375,62 @@ struct Unit3D
         out[0] = 1.;
     }
 };
+// Steady diffusion in first-order form on quads, unknowns (T, qx, qy), four equations (the operator entries of the oracle's
+// Diffusion2D, oracle/oracle.cpp): -div q = 0, grad T - q = 0 (two rows), rot q = 0; no source
+struct Diffusion2D
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 4, .n_unknowns = 3};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In&, Out& out) const
+    {
+        auto& [operators, rhs] = out;
+        auto& [A0, Ax, Ay]     = operators;
+        Ax(0, 1) = -1.;
+        Ay(0, 2) = -1.;
+        A0(1, 1) = -1.;
+        Ax(1, 0) = 1.;
+        A0(2, 2) = -1.;
+        Ay(2, 0) = 1.;
+        Ax(3, 2) = 1.;
+        Ay(3, 1) = -1.;
+    }
+};
+
+// Diffusion2D with the diffusivity lambda an external field: -grad lambda . q - lambda div q = 0 on the first row
+struct Diffusion2DVar
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 4, .n_unknowns = 3, .n_fields = 1};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In& in, Out& out) const
+    {
+        const auto& [field_vals, field_ders, _] = in;
+        const double lambda                     = field_vals[0];
+        const double dl_dx = field_ders[0][0], dl_dy = field_ders[1][0];
+
+        auto& [operators, rhs] = out;
+        auto& [A0, Ax, Ay]     = operators;
+        A0(0, 1) = -dl_dx;
+        A0(0, 2) = -dl_dy;
+        Ax(0, 1) = -lambda;
+        Ay(0, 2) = -lambda;
+        A0(1, 1) = -1.;
+        Ax(1, 0) = 1.;
+        A0(2, 2) = -1.;
+        Ay(2, 0) = 1.;
+        Ax(3, 2) = 1.;
+        Ay(3, 1) = -1.;
+    }
+};
 } // namespace l3k::kernels
 
 // id, functor type, name
 #define L3K_FOR_EACH_KERNEL(X)                                                                                         \
     X(0, ::l3k::kernels::Diffusion3D, "diffusion3d")                                                                   \
     X(1, ::l3k::kernels::Diffusion3DVar, "diffusion3d_var")                                                            \
+    X(2, ::l3k::kernels::Diffusion2D, "diffusion2d")                                                                   \
+    X(3, ::l3k::kernels::Diffusion2DVar, "diffusion2d_var")                                                            \
     X(4, ::l3k::kernels::AdvDiff3D, "advdiff3d")                                                                       \
     X(8, ::l3k::kernels::Mass3D, "mass3d")                                                                             \
     X(10, ::l3k::kernels::Diffusion3DPoint, "diffusion3d_point")                                                       \
@@ -432,7 +482,26 @@ struct Unit3D
     X(::l3k::kernels::Advection3D, 6, 7, 1)                                                                            \
     X(::l3k::kernels::DivCurl3D, 2, 3, 1)                                                                              \
     X(::l3k::kernels::DivCurl3D, 4, 5, 1)                                                                              \
-    X(::l3k::kernels::DivCurl3D, 6, 7, 1)
+    X(::l3k::kernels::DivCurl3D, 6, 7, 1)                                                                              \
+    X(::l3k::kernels::Diffusion2D, 1, 2, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 1, 2, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 2, 3, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 2, 3, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 3, 4, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 3, 4, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 4, 5, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 4, 5, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 5, 6, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 5, 6, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 6, 7, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 6, 7, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 4, 9, 1)                                                                            \
+    X(::l3k::kernels::Diffusion2D, 4, 9, 2)                                                                            \
+    X(::l3k::kernels::Diffusion2DVar, 2, 3, 1)                                                                         \
+    X(::l3k::kernels::Diffusion2DVar, 2, 3, 2)                                                                         \
+    X(::l3k::kernels::Diffusion2DVar, 4, 5, 1)                                                                         \
+    X(::l3k::kernels::Diffusion2DVar, 4, 9, 1)                                                                         \
+    X(::l3k::kernels::Diffusion2DVar, 4, 9, 2)
 
 #define L3K_FOR_EACH_BOUNDARY_INSTANCE(X)                                                                              \
     X(::l3k::kernels::Adiabatic3D, 2, 3, 1)                                                                            \

@@ -18,11 +18,10 @@ from . import system
 
 
 class PartitionedMesh:
-    dim = 3
-
     def __init__(self, elem_nodes, elem_verts, n_noninternal, elem_part, rank, world, order, device=None):
-        """elem_nodes: [n_elems][(order+1)^3] global node ids numbered [non-internal | internal, contiguous per element]
-        (what system.elevate_order returns); elem_verts [n_elems][8][3]; elem_part [n_elems] in [0, world).  The index
+        """elem_nodes: [n_elems][(order+1)^dim] global node ids numbered [non-internal | internal, contiguous per element]
+        (what system.elevate_order or system.SquarePartition give); elem_verts [n_elems][2^dim][3] -- 8 vertices make a
+        hex mesh (dim 3), 4 a quad mesh (dim 2); elem_part [n_elems] in [0, world).  The index
         work (sorts, uniques, searches over the global node table) runs in torch on `device` (default: the GPU if there
         is one); the attributes are numpy arrays like CubePartition's."""
         dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
@@ -30,6 +29,7 @@ class PartitionedMesh:
         part = torch.as_tensor(np.ascontiguousarray(elem_part).astype(np.int64), device=dev)
         n_elems, N = en.shape
         n_nodes = int(en.max()) + 1 if n_elems else 0
+        self.dim = {4: 2, 8: 3}[np.asarray(elem_verts).shape[1]]
         self.order, self.rank, self.parts = order, rank, (world, 1, 1)
         # ownership: lowest part touching the node (SegmentedOwnership / the METIS-based distribution's rule)
         owner = torch.full((n_nodes,), world, dtype=torch.int64, device=dev)

@@ -3,6 +3,7 @@
 Mirrors (names, argument meaning, error behaviour) for this path only:
   * tables            -- math::getLobattoRuleAbsc, quad::getReferenceQuadrature, SumFactorization tables
   * CubePartition     -- generateAndDistributeMesh for structured cubes (comm/DistributeMesh.hpp:284-299)
+  * SquarePartition   -- makeSquareMesh + convertMeshToOrder on one part (quads, mesh/primitives/SquareMesh.hpp)
   * MatrixFreeSystem  -- algsys::MatrixFreeSystem: assembleProblem -> Operator.apply(X, Y, alpha, beta)
                          (algsys/MatrixFreeSystem.hpp:24-89,1020-1140)
 Vectors are torch tensors of shape (ncols, n_owned_dofs), i.e. column-major [row][col] multivectors with owned rows
@@ -19,6 +20,8 @@ from .capi import L3KError, check
 
 KERNEL_DIFFUSION3D = 0
 KERNEL_DIFFUSION3D_VAR = 1
+KERNEL_DIFFUSION2D = 2  # quads: E = 4, U = 3 (T, qx, qy)
+KERNEL_DIFFUSION2D_VAR = 3  # quads, diffusivity as an external field (F = 1)
 KERNEL_ADVDIFF3D = 4
 KERNEL_MASS3D = 8  # A0 = I: known answers for w * detJ
 KERNEL_DIFFUSION3D_POINT = 10  # operators and rhs read point.space.{x,y,z} and point.time
@@ -154,13 +157,15 @@ class CubePartition:
         return np.concatenate(fe), np.concatenate(fs)
 
     def node_coords(self):
-        """Physical location of every local node (mesh/NodePhysicalLocation.hpp: tri-linear map of the element vertices
-        at the GLL reference positions).  Returns float64 [n_local_nodes, 3]."""
+        """Physical location of every local node (mesh/NodePhysicalLocation.hpp: tri-linear map -- bilinear on quads -- of
+        the element vertices at the GLL reference positions).  Returns float64 [n_local_nodes, 3]."""
         g = gll_nodes(self.order + 1)
         l = np.stack([(1 - g) / 2, (1 + g) / 2], axis=1)  # [n][2] linear shape functions at the GLL points
         n = self.order + 1
-        # shape[(ix,iy,iz) lexicographic, v = i + 2j + 4k]
-        shape = np.einsum("xi,yj,zk->zyxkji", l, l, l).reshape(n ** 3, 8)
+        if self.elem_verts.shape[1] == 4:  # quads: shape[(ix,iy) lexicographic, v = i + 2j]
+            shape = np.einsum("xi,yj->yxji", l, l).reshape(n ** 2, 4)
+        else:  # shape[(ix,iy,iz) lexicographic, v = i + 2j + 4k]
+            shape = np.einsum("xi,yj,zk->zyxkji", l, l, l).reshape(n ** 3, 8)
         coords = np.zeros((self.n_local_nodes, 3))
         for e0 in range(0, self.n_elems, 65536):
             ev = self.elem_verts[e0:e0 + 65536]
@@ -181,6 +186,50 @@ class CubePartition:
                 z = z ^ (z >> np.uint64(31))
             out[c] = (z >> np.uint64(11)).astype(np.float64) * (2.0 / (1 << 53)) - 1.0
         return out
+
+
+class SquarePartition:
+    """A single-part structured order-p quad mesh of [0,1]^2 (host arrays; l3k_square_mesh_create): the attributes of
+    CubePartition with dim = 2, elem_verts [n_elems][4][3] (z = 0), node_grid_id = gx + NX*gy and the quad side order
+    0 y=0, 1 y=1, 2 x=0, 3 x=1 (mesh/ElementTraits.hpp:84-95).  Multi-part quad meshes: partition.rcb_partition +
+    partition.PartitionedMesh on its arrays."""
+
+    def __init__(self, ne, order, perturb=0.0):
+        lib = capi.load()
+        ne = (ne,) * 2 if np.isscalar(ne) else tuple(ne)
+        self.ne, self.order, self.parts, self.rank = ne, order, (1, 1), 0
+        h = C.c_void_p()
+        check(lib.l3k_square_mesh_create((C.c_int * 2)(*ne), order, perturb, C.byref(h)))
+        try:
+            v = capi.HostMeshView()
+            check(lib.l3k_hostmesh_view_get(h, C.byref(v)))
+            N = (order + 1) ** 2
+            as_np = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape).copy()
+            self.dim = v.dim
+            self.n_elems, self.n_interior_elems = v.n_elems, v.n_interior_elems
+            self.n_owned_nodes, self.n_ghost_nodes = v.n_owned_nodes, v.n_ghost_nodes
+            self.global_node_base, self.n_global_nodes = v.global_node_base, v.n_global_nodes
+            self.elem_nodes = as_np(v.elem_nodes, (v.n_elems, N))
+            self.elem_verts = as_np(v.elem_verts, (v.n_elems, 4, 3))
+            self.node_grid_id = as_np(v.node_grid_id, (v.n_owned_nodes,))
+            self.node_boundary = as_np(v.node_boundary, (v.n_owned_nodes,))
+            self.elem_boundary = as_np(v.elem_boundary, (v.n_elems,))
+            self.ghost_global_id = np.zeros(0, np.int64)
+            self.nbr_rank, self.send_nodes, self.ghost_ranges = [], [], []
+        finally:
+            lib.l3k_hostmesh_destroy(h)
+
+    n_local_nodes = CubePartition.n_local_nodes
+    node_coords = CubePartition.node_coords
+    synthetic_vector = CubePartition.synthetic_vector
+
+    def dirichlet_mask(self, dofs_per_node, unknowns=(0,), sides=range(4)):
+        """Byte mask over local dofs: the listed unknowns on the listed square sides."""
+        return CubePartition.dirichlet_mask(self, dofs_per_node, unknowns, sides)
+
+    def boundary_sides(self, sides=range(4)):
+        """(element index, side) of the element sides on the listed square sides.  Returns (int64[n], uint8[n])."""
+        return CubePartition.boundary_sides(self, sides)
 
 
 def synthetic_vector_torch(node_grid_id, dofs_per_node, device, seed=42, ncols=1):
