@@ -25,8 +25,9 @@ extern "C" {
 /* 101 (round 4): l3k_cg_update_xr / _update_p replaced by l3k_cg_update_z / _update_px (the iteration keeps z = M^-1 r; d_r holds z),
  * new: l3k_ctx_set_reference_z0, l3k_ctx_get/set_tuning, l3k_mf_route, l3k_update_solution, l3k_pcg_solve_cols */
 /* Quadrilateral meshes (dim = 2) on the device -- l3k_mesh_create, the matrix-free apply and l3k_mf_diag_rhs, kernels
- * L3K_KERNEL_DIFFUSION2D / _VAR, l3k_square_mesh_create -- are additions only: no existing entry point changed, so the
- * version stays (tests/test_cabi_cpu.py pins it). */
+ * L3K_KERNEL_DIFFUSION2D / _VAR, l3k_square_mesh_create; then l3k_bnd_create, l3k_integrate and l3k_values_at_nodes with
+ * dim = 2 and the 2-D boundary / residual kernels -- are additions only: no existing entry point changed its behaviour on
+ * hexes, so the version stays (tests/test_cabi_cpu.py pins it). */
 #define L3K_VERSION 101
 
 typedef struct l3k_ctx      l3k_ctx;
@@ -78,6 +79,7 @@ enum
     L3K_KERNEL_DIFFUSION2D_VAR = 3, /* tests/Kernels.hpp:27-52: quads, n_fields = 1 (diffusivity, value + derivatives) */
     L3K_KERNEL_ADVDIFF3D       = 4, /* config-5 synthetic; params {double k, sigma, s}, n_fields = 3 */
     /* boundary equation kernels (wrapBoundaryEquationKernel: the input carries the outward normal); l3k_bnd_create */
+    L3K_KERNEL_ADIABATIC2D     = 5, /* tests/Kernels.hpp:120-128: quads, U = 3 (T, qx, qy), E = 1, q.n = 0           */
     L3K_KERNEL_ADIABATIC3D     = 6, /* 3-D twin of tests/Kernels.hpp:120-128: q.n = 0                                 */
     L3K_KERNEL_ROBIN3D         = 7  /* synthetic: q.n + h T = h T_inf; params {double h, t_inf}                      */
 };
@@ -85,8 +87,11 @@ enum
 enum
 {
     L3K_RESIDUAL_DIFFUSION3D_ERROR = 0, /* benchmarks/Diffusion3D.hpp:81-103; fields (T,qx,qy,qz); params {double k, s} */
+    L3K_RESIDUAL_LINEAR2D_ERROR    = 1, /* tests/Diffusion2D.hpp:84-92 (quads): fields (T,qx,qy), error against T = x   */
     L3K_RESIDUAL_LINEAR3D_ERROR    = 2, /* 3-D twin of tests/Diffusion2D.hpp:84-92: error against T = x, q = (1,0,0)   */
+    L3K_RESIDUAL_UNIT2D            = 3, /* quads: integrand 1 (area, side length)                                     */
     L3K_RESIDUAL_UNIT3D            = 4, /* tests/MappingTests.cpp:567-569: integrand 1                                */
+    L3K_RESIDUAL_COORDX2D          = 5, /* tests/Diffusion2D.hpp:49-50 (quads): out[0] = x (Dirichlet value kernel)     */
     L3K_RESIDUAL_COORDX3D          = 6  /* 3-D twin of tests/Diffusion2D.hpp:49-50: out[0] = x (Dirichlet value kernel) */
 };
 int l3k_kernel_info(int kernel_id, l3k_kparams* params, const char** name, size_t* param_bytes);
@@ -155,8 +160,8 @@ int l3k_ctx_destroy(l3k_ctx* ctx);
  * (dofs/NodeToDofMap.hpp:84-109) and LocalDirichletBC (bcs/LocalDirichletBC.hpp:13-32), flattened.  Uploaded once. */
 typedef struct
 {
-    int             dim;            /* 3 (hex) or 2 (quad: apply and diag / rhs only; no LocalAssembly, boundary
-                                       kernels, integrals or values at nodes on quads)                                 */
+    int             dim;            /* 3 (hex) or 2 (quad: apply, diag / rhs, boundary kernels, integrals and values
+                                       at nodes; no LocalAssembly or assembled path on quads)                          */
     int             order;          /* p; nodes per element N = (p+1)^dim, lexicographic, xi fastest               */
     int64_t         n_elems;        /* elements [0, n_interior_elems) touch owned dofs only, the rest are "border" */
     int64_t         n_interior_elems; /* splitBorderAndInterior, algsys/MatrixFreeSystem.hpp:969-981              */
@@ -238,7 +243,9 @@ int l3k_mf_dirichlet_finalize(l3k_mf* mf, const double* d_dirichlet_vals, size_t
  * sum over the listed element sides of  int_side B^T B  with the side quadrature, surface jacobian and outward normal
  * of map::mapBoundary (algsys/EvaluateLocalOperator.hpp:238-274,303-330; mapping/BoundaryNormal.hpp:8-64;
  * mapping/BoundaryIntegralJacobian.hpp:9-29; basisfun/ReferenceElementBasisAtQuadrature.hpp:57-97).
- * A side is (element index in the mesh, side): hex sides 0..5 = z-, z+, y-, y+, x-, x+ (mesh/ElementTraits.hpp:84-95).
+ * A side is (element index in the mesh, side): hex sides 0..5 = z-, z+, y-, y+, x-, x+ (mesh/ElementTraits.hpp:84-95);
+ * quad sides 0..3 = y- (eta = -1), y+ (eta = +1), x- (xi = -1), x+ (xi = +1).  A side index >= 2 * dim is refused.
+ * l3k_bnd_create, l3k_integrate and l3k_values_at_nodes take hex and quad meshes, with kernels of the mesh's dimension.
  * l3k_mf_attach_boundary registers the term with a system: l3k_mf_apply / l3k_mf_apply_elems / l3k_mf_diag_rhs then
  * include it, like the reference evaluates every kernel passed to assembleProblem.  `which` as in l3k_mf_apply_elems:
  * sides of interior elements (0), of border elements (1), all (2).  The term does not own the system or the mesh and

@@ -479,13 +479,10 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
         for (int v = 0; v < nv; ++v)
             used[d->elem_nodes[e * N + corner[v]]] |= uint64_t(1) << c;
     }
-    if (d->dim == 3) // (the colouring of boundary sides; quads have no boundary terms on the device)
-    {
-        m.det_corner_nodes.resize(static_cast< size_t >(d->n_elems) * 8);
-        for (int64_t e = 0; e < d->n_elems; ++e)
-            for (int v = 0; v < 8; ++v)
-                m.det_corner_nodes[size_t(e) * 8 + v] = d->elem_nodes[e * N + corner[v]];
-    }
+    m.det_corner_nodes.resize(static_cast< size_t >(d->n_elems) * nv); // (the colouring of boundary sides)
+    for (int64_t e = 0; e < d->n_elems; ++e)
+        for (int v = 0; v < nv; ++v)
+            m.det_corner_nodes[size_t(e) * nv + v] = d->elem_nodes[e * N + corner[v]];
     std::vector< int64_t > order(static_cast< size_t >(d->n_elems));
     for (int64_t e = 0; e < d->n_elems; ++e)
         order[e] = e;
@@ -1833,8 +1830,6 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
         setError("l3k_bnd_create: bad argument");
         return -1;
     }
-    if (int rc = refuseQuads(mesh, "l3k_bnd_create"))
-        return rc;
     const auto* k = findKernel(kernel_id);
     if (!k || !k->boundary)
     {
@@ -1843,7 +1838,7 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
     }
     if (k->kp.dimension != mesh->dim)
     {
-        setError("kernel dimension %d != mesh dimension %d", k->kp.dimension, mesh->dim);
+        setError("kernel dimension %d != mesh dimension %d%s", k->kp.dimension, mesh->dim, quadsNote(mesh));
         return -1;
     }
     if (kparam_blob && kparam_bytes != k->bytes)
@@ -1857,7 +1852,7 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
         return -1;
     }
     for (int64_t i = 0; i < n_faces; ++i) // operand shapes must match what the kernel assumes
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 6)
+        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
         {
             setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
                      int(face_side[i]));
@@ -1898,25 +1893,26 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
     b->n_faces = n_faces;
     if (ctx->deterministic)
     {
-        // greedy colouring of the sides by ALL EIGHT corner nodes of their elements: the side kernel scatter-adds over every
-        // node of the element (the normal derivative couples all of them, device/boundary.hpp), so two sides may share a
-        // colour only if their elements share no node -- for conforming hexes: no corner.  (Colouring by the side's own four
-        // corners let the z- side of a corner element and the x- side of the element stacked on it into one launch.)
-        // Class by class; the lists are stored in (class, colour) order
+        // greedy colouring of the sides by ALL 2^dim corner nodes of their elements: the side kernel scatter-adds over every
+        // node of the element (the normal derivative couples all of them, device/boundary.hpp, device/quad_boundary.hpp), so
+        // two sides may share a colour only if their elements share no node -- for conforming hexes / quads: no corner.
+        // (Colouring by the side's own four corners let the z- side of a corner element and the x- side of the element stacked
+        // on it into one launch.)  Class by class; the lists are stored in (class, colour) order
         if (!mesh->det_built)
         {
             setError("deterministic mode was enabled after this mesh was created: create the mesh with the mode on");
             return -1;
         }
+        const int                                nv = 1 << mesh->dim;
         std::unordered_map< uint32_t, uint64_t > used;
         std::vector< uint8_t >                   colour(fe.size());
         int                                      n_colours = 0;
         for (size_t i = 0; i < fe.size(); ++i)
         {
             uint64_t taken = 0;
-            for (int v = 0; v < 8; ++v)
+            for (int v = 0; v < nv; ++v)
             {
-                const auto it = used.find(mesh->det_corner_nodes[size_t(fe[i]) * 8 + v]);
+                const auto it = used.find(mesh->det_corner_nodes[size_t(fe[i]) * nv + v]);
                 if (it != used.end())
                     taken |= it->second;
             }
@@ -1930,8 +1926,8 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
             }
             colour[i] = uint8_t(c);
             n_colours = std::max(n_colours, c + 1);
-            for (int v = 0; v < 8; ++v)
-                used[mesh->det_corner_nodes[size_t(fe[i]) * 8 + v]] |= uint64_t(1) << c;
+            for (int v = 0; v < nv; ++v)
+                used[mesh->det_corner_nodes[size_t(fe[i]) * nv + v]] |= uint64_t(1) << c;
         }
         std::vector< size_t > order(fe.size());
         for (size_t i = 0; i < order.size(); ++i)

@@ -65,8 +65,6 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
         setError("l3k_integrate: bad argument");
         return -1;
     }
-    if (int rc = refuseQuads(mesh, "l3k_integrate"))
-        return rc;
     const auto* k = findResidual(residual_id);
     if (!k)
     {
@@ -75,7 +73,7 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
     }
     if (k->kp.dimension != mesh->dim)
     {
-        setError("kernel dimension %d != mesh dimension %d", k->kp.dimension, mesh->dim);
+        setError("kernel dimension %d != mesh dimension %d%s", k->kp.dimension, mesh->dim, quadsNote(mesh));
         return -1;
     }
     if (kparam_blob && kparam_bytes != k->bytes)
@@ -90,7 +88,7 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
     }
     const bool side = n_faces >= 0;
     for (int64_t i = 0; i < n_faces; ++i)
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 6)
+        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
         {
             setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
                      int(face_side[i]));
@@ -165,8 +163,6 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
         setError("l3k_values_at_nodes: bad argument");
         return -1;
     }
-    if (int rc = refuseQuads(mesh, "l3k_values_at_nodes"))
-        return rc;
     const auto* k = findResidual(residual_id);
     if (!k)
     {
@@ -175,7 +171,8 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
     }
     if (k->kp.dimension != mesh->dim || k->kp.n_equations > l3k::dev::max_unknowns)
     {
-        setError("kernel %s does not fit this mesh (dimension %d, %d equations)", k->name, k->kp.dimension, k->kp.n_equations);
+        setError("kernel %s does not fit this mesh (dimension %d, %d equations)%s", k->name, k->kp.dimension, k->kp.n_equations,
+                 k->kp.dimension != mesh->dim ? quadsNote(mesh) : "");
         return -1;
     }
     if (kparam_blob && kparam_bytes != k->bytes)
@@ -195,7 +192,7 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
             return -1;
         }
     for (int64_t i = 0; i < n_faces; ++i)
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 6)
+        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
         {
             setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
                      int(face_side[i]));

@@ -14,6 +14,7 @@
 #include "boundary.hpp"
 #include "integral.hpp"
 #include "quad.hpp"
+#include "quad_boundary.hpp"
 
 namespace l3k::dev
 {
@@ -103,7 +104,7 @@ namespace l3k::dev
 {
 // The registry entry of one (functor, order, nq, columns) shape: quads (dimension 2) take the kernels of quad.hpp and have no
 // LocalAssembly (assemble = nullptr); hexes the sum-factorised hex kernels.  `if constexpr` keeps the templates of the other
-// dimension uninstantiated.
+// dimension uninstantiated (here and in the boundary / residual entries below).
 template < typename T, int P, int NQ, int R >
 Instance makeInstance()
 {
@@ -114,6 +115,26 @@ Instance makeInstance()
         return {KernelId< T >::value, P, NQ, R, selectApply< T, P, NQ, R >(), &launchDiagRhs< T, P, NQ, R >, &launchAssemble< T, P, NQ >,
                 assembleWorkspaceDoublesPerElem< T, P, NQ >(), selectApplyCols< T, P, NQ, R >(), SfAsmCfg< P, NQ >::feasible,
                 selectRoute< T, P, NQ, R >()};
+}
+// ... of a boundary equation kernel: the side kernel of quad_boundary.hpp on quads, of boundary.hpp on hexes
+template < typename T, int P, int NQ, int R >
+BoundaryInstance makeBoundaryInstance()
+{
+    if constexpr (T::params.dimension == 2)
+        return {KernelId< T >::value, P, NQ, R, &launchQuadSide< T, P, NQ, R, false >, &launchQuadSide< T, P, NQ, R, true >};
+    else
+        return {KernelId< T >::value, P, NQ, R, &launchFace< T, P, NQ, R, false >, &launchFace< T, P, NQ, R, true >};
+}
+// ... of a residual kernel (integrals over elements and sides, values at nodes), chosen the same way
+template < typename T, int P, int NQ >
+IntegralInstance makeIntegralInstance()
+{
+    if constexpr (T::params.dimension == 2)
+        return {ResidualId< T >::value, P, NQ, &launchQuadIntegral< T, P, NQ, false >, &launchQuadIntegral< T, P, NQ, true >,
+                &launchQuadValuesAtNodesAny< T, P, NQ >};
+    else
+        return {ResidualId< T >::value, P, NQ, &launchIntegral< T, P, NQ, false >, &launchIntegral< T, P, NQ, true >,
+                &launchValuesAtNodesAny< T, P, NQ >};
 }
 } // namespace l3k::dev
 
@@ -151,9 +172,7 @@ Instance makeInstance()
     {                                                                                                                  \
         L3K_CAT(BRegistrar_, __LINE__)()                                                                               \
         {                                                                                                              \
-            ::l3k::dev::registerBoundaryInstance({::l3k::dev::KernelId< T >::value, P, NQ, R,                          \
-                                                  &::l3k::dev::launchFace< T, P, NQ, R, false >,                       \
-                                                  &::l3k::dev::launchFace< T, P, NQ, R, true >});                      \
+            ::l3k::dev::registerBoundaryInstance(::l3k::dev::makeBoundaryInstance< T, P, NQ, R >());                   \
         }                                                                                                              \
     } L3K_CAT(bregistrar_, __LINE__);                                                                                  \
     }
@@ -164,10 +183,7 @@ Instance makeInstance()
     {                                                                                                                  \
         L3K_CAT(RRegistrar_, __LINE__)()                                                                               \
         {                                                                                                              \
-            ::l3k::dev::registerIntegralInstance({::l3k::dev::ResidualId< T >::value, P, NQ,                           \
-                                                  &::l3k::dev::launchIntegral< T, P, NQ, false >,                      \
-                                                  &::l3k::dev::launchIntegral< T, P, NQ, true >,                       \
-                                                  &::l3k::dev::launchValuesAtNodesAny< T, P, NQ >});                   \
+            ::l3k::dev::registerIntegralInstance(::l3k::dev::makeIntegralInstance< T, P, NQ >());                      \
         }                                                                                                              \
     } L3K_CAT(rregistrar_, __LINE__);                                                                                  \
     }

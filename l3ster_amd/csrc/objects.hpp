@@ -155,20 +155,26 @@ struct l3k_mesh
     DevBuf< double >       det_elem_verts;
     DevBuf< uint8_t >      det_elem_flags;
     std::vector< int64_t > det_ptr[2];
-    std::vector< uint32_t > det_corner_nodes; // host, [n_elems][8] in the ORIGINAL element order: colouring of boundary sides
+    std::vector< uint32_t > det_corner_nodes; // host, [n_elems][2^dim] in the ORIGINAL element order: colouring of boundary sides
     int64_t nOwnedDofs() const { return n_owned_nodes * dofs_per_node; }
     int64_t nLocalDofs() const { return (n_owned_nodes + n_ghost_nodes) * dofs_per_node; }
 };
-// Entry points without quad kernels (LocalAssembly, the assembled path, boundary terms, integrals, values at nodes) refuse quad
-// meshes up front: -1 and the reason, and no hex kernel ever sees quad data
+// Entry points without quad kernels (LocalAssembly and the assembled path) refuse quad meshes up front: -1 and the reason, and
+// no hex kernel ever sees quad data
 inline int refuseQuads(const l3k_mesh* m, const char* what)
 {
     if (m && m->dim == 2)
     {
-        setError("%s: quads (dim = 2) are not supported here; the device runs the matrix-free apply and diag / rhs on quads only", what);
+        setError("%s: quads (dim = 2) are not supported here; the device runs the matrix-free apply, diag / rhs, boundary terms, "
+                 "integrals and values at nodes on quads", what);
         return -1;
     }
     return 0;
+}
+// appended to a dimension mismatch on a quad mesh: " (quads)"
+inline const char* quadsNote(const l3k_mesh* m)
+{
+    return m->dim == 2 ? " (quads)" : "";
 }
 struct l3k_bnd;
 struct l3k_mf

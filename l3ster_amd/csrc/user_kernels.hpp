@@ -319,6 +319,22 @@ struct NormalFlux3D
     }
 };
 
+// Adiabatic wall of the first-order 2-D diffusion system (unknowns T, qx, qy; tests/Kernels.hpp:120-128): q . n = 0
+struct Adiabatic2D
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 1, .n_unknowns = 3};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In& in, Out& out) const
+    {
+        const auto& normal     = in.normal;
+        auto& [operators, rhs] = out;
+        auto& [A0, A1, A2]     = operators;
+        A0(0, 1) = normal[0];
+        A0(0, 2) = normal[1];
+    }
+};
+
 // ---- residual kernels (integrals, L2 norms): out[n_equations] from the interpolated fields ------------------------
 // benchmarks/Diffusion3D.hpp:81-103: residuals of the first-order diffusion system for the fields (T, qx, qy, qz)
 struct Diffusion3DError
@@ -373,6 +389,42 @@ struct Unit3D
     L3K_HD void operator()(const In&, Out& out) const
     {
         out[0] = 1.;
+    }
+};
+// tests/Diffusion2D.hpp:84-92: error of the fields (T, qx, qy) against the exact solution T = x, q = (1, 0)
+struct Linear2DError
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 3, .n_fields = 3};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In& in, Out& error) const
+    {
+        const auto& vals = in.field_vals;
+        error[0]         = vals[0] - in.point.space.x();
+        error[1]         = vals[1] - 1.;
+        error[2]         = vals[2];
+    }
+};
+// integrand 1 on quads (area / side length)
+struct Unit2D
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 1};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In&, Out& out) const
+    {
+        out[0] = 1.;
+    }
+};
+// the Dirichlet value kernel of tests/Diffusion2D.hpp:49-50: out[0] = x
+struct CoordX2D
+{
+    static constexpr KernelParams params{.dimension = 2, .n_equations = 1};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In& in, Out& out) const
+    {
+        out[0] = in.point.space.x();
     }
 };
 // Steady diffusion in first-order form on quads, unknowns (T, qx, qy), four equations (the operator entries of the oracle's
@@ -437,18 +489,22 @@ struct Diffusion2DVar
     X(11, ::l3k::kernels::Advection3D, "advection3d")                                                                  \
     X(12, ::l3k::kernels::DivCurl3D, "divcurl3d")
 
-// boundary equation kernels (ids continue the numbering above; 5 is the 2-D adiabatic kernel of the CPU oracle)
+// boundary equation kernels (ids continue the numbering above; 5 is the oracle's 2-D adiabatic kernel)
 #define L3K_FOR_EACH_BOUNDARY_KERNEL(X)                                                                                \
+    X(5, ::l3k::kernels::Adiabatic2D, "adiabatic2d")                                                                   \
     X(6, ::l3k::kernels::Adiabatic3D, "adiabatic3d")                                                                   \
     X(7, ::l3k::kernels::Robin3D, "robin3d")                                                                           \
     X(9, ::l3k::kernels::NormalFlux3D, "normalflux3d")                                                                 \
     X(14, ::l3k::kernels::RobinPoint3D, "robinpoint3d")
 
-// residual kernels (own id space; 1 and 3 are the 2-D kernels of the CPU oracle)
+// residual kernels (own id space; the odd ids are the 2-D kernels, with the oracle's numbers)
 #define L3K_FOR_EACH_RESIDUAL_KERNEL(X)                                                                                \
     X(0, ::l3k::kernels::Diffusion3DError, "diffusion3d_error")                                                        \
+    X(1, ::l3k::kernels::Linear2DError, "linear2d_error")                                                              \
     X(2, ::l3k::kernels::Linear3DError, "linear3d_error")                                                              \
+    X(3, ::l3k::kernels::Unit2D, "unit2d")                                                                             \
     X(4, ::l3k::kernels::Unit3D, "unit3d")                                                                             \
+    X(5, ::l3k::kernels::CoordX2D, "coordx2d")                                                                         \
     X(6, ::l3k::kernels::CoordX3D, "coordx3d")
 
 // Shapes instantiated on the device: (functor, order p, quadrature points per direction nq, columns R).
@@ -518,7 +574,17 @@ struct Diffusion2DVar
     X(::l3k::kernels::RobinPoint3D, 2, 3, 1)                                                                           \
     X(::l3k::kernels::RobinPoint3D, 2, 3, 2)                                                                           \
     X(::l3k::kernels::RobinPoint3D, 3, 7, 1)                                                                           \
-    X(::l3k::kernels::RobinPoint3D, 4, 5, 1)
+    X(::l3k::kernels::RobinPoint3D, 4, 5, 1)                                                                           \
+    X(::l3k::kernels::Adiabatic2D, 1, 2, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 2, 3, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 3, 4, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 4, 5, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 5, 6, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 6, 7, 1)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 1, 2, 2)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 2, 3, 2)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 4, 5, 2)                                                                            \
+    X(::l3k::kernels::Adiabatic2D, 6, 7, 2)
 
 // (functor, order p, nq); computeNormL2 doubles the quadrature orders: nq = 2p+1 for the default options
 #define L3K_FOR_EACH_RESIDUAL_INSTANCE(X)                                                                              \
@@ -533,6 +599,19 @@ struct Diffusion2DVar
     X(::l3k::kernels::Unit3D, 2, 5)                                                                                    \
     X(::l3k::kernels::CoordX3D, 2, 3)                                                                                  \
     X(::l3k::kernels::CoordX3D, 4, 5)                                                                                  \
-    X(::l3k::kernels::CoordX3D, 6, 7)
+    X(::l3k::kernels::CoordX3D, 6, 7)                                                                                  \
+    X(::l3k::kernels::Linear2DError, 2, 5)                                                                             \
+    X(::l3k::kernels::Linear2DError, 4, 9)                                                                             \
+    X(::l3k::kernels::Linear2DError, 6, 13)                                                                            \
+    X(::l3k::kernels::Unit2D, 1, 6)                                                                                    \
+    X(::l3k::kernels::Unit2D, 2, 3)                                                                                    \
+    X(::l3k::kernels::Unit2D, 2, 5)                                                                                    \
+    X(::l3k::kernels::Unit2D, 4, 9)                                                                                    \
+    X(::l3k::kernels::CoordX2D, 1, 2)                                                                                  \
+    X(::l3k::kernels::CoordX2D, 2, 3)                                                                                  \
+    X(::l3k::kernels::CoordX2D, 3, 4)                                                                                  \
+    X(::l3k::kernels::CoordX2D, 4, 5)                                                                                  \
+    X(::l3k::kernels::CoordX2D, 5, 6)                                                                                  \
+    X(::l3k::kernels::CoordX2D, 6, 7)
 
 #endif

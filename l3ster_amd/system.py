@@ -27,6 +27,7 @@ KERNEL_MASS3D = 8  # A0 = I: known answers for w * detJ
 KERNEL_DIFFUSION3D_POINT = 10  # operators and rhs read point.space.{x,y,z} and point.time
 KERNEL_ADVECTION3D = 11  # scalar BDF3 advection, U = E = 1, F = 3, velocity from the point
 KERNEL_DIVCURL3D = 12  # div-curl system, U = 3, E = 4
+KERNEL_ADIABATIC2D = 5  # boundary equation kernel on quads: U = 3 (T, qx, qy), q . n = 0
 KERNEL_ADIABATIC3D = 6  # boundary equation kernels
 KERNEL_ROBIN3D = 7
 KERNEL_NORMALFLUX3D = 9  # boundary kernel with derivative operators (A1..A3)
@@ -35,6 +36,9 @@ RESIDUAL_DIFFUSION3D_ERROR = 0
 RESIDUAL_LINEAR3D_ERROR = 2
 RESIDUAL_UNIT3D = 4
 RESIDUAL_COORDX3D = 6
+RESIDUAL_LINEAR2D_ERROR = 1  # quads: fields (T, qx, qy), error against T = x, q = (1, 0)
+RESIDUAL_UNIT2D = 3  # quads: integrand 1
+RESIDUAL_COORDX2D = 5  # quads: out[0] = x (Dirichlet values)
 
 
 # ------------------------------------------------------------------------------------------------------- tables
