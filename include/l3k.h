@@ -401,6 +401,37 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
                         double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes,
                         int64_t* n_missing);
 
+/* ---- static condensation of the element-internal dofs (hexes) -----------------------------------------------------------
+ * The reference's CondensationPolicy::ElementBoundary (algsys/StaticCondensationManager.hpp).  Per element, with the primary
+ * dofs b (nodes on the element boundary) and the internal dofs i (nodes with 1 <= ix, iy, iz <= p-1), both in ascending
+ * element-local node index (mesh/ElementTraits.hpp:37-59 boundary_node_inds / internal_node_inds), node-major b U + u:
+ *   S_e = K_bb - K_bi K_ii^-1 K_ib,  g_e = F_b - K_bi K_ii^-1 F_i        (condenseSystem, StaticCondensationManager.hpp:322-350)
+ *   x_i = K_ii^-1 (F_i - K_ib x_b)                                        (recoverSolution, :410-470)
+ * through a Cholesky factorisation K_ii = L L^T on the device (the reference inverts K_ii with Eigen on the host; equal to
+ * rounding).  Np = (p+1)^3 - (p-1)^3 primary nodes, Nbd = Np U.  At order 1 there are no internal nodes: S_e = K_e bit for bit,
+ * g_e = F_e, recovery does nothing.  A pivot of K_ii that is not positive returns -2, "non-positive pivot in the
+ * element-internal block": nothing of that element reaches S_e / G_e (zeros) or the global system.  A degenerate element
+ * returns -2 as l3k_local_assemble does.  Quads are refused ("quads").
+ *
+ * l3k_condense_local: S_e [count][Nbd][Nbd] row-major, bitwise symmetric, G_e [count][Nbd][n_rhs] column-major (i.e.
+ *   [count][n_rhs][Nbd]); either may be NULL.
+ * l3k_condense_global: assemble + condense + scatter of S_e / g_e into the caller's CSR graph and rhs (condenseSystem for every
+ *   element, then endAssembly's sum into the condensed matrix, :352-408): same graph, ldr, skip_dirichlet, workspace_bytes
+ *   (0 = 2 GiB) and n_missing semantics as l3k_assemble_global; S_e never leaves the device.  Rows and columns use the local
+ *   dof numbering of l3k_assembled_scatter; the rows of internal dofs get nothing, so a graph that couples the primary nodes of
+ *   each element is enough.  skip_dirichlet leaves out the rows and columns of flagged dofs; a flag on an internal dof is
+ *   ignored (a domain-boundary node is never element-internal).
+ * l3k_condensed_recover: x [n_rhs][ldx] over the local dofs (owned + ghost, ghosts imported): reads the primary dofs of the
+ *   elements [first, first+count), writes their internal dofs (plain stores: each internal dof belongs to one element, the
+ *   result is bitwise reproducible).  Stateless: the element systems are formed and eliminated again from the system's
+ *   current fields and time, which must therefore not change between condensing and recovering. */
+/* S_e [count][Nbd][Nbd] row-major, G_e [count][Nbd][n_rhs] column-major (Nbd = Np*U); either may be NULL */
+int l3k_condense_local(l3k_mf* mf, int64_t first, int64_t count, double* d_S, double* d_G);
+int l3k_condense_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind,
+                        double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes,
+                        int64_t* n_missing);
+int l3k_condensed_recover(l3k_mf* mf, int64_t first, int64_t count, double* d_x, size_t ldx);
+
 /* ---- ghost exchange of a partitioned system: RCCL neighbour send / receive behind the C ABI -----------------------------
  * Stands in for comm::Import / comm::Export and their ImportExportContext (comm/ImportExport.hpp:29-72,130-215,295-372,
  * 402-470) and for the communication part of MatrixFreeSystem::applyImpl (algsys/MatrixFreeSystem.hpp:1046-1111).  The

@@ -118,6 +118,8 @@ struct ElemArgs
 
 using LaunchFn = int (*)(const ElemArgs&, const void* kparam_blob, hipStream_t stream);
 using RouteFn  = int (*)(const ElemArgs&, char* buf, size_t n); // describes the kernel a launch with these arguments takes
+struct CondenseArgs; // device/condense.hpp
+using CondenseFn = int (*)(const CondenseArgs&, hipStream_t stream);
 
 // the launch-route settings of a launch: the context's, or the defaults (host/registry.cpp)
 const l3k_tuning& defaultTuning();
@@ -136,6 +138,7 @@ struct Instance
     LaunchFn apply_cols = nullptr; // ncols == 1 instances: applies a.n_cols columns in one pass over the elements, or nullptr
     bool     assemble_tiled = false; // `assemble` can write the tiled layout (ElemArgs::K_tiled): the sum-factorised kernel fits
     RouteFn  route = nullptr; // text description of the kernel `apply` (or `apply_cols`, with a.n_cols > 1) launches
+    CondenseFn condense = nullptr; // static condensation of element systems of this (order, unknowns) shape; nullptr on quads
 };
 
 // boundary equation kernel on element sides (device/boundary.hpp)

@@ -11,6 +11,7 @@
 #include "sumfact_fast.hpp"
 #include "diag.hpp"
 #include "assemble.hpp"
+#include "condense.hpp"
 #include "boundary.hpp"
 #include "integral.hpp"
 #include "quad.hpp"
@@ -103,7 +104,8 @@ constexpr RouteFn selectRoute()
 namespace l3k::dev
 {
 // The registry entry of one (functor, order, nq, columns) shape: quads (dimension 2) take the kernels of quad.hpp and have no
-// LocalAssembly (assemble = nullptr); hexes the sum-factorised hex kernels.  `if constexpr` keeps the templates of the other
+// LocalAssembly (assemble = nullptr) nor condensation; hexes the sum-factorised hex kernels and the condensation kernels of
+// their (order, unknowns) shape.  `if constexpr` keeps the templates of the other
 // dimension uninstantiated (here and in the boundary / residual entries below).
 template < typename T, int P, int NQ, int R >
 Instance makeInstance()
@@ -114,7 +116,7 @@ Instance makeInstance()
     else
         return {KernelId< T >::value, P, NQ, R, selectApply< T, P, NQ, R >(), &launchDiagRhs< T, P, NQ, R >, &launchAssemble< T, P, NQ >,
                 assembleWorkspaceDoublesPerElem< T, P, NQ >(), selectApplyCols< T, P, NQ, R >(), SfAsmCfg< P, NQ >::feasible,
-                selectRoute< T, P, NQ, R >()};
+                selectRoute< T, P, NQ, R >(), selectCondense< P, T::params.n_unknowns >()};
 }
 // ... of a boundary equation kernel: the side kernel of quad_boundary.hpp on quads, of boundary.hpp on hexes
 template < typename T, int P, int NQ, int R >

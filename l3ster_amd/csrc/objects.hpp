@@ -177,6 +177,33 @@ inline const char* quadsNote(const l3k_mesh* m)
     return m->dim == 2 ? " (quads)" : "";
 }
 struct l3k_bnd;
+// l3k_condense_local / l3k_condense_global / l3k_condensed_recover: two halves of element-system buffers (K_e, F_e, the factored
+// diagonal blocks and the pivot flags of a sub-batch), a second stream for the scatter and the events that order the reuse of the
+// halves; kept across calls, as l3k_mf::gasm
+struct CondenseBufs
+{
+    double*     buf[2]  = {nullptr, nullptr};
+    size_t      doubles = 0; // per half
+    unsigned*   nfail   = nullptr; // device counter of elements with a non-positive pivot
+    hipStream_t second  = nullptr;
+    hipEvent_t  formed[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
+    ~CondenseBufs()
+    {
+        for (int k = 0; k < 2; ++k)
+        {
+            if (buf[k])
+                (void)hipFree(buf[k]);
+            if (formed[k])
+                (void)hipEventDestroy(formed[k]);
+            if (consumed[k])
+                (void)hipEventDestroy(consumed[k]);
+        }
+        if (nfail)
+            (void)hipFree(nfail);
+        if (second)
+            (void)hipStreamDestroy(second);
+    }
+};
 struct l3k_mf
 {
     std::vector< l3k_bnd* > boundary_terms; // attached boundary equation kernels (not owned)
@@ -206,6 +233,7 @@ struct l3k_mf
         hipStream_t second      = nullptr;
         hipEvent_t  formed[2]   = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     } gasm;
+    CondenseBufs gcond;
     ~l3k_mf()
     {
         if (ws)

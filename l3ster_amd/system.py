@@ -527,6 +527,43 @@ def norm_l2(mesh, residual_id, fields=None, kernel_params=None, asm_opts=(1, 0, 
     return np.sqrt(sq)
 
 
+def element_node_split(order):
+    """(primary, internal) element-local node indices of a hex of `order` (ix + n iy + n^2 iz, n = order + 1), each ascending:
+    the internal nodes have all of ix, iy, iz in 1 .. order-1 (mesh/ElementTraits.hpp:37-59)."""
+    n = order + 1
+    idx = np.arange(n ** 3)
+    ix, iy, iz = idx % n, (idx // n) % n, idx // (n * n)
+    inner = (ix >= 1) & (ix <= order - 1) & (iy >= 1) & (iy <= order - 1) & (iz >= 1) & (iz <= order - 1)
+    return idx[~inner], idx[inner]
+
+
+def condensed_graph(elem_nodes, order, dofs_per_node, field_inds):
+    """CSR sparsity (row_ptr int64, col_ind int32, columns ascending) over the local dofs that couples the primary dofs of every
+    element with each other: the graph of the condensed system (the rows of internal dofs are empty).  Built at node level
+    (one entry per coupled node pair), then expanded to the dofs of the fields."""
+    elem_nodes = np.asarray(elem_nodes).astype(np.int64)
+    fi = np.sort(np.asarray(field_inds, dtype=np.int64))
+    U, dpn = len(fi), int(dofs_per_node)
+    primary, _ = element_node_split(order)
+    n_nodes = int(elem_nodes.max()) + 1 if elem_nodes.size else 0
+    en = elem_nodes[:, primary]
+    key = np.unique((en[:, :, None] * n_nodes + en[:, None, :]).ravel())
+    ra, cb = key // max(n_nodes, 1), key % max(n_nodes, 1)
+    deg = np.bincount(ra, minlength=n_nodes).astype(np.int64)
+    node_cols = (cb[:, None] * dpn + fi[None, :]).ravel()  # per node: its neighbour dofs, ascending
+    seg_start = U * (np.cumsum(deg) - deg)
+    seg_len = U * deg
+    # rows (a, f) for f in fi, ascending in the dof a dpn + f; each holds node a's segment
+    row_len = np.zeros((n_nodes, dpn), dtype=np.int64)
+    row_len[:, fi] = seg_len[:, None]
+    row_ptr = np.concatenate([[0], np.cumsum(row_len.ravel())]).astype(np.int64)
+    starts, lens = np.repeat(seg_start, U), np.repeat(seg_len, U)
+    total = int(lens.sum())
+    base = np.repeat(starts - (np.cumsum(lens) - lens), lens)
+    col_ind = node_cols[base + np.arange(total)] if total else np.zeros(0, np.int64)
+    return row_ptr, col_ind.astype(np.int32)
+
+
 class MatrixFreeSystem:
     """algsys::MatrixFreeSystem for one rank: kernel + mesh -> operator.  apply() is Operator::apply
     (Y <- alpha*A*X + beta*Y, algsys/MatrixFreeSystem.hpp:34-41,1038)."""
@@ -715,6 +752,41 @@ class MatrixFreeSystem:
                                               0 if rhs is None else rhs.stride(0) if rhs.dim() == 2 else rhs.numel(),
                                               int(skip_dirichlet), workspace_bytes, C.byref(missing)))
         return missing.value
+
+    def condense_local(self, first=0, count=None, want_S=True, want_G=True):
+        """Static condensation of the element-internal dofs (StaticCondensationManager::condenseSystem,
+        algsys/StaticCondensationManager.hpp:322-350) for elements [first, first+count): S [count, Nbd, Nbd] = K_bb - K_bi K_ii^-1 K_ib
+        (row-major, bitwise symmetric) and G [count, n_rhs, Nbd] = F_b - K_bi K_ii^-1 F_i over the primary dofs of each element
+        (element_node_split(order)[0], node-major)."""
+        import torch
+        count = self.mesh.part.n_elems - first if count is None else count
+        primary, _ = element_node_split(self.mesh.part.order)
+        Nbd = len(primary) * self.info["n_unknowns"]
+        S = torch.empty((count, Nbd, Nbd), dtype=torch.float64, device="cuda") if want_S else None
+        G = torch.empty((count, self.n_rhs, Nbd), dtype=torch.float64, device="cuda") if want_G else None
+        check(capi.load().l3k_condense_local(self._h, first, count, _ptr(S), _ptr(G)))
+        return S, G
+
+    def condense_global(self, row_ptr, col_ind, values, rhs=None, first=0, count=None, skip_dirichlet=False, workspace_bytes=0):
+        """Condensed assembleGlobalSystem for the elements [first, first + count): element systems formed, condensed and their
+        S_e / g_e summed into `values` (over the CSR graph row_ptr int64 / col_ind int32, e.g. condensed_graph) and `rhs`
+        [n_rhs, n_local_dofs] inside the library.  Returns the number of entries outside the graph."""
+        import ctypes as C
+        count = self.mesh.part.n_elems - first if count is None else count
+        missing = C.c_int64(0)
+        check(capi.load().l3k_condense_global(self._h, first, count, _ptr(row_ptr), _ptr(col_ind), _ptr(values), _ptr(rhs),
+                                              0 if rhs is None else rhs.stride(0) if rhs.dim() == 2 else rhs.numel(),
+                                              int(skip_dirichlet), workspace_bytes, C.byref(missing)))
+        return missing.value
+
+    def recover_internal(self, X, first=0, count=None):
+        """StaticCondensationManager::recoverSolution for the elements [first, first + count): X [n_rhs, n_local_dofs] holds the
+        solution on the primary dofs; its element-internal dofs are overwritten with K_ii^-1 (F_i - K_ib x_b).  The element systems
+        are formed again: the system's fields and time must be those it was condensed with."""
+        count = self.mesh.part.n_elems - first if count is None else count
+        ldx = (X.stride(0) if X.shape[0] > 1 else X.shape[1]) if X.dim() == 2 else X.numel()  # (a single row may carry stride 0)
+        check(capi.load().l3k_condensed_recover(self._h, first, count, _ptr(X), ldx))
+        return X
 
     def new_ghost_buffer(self, ncols, like):
         import torch

@@ -1,0 +1,305 @@
+"""GPU tests of static condensation (the reference's CondensationPolicy::ElementBoundary, StaticCondensationManager.hpp):
+l3k_condense_local against a numpy Schur complement of the oracle's element systems, l3k_condense_global against a dense
+Schur complement of the oracle-assembled global matrix, a condensed solve + l3k_condensed_recover against the full assembled
+solve, other shapes (a U = 7 plugin, order 8) and the error paths."""
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from helpers import HEX, SingleElementMesh
+from l3ster_amd import system
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    assert torch.cuda.is_available()
+    torch.cuda.set_device(0)
+    return system.Context(0, torch.cuda.current_stream().cuda_stream)
+
+
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda")
+
+
+def split_dofs(p, U):
+    primary, internal = system.element_node_split(p)
+    return (primary[:, None] * U + np.arange(U)).ravel(), (internal[:, None] * U + np.arange(U)).ravel()
+
+
+def schur(K, F, p, U):
+    """S = K_bb - K_bi K_ii^-1 K_ib, g = F_b - K_bi K_ii^-1 F_i (F [Nd, R]) and cond_2(K_ii)"""
+    b, i = split_dofs(p, U)
+    if len(i) == 0:
+        return K.copy(), F.copy(), 1.0
+    Kii = K[np.ix_(i, i)]
+    X = np.linalg.solve(Kii, np.concatenate([K[np.ix_(i, b)], F[i]], axis=1))
+    return K[np.ix_(b, b)] - K[np.ix_(b, i)] @ X[:, :len(b)], F[b] - K[np.ix_(b, i)] @ X[:, len(b):], np.linalg.cond(Kii)
+
+
+def tol(cond, K):
+    return max(1e-12, 100 * cond * 2.0 ** -52) * np.abs(K).max()
+
+
+LOCAL_CASES = [
+    # kid, ne, p, value_order, R, kparams
+    (system.KERNEL_DIFFUSION3D, 2, 1, 1, 1, [0.7, 1.3]),
+    (system.KERNEL_DIFFUSION3D, 2, 2, 1, 2, [0.7, 1.3]),
+    (system.KERNEL_DIFFUSION3D, (2, 1, 1), 3, 2, 3, [1.0, 0.5]),
+    (system.KERNEL_DIFFUSION3D, (2, 1, 1), 4, 1, 1, [1.0, 1.0]),
+    (system.KERNEL_DIFFUSION3D, (2, 1, 1), 6, 1, 1, [0.7, 1.3]),
+    (system.KERNEL_DIFFUSION3D_VAR, (2, 1, 1), 3, 2, 2, None),
+    (system.KERNEL_ADVDIFF3D, 2, 2, 1, 2, [0.7, 1.3, 0.5]),
+]
+
+
+@pytest.mark.parametrize("kid,ne,p,vo,R,kpar", LOCAL_CASES)
+def test_condense_local_vs_numpy(ctx, kid, ne, p, vo, R, kpar):
+    info = system.kernel_info(kid)
+    U, NF = info["n_unknowns"], info["n_fields"]
+    part = system.CubePartition(ne, p, perturb=0.15)
+    nq = system.n_qps1d(p, vo)
+    mesh = system.DeviceMesh(ctx, part, U)
+    mf = system.MatrixFreeSystem(mesh, kid, kpar, asm_opts=(vo, 0, 0), n_rhs=R)
+    fields = np.random.default_rng(2).uniform(-1, 1, (NF, part.n_local_nodes)) if NF else None
+    if NF:
+        mf.set_fields(dev(fields))
+    S, G = mf.condense_local()
+    S2, G2 = mf.condense_local()
+    torch.cuda.synchronize()
+    assert torch.equal(S, S2) and torch.equal(G, G2)  # bitwise reproducible
+    assert torch.equal(S, S.transpose(1, 2))  # bitwise symmetric
+    S, G = S.cpu().numpy(), G.cpu().numpy()
+    if p == 1:
+        K, Fe, _ = mf.local_assemble()
+        assert np.array_equal(S, K.cpu().numpy()) and np.array_equal(G, Fe.cpu().numpy())
+    for e in range(part.n_elems):
+        nf = fields[:, part.elem_nodes[e]].T if NF else None
+        K_ref, F_ref = O.assemble_local(kid, p, nq, R, part.elem_verts[e], nf, kpar)
+        S_ref, g_ref, cond = schur(K_ref, F_ref, p, U)
+        assert np.abs(S[e] - S_ref).max() <= tol(cond, K_ref)
+        assert np.abs(G[e].T - g_ref).max() <= max(1e-12, 100 * cond * 2.0 ** -52) * max(1.0, np.abs(F_ref).max(), np.abs(K_ref).max())
+
+
+def _global_ref(kid, p, nq, R, kpar, part, U, skip_mask=None):
+    """dense Schur complement of the oracle-assembled global matrix over all internal dofs -> (S over all dofs, rhs, b, i)"""
+    n = part.n_local_nodes * U
+    A, rhs = np.zeros((n, n)), np.zeros((n, R))
+    for e in range(part.n_elems):
+        K, F = O.assemble_local(kid, p, nq, R, part.elem_verts[e], None, kpar)
+        dofs = (part.elem_nodes[e].astype(np.int64)[:, None] * U + np.arange(U)).ravel()
+        if skip_mask is not None:  # the rows / columns of Dirichlet dofs left out, as skip_dirichlet does
+            keep = ~skip_mask[dofs].astype(bool)
+            K = K * keep[:, None] * keep[None, :]
+            F = F * keep[:, None]
+        A[np.ix_(dofs, dofs)] += K
+        rhs[dofs] += F
+    _, internal = system.element_node_split(p)
+    i = np.unique((part.elem_nodes[:, internal].astype(np.int64)[:, :, None] * U + np.arange(U)).ravel())
+    b = np.setdiff1d(np.arange(n), i)
+    full = np.zeros((n, n))
+    g = np.zeros((n, R))
+    if len(i):
+        X = np.linalg.solve(A[np.ix_(i, i)], np.concatenate([A[np.ix_(i, b)], rhs[i]], axis=1))
+        full[np.ix_(b, b)] = A[np.ix_(b, b)] - A[np.ix_(b, i)] @ X[:, :len(b)]
+        g[b] = rhs[b] - A[np.ix_(b, i)] @ X[:, len(b):]
+    return full, g, A, np.linalg.cond(A[np.ix_(i, i)]) if len(i) else 1.0
+
+
+@pytest.mark.parametrize("ne,p", [(3, 2), (2, 4)])
+def test_condense_global_vs_dense_schur(ctx, ne, p):
+    import scipy.sparse as sp
+    kid, U, R, kpar, vo = system.KERNEL_DIFFUSION3D, 4, 1, [0.7, 1.3], 1
+    part = system.CubePartition(ne, p, perturb=0.15)
+    nq = system.n_qps1d(p, vo)
+    mask = part.dirichlet_mask(U)
+    mesh = system.DeviceMesh(ctx, part, U, mask)
+    mf = system.MatrixFreeSystem(mesh, kid, kpar, asm_opts=(vo, 0, 0), n_rhs=R)
+    row_ptr, col_ind = system.condensed_graph(part.elem_nodes, p, U, np.arange(U))
+    n = part.n_local_nodes * U
+    RP, CI = torch.as_tensor(row_ptr, device="cuda"), torch.as_tensor(col_ind, device="cuda")
+    Nd = (p + 1) ** 3 * U
+    small = 2 * 3 * 8 * (Nd * Nd + Nd * R + 32 * Nd)  # about three elements per half: several sub-batches
+
+    def run(skip):
+        vals = torch.zeros(len(col_ind), dtype=torch.float64, device="cuda")
+        rhs = torch.zeros((R, n), dtype=torch.float64, device="cuda")
+        half = part.n_elems // 2
+        assert mf.condense_global(RP, CI, vals, rhs, first=0, count=half, skip_dirichlet=skip, workspace_bytes=small) == 0
+        assert mf.condense_global(RP, CI, vals, rhs, first=half, skip_dirichlet=skip) == 0
+        torch.cuda.synchronize()
+        return sp.csr_matrix((vals.cpu().numpy(), col_ind, row_ptr), shape=(n, n)).toarray(), rhs.cpu().numpy()
+
+    for skip in (False, True):
+        Sg, rhs = run(skip)
+        S_ref, g_ref, A, cond = _global_ref(kid, p, nq, R, kpar, part, U, mask if skip else None)
+        t = max(1e-12, 100 * cond * 2.0 ** -52) * np.abs(A).max()
+        assert np.abs(Sg - S_ref).max() <= t
+        assert np.abs(rhs.T - g_ref).max() <= t
+        if not skip:
+            Sg_plain, rhs_plain = Sg, rhs
+    # the same as condense_local + condensed_graph scattered on the host
+    S, G = mf.condense_local()
+    S, G = S.cpu().numpy(), G.cpu().numpy()
+    primary, _ = system.element_node_split(p)
+    A_h, r_h = np.zeros((n, n)), np.zeros((n, R))
+    for e in range(part.n_elems):
+        bd = (part.elem_nodes[e, primary].astype(np.int64)[:, None] * U + np.arange(U)).ravel()
+        A_h[np.ix_(bd, bd)] += S[e]
+        r_h[bd] += G[e].T
+    assert np.abs(A_h - Sg_plain).max() <= 1e-13 * np.abs(A_h).max()
+    assert np.abs(r_h - rhs_plain.T).max() <= 1e-13 * max(1.0, np.abs(r_h).max())
+    # a graph that lacks entries: they are skipped and counted
+    r5 = int(np.flatnonzero(np.diff(row_ptr))[3])
+    keep = np.ones(len(col_ind), bool)
+    keep[row_ptr[r5]:row_ptr[r5 + 1]][::2] = False
+    rp2 = np.concatenate([[0], np.cumsum(keep)])[row_ptr].astype(np.int64)
+    vals2 = torch.zeros(int(keep.sum()), dtype=torch.float64, device="cuda")
+    missing = mf.condense_global(torch.as_tensor(rp2, device="cuda"), torch.as_tensor(col_ind[keep], device="cuda"), vals2)
+    torch.cuda.synchronize()
+    assert missing >= (~keep).sum()
+    A2 = sp.csr_matrix((vals2.cpu().numpy(), col_ind[keep], rp2), shape=(n, n)).toarray()
+    dropped = np.zeros((n, n), bool)
+    dropped[r5, col_ind[row_ptr[r5]:row_ptr[r5 + 1]][::2]] = True
+    assert np.abs(np.where(dropped, 0.0, Sg_plain) - A2).max() <= 1e-13 * np.abs(Sg_plain).max()
+
+
+@pytest.mark.parametrize("ne,p", [(3, 2), (2, 4)])
+def test_condensed_solve_and_recovery_match_full_solve(ctx, ne, p):
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    kid, U, R, kpar, vo = system.KERNEL_DIFFUSION3D, 4, 1, [0.7, 1.3], 1
+    part = system.CubePartition(ne, p, perturb=0.15)
+    mask = part.dirichlet_mask(U)
+    mesh = system.DeviceMesh(ctx, part, U, mask)
+    mf = system.MatrixFreeSystem(mesh, kid, kpar, asm_opts=(vo, 0, 0), n_rhs=R)
+    n = part.n_local_nodes * U
+    dmask = np.asarray(mask).astype(bool).ravel()[:n]
+    gvals = np.where(dmask, np.sin(np.arange(n) * 0.37), 0.0)  # Dirichlet values
+
+    def solve(row_ptr, col_ind, assemble):
+        RP, CI = torch.as_tensor(row_ptr, device="cuda"), torch.as_tensor(col_ind, device="cuda")
+        vals = torch.zeros(len(col_ind), dtype=torch.float64, device="cuda")
+        rhs = torch.zeros((R, n), dtype=torch.float64, device="cuda")
+        assert assemble(RP, CI, vals, rhs) == 0
+        torch.cuda.synchronize()
+        A = sp.csr_matrix((vals.cpu().numpy(), col_ind, row_ptr), shape=(n, n))
+        f = rhs.cpu().numpy()[0] - A @ gvals  # Dirichlet columns eliminated on the host
+        live = np.flatnonzero((np.diff(row_ptr) > 0) & ~dmask)
+        x = gvals.copy()
+        x[live] = spla.spsolve(A[live][:, live].tocsc(), f[live])
+        return x
+
+    x_full = solve(*_full_graph(part, U), lambda RP, CI, v, r: mf.assemble_global(RP, CI, v, r))
+    x_c = solve(*system.condensed_graph(part.elem_nodes, p, U, np.arange(U)), lambda RP, CI, v, r: mf.condense_global(RP, CI, v, r))
+    _, internal = system.element_node_split(p)
+    i = np.unique((part.elem_nodes[:, internal].astype(np.int64)[:, :, None] * U + np.arange(U)).ravel())
+    X = dev(np.where(np.isin(np.arange(n), i), np.nan, x_c)[None, :])  # (internal entries must all be overwritten)
+    X2 = X.clone()
+    mf.recover_internal(X)
+    mf.recover_internal(X2)
+    torch.cuda.synchronize()
+    assert torch.equal(X, X2)  # bitwise reproducible
+    x = X.cpu().numpy()[0]
+    assert np.isfinite(x).all()
+    assert np.linalg.norm(x - x_full) <= 1e-9 * np.linalg.norm(x_full)
+
+
+def _full_graph(part, U):
+    import scipy.sparse as sp
+    dofs = (part.elem_nodes.astype(np.int64)[:, :, None] * U + np.arange(U)).reshape(part.n_elems, -1)
+    nd = dofs.shape[1]
+    n = part.n_local_nodes * U
+    G = sp.coo_matrix((np.ones(part.n_elems * nd * nd), (np.repeat(dofs, nd, axis=1).ravel(), np.tile(dofs, (1, nd)).ravel())),
+                      shape=(n, n)).tocsr()
+    G.sort_indices()
+    return G.indptr.astype(np.int64), G.indices.astype(np.int32)
+
+
+NS3D_SOURCE_FILE = "ns3d.hpp"
+ZERO_SOURCE = """
+struct ZeroOperator
+{
+    static constexpr l3k::KernelParams params{.dimension = 3, .n_equations = 1, .n_unknowns = 1};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In&, Out& out) const
+    {
+        auto& [operators, rhs] = out;
+        rhs[0]                 = 1.;
+    }
+};
+"""
+
+
+def test_plugin_u7_and_order8_vs_numpy(ctx):
+    import os
+    from l3ster_amd import plugin
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "kernels", NS3D_SOURCE_FILE)).read()
+    kid = plugin.compile_kernel("NS3D", src, 1013, shapes=[(2, 4, 1), (4, 8, 1), (6, 12, 1)])  # (as test_ns3d_plugin.py: one library)
+    cases = [(kid, 2, (1, 1, 0), system.CubePartition((2, 1, 1), 2, perturb=0.1)),
+             (system.KERNEL_DIFFUSION3D, 8, (1, 0, 0), SingleElementMesh(8, HEX))]
+    for k, p, opts, part in cases:
+        info = system.kernel_info(k)
+        U, NF = info["n_unknowns"], info["n_fields"]
+        mesh = system.DeviceMesh(ctx, part, U)
+        mf = system.MatrixFreeSystem(mesh, k, None if NF else [0.7, 1.3], asm_opts=opts)
+        if NF:
+            mf.set_fields(dev(np.random.default_rng(3).uniform(0.5, 1.0, (NF, part.n_local_nodes))))
+        K, Fe, _ = mf.local_assemble()
+        S, G = mf.condense_local()
+        torch.cuda.synchronize()
+        assert torch.equal(S, S.transpose(1, 2))
+        K, Fe, S, G = K.cpu().numpy(), Fe.cpu().numpy(), S.cpu().numpy(), G.cpu().numpy()
+        for e in range(part.n_elems):
+            S_ref, g_ref, cond = schur(K[e], Fe[e].T, p, U)
+            assert np.abs(S[e] - S_ref).max() <= tol(cond, K[e]), (k, p)
+            assert np.abs(G[e].T - g_ref).max() <= tol(cond, K[e]) + 1e-12 * np.abs(Fe[e]).max(), (k, p)
+
+
+def test_errors(ctx):
+    import ctypes as C
+    lib = system.capi.load()
+    # quads
+    quad = system.SquarePartition(3, 2)
+    qmf = system.MatrixFreeSystem(system.DeviceMesh(ctx, quad, 3), system.KERNEL_DIFFUSION2D)
+    buf = torch.zeros(1 << 16, dtype=torch.float64, device="cuda")
+    idx32 = torch.zeros(16, dtype=torch.int32, device="cuda")
+    idx64 = torch.zeros(16, dtype=torch.int64, device="cuda")
+    bp = C.c_void_p(buf.data_ptr())
+    for rc in (lib.l3k_condense_local(qmf._h, 0, 1, bp, None),
+               lib.l3k_condense_global(qmf._h, 0, 1, C.c_void_p(idx64.data_ptr()), C.c_void_p(idx32.data_ptr()), bp, None, 0, 0, 0, None),
+               lib.l3k_condensed_recover(qmf._h, 0, 1, bp, 1 << 16)):
+        assert rc < 0 and "quads" in lib.l3k_last_error().decode()
+    # ranges and null arguments
+    part = system.CubePartition(2, 2)
+    mf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, 4), system.KERNEL_DIFFUSION3D, [1.0, 1.0])
+    with pytest.raises(system.L3KError, match="outside"):
+        mf.condense_local(first=5, count=4)
+    with pytest.raises(system.L3KError, match="outside"):
+        mf.recover_internal(torch.zeros((1, part.n_local_nodes * 4), dtype=torch.float64, device="cuda"), first=-1, count=1)
+    assert lib.l3k_condense_global(mf._h, 0, 1, None, None, bp, None, 0, 0, 0, None) == -1
+    assert lib.l3k_condensed_recover(mf._h, 0, 1, None, 1 << 16) == -1
+    assert lib.l3k_condense_local(None, 0, 1, bp, None) == -1
+    # a degenerate element: the existing message
+    bad = HEX.copy()
+    bad[[0, 1]] = bad[[1, 0]]
+    dmf = system.MatrixFreeSystem(system.DeviceMesh(ctx, SingleElementMesh(2, bad), 4), system.KERNEL_DIFFUSION3D)
+    with pytest.raises(system.L3KError, match="degenerate"):
+        dmf.condense_local()
+    # K_e = 0: the pivot error, and no NaN in the global system
+    from l3ster_amd import plugin
+    zid = plugin.compile_kernel("ZeroOperator", ZERO_SOURCE, 1077, shapes=[(2, 3, 1)])
+    part = system.CubePartition(2, 2)
+    zmf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, 1), zid)
+    rp, ci = system.condensed_graph(part.elem_nodes, 2, 1, [0])
+    vals = torch.zeros(len(ci), dtype=torch.float64, device="cuda")
+    rhs = torch.zeros((1, part.n_local_nodes), dtype=torch.float64, device="cuda")
+    with pytest.raises(system.L3KError, match="non-positive pivot in the element-internal block"):
+        zmf.condense_global(torch.as_tensor(rp, device="cuda"), torch.as_tensor(ci, device="cuda"), vals, rhs)
+    torch.cuda.synchronize()
+    assert torch.isfinite(vals).all() and torch.isfinite(rhs).all()
+    with pytest.raises(system.L3KError, match="non-positive pivot"):
+        zmf.condense_local()
