@@ -1,7 +1,9 @@
 """GPU tests of static condensation (the reference's CondensationPolicy::ElementBoundary, StaticCondensationManager.hpp):
 l3k_condense_local against a numpy Schur complement of the oracle's element systems, l3k_condense_global against a dense
 Schur complement of the oracle-assembled global matrix, a condensed solve + l3k_condensed_recover against the full assembled
-solve, other shapes (a U = 7 plugin, order 8) and the error paths."""
+solve, other shapes (a U = 7 plugin, order 8) and the error paths; recovery with three right-hand sides per element against numpy,
+strict sub-ranges of condense_local / recover_internal against slices of the full range, and a mesh on which some elements fail their
+pivot while their neighbours do not."""
 import numpy as np
 import pytest
 
@@ -303,3 +305,210 @@ def test_errors(ctx):
     assert torch.isfinite(vals).all() and torch.isfinite(rhs).all()
     with pytest.raises(system.L3KError, match="non-positive pivot"):
         zmf.condense_local()
+
+
+# Diffusion3D (k = 0.7) with a source per right-hand side: the built-in kernel fills column 0 only
+SOURCES = (1.0, -2.5, 0.75)
+SOURCES_SOURCE = """
+struct Diffusion3DSources
+{
+    static constexpr l3k::KernelParams params{.dimension = 3, .n_equations = 7, .n_unknowns = 4};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In&, Out& out) const
+    {
+        constexpr double k = 0.7, s[3] = {%r, %r, %r};
+        auto& [operators, rhs] = out;
+        auto& [A0, Ax, Ay, Az] = operators;
+        Ax(0, 1) = -k;
+        Ay(0, 2) = -k;
+        Az(0, 3) = -k;
+        for (int r = 0; r < rhs.cols() && r < 3; ++r)
+            rhs(0, r) = s[r];
+        A0(1, 1) = -1.;
+        Ax(1, 0) = 1.;
+        A0(2, 2) = -1.;
+        Ay(2, 0) = 1.;
+        A0(3, 3) = -1.;
+        Az(3, 0) = 1.;
+        Ay(4, 3) = 1.;
+        Az(4, 2) = -1.;
+        Ax(5, 3) = -1.;
+        Az(5, 1) = 1.;
+        Ax(6, 2) = 1.;
+        Ay(6, 1) = -1.;
+    }
+};
+""" % SOURCES
+
+
+@pytest.fixture(scope="module")
+def sources_kid():
+    from l3ster_amd import plugin
+    return plugin.compile_kernel("Diffusion3DSources", SOURCES_SOURCE, 1078, shapes=[(2, 3, 3), (3, 4, 3), (4, 5, 3)])
+
+
+def _sources_case(ctx, kid, p, ne=(3, 2, 1)):
+    """the three-column system on a perturbed mesh, X [3, n] with three different random columns on the primary dofs and NaN on the
+    internal ones, and the internal dofs' indices"""
+    U, R = 4, 3
+    part = system.CubePartition(ne, p, perturb=0.15)
+    mf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, U), kid, asm_opts=(1, 0, 0), n_rhs=R)
+    n = part.n_local_nodes * U
+    _, internal = system.element_node_split(p)
+    i_all = np.unique((part.elem_nodes[:, internal].astype(np.int64)[:, :, None] * U + np.arange(U)).ravel())
+    x = np.random.default_rng(p).uniform(-1, 1, (R, n))
+    x[:, i_all] = np.nan
+    return part, mf, x, i_all
+
+
+@pytest.mark.parametrize("p", [2, 3, 4])
+def test_recover_three_columns_vs_numpy(ctx, sources_kid, p):
+    """l3k_condensed_recover with R = 3, per element and column against solve(K_ii, F_i - K_ib x_b) of the oracle's element systems
+    (F_e is linear in the source: column r is SOURCES[r] times the oracle's F_e for s = 1).  The 4 (p - 1)^3 internal dofs are a single
+    partial panel of 4 (p = 2), exactly one panel of 32 (p = 3), three panels and a partial one of 12 (p = 4).  The columns have
+    different x_b and different F: a value kept in the kernel's xs[] from one column to the next shows.  Bound: the relative error of
+    a Cholesky solve grows with cond(K_ii) eps -- the factor of tol(), the bound the Schur complement is held to, on the scale of
+    the solution."""
+    U, R = 4, 3
+    part, mf, x, i_all = _sources_case(ctx, sources_kid, p)
+    nq = system.n_qps1d(p, 1)
+    assert len(i_all) == part.n_elems * 4 * (p - 1) ** 3
+    X = dev(x)
+    X2 = X.clone()
+    mf.recover_internal(X)
+    mf.recover_internal(X2)
+    torch.cuda.synchronize()
+    assert torch.equal(X, X2)  # bitwise reproducible (no NaN is left: every internal dof is overwritten)
+    got = X.cpu().numpy()
+    assert np.isfinite(got).all()
+    prim = np.setdiff1d(np.arange(x.shape[1]), i_all)
+    assert np.array_equal(got[:, prim], x[:, prim])  # the primary dofs are read only
+    b, i = split_dofs(p, U)
+    for e in range(part.n_elems):
+        K_ref, F1 = O.assemble_local(system.KERNEL_DIFFUSION3D, p, nq, 1, part.elem_verts[e], None, [0.7, 1.0])
+        F_ref = F1[:, :1] * np.asarray(SOURCES)[None, :]
+        dofs = (part.elem_nodes[e].astype(np.int64)[:, None] * U + np.arange(U)).ravel()
+        Kii = K_ref[np.ix_(i, i)]
+        x_ref = np.linalg.solve(Kii, F_ref[i] - K_ref[np.ix_(i, b)] @ x[:, dofs[b]].T)  # [Ni, R]
+        assert np.abs(x_ref[:, 0] - x_ref[:, 1]).max() > 1e-3 and np.abs(x_ref[:, 1] - x_ref[:, 2]).max() > 1e-3
+        bound = tol(np.linalg.cond(Kii), np.append(x_ref.ravel(), 1.0))
+        for r in range(R):
+            assert np.abs(got[r, dofs[i]] - x_ref[:, r]).max() <= bound, (e, r)
+
+
+@pytest.mark.parametrize("p", [3, 4])
+def test_sub_ranges_equal_slices_of_the_full_range(ctx, sources_kid, p):
+    """condense_local(first, count) and recover_internal(first=, count=) over a strict sub-range: bit for bit the slices of the
+    full-range call; recovery leaves the internal dofs of the elements outside the range alone"""
+    U = 4
+    part, mf, x, i_all = _sources_case(ctx, sources_kid, p)
+    first, count = 2, 3
+    assert 0 < first and first + count < part.n_elems
+    S, G = mf.condense_local()
+    Ss, Gs = mf.condense_local(first=first, count=count)
+    torch.cuda.synchronize()
+    assert Ss.shape[0] == count and Gs.shape[0] == count
+    assert torch.equal(Ss, S[first:first + count]) and torch.equal(Gs, G[first:first + count])
+    X_full, X_sub = dev(x), dev(x)
+    mf.recover_internal(X_full)
+    mf.recover_internal(X_sub, first=first, count=count)
+    torch.cuda.synchronize()
+    full, sub = X_full.cpu().numpy(), X_sub.cpu().numpy()
+    _, internal = system.element_node_split(p)
+    in_range = np.zeros(x.shape[1], bool)
+    in_range[(part.elem_nodes[first:first + count][:, internal].astype(np.int64)[:, :, None] * U + np.arange(U)).ravel()] = True
+    outside = np.setdiff1d(i_all, np.flatnonzero(in_range))
+    assert len(outside) == (part.n_elems - count) * 4 * (p - 1) ** 3
+    assert np.isnan(sub[:, outside]).all()  # untouched
+    assert np.isfinite(full).all() and np.array_equal(sub[:, in_range], full[:, in_range])
+    prim = np.setdiff1d(np.arange(x.shape[1]), i_all)
+    assert np.array_equal(sub[:, prim], x[:, prim])
+
+
+# grad u . grad v + u v with the source 1 where x >= 0.34, nothing (K_e = 0, F_e = 0) where x < 0.34
+HALF_SPACE_X = 0.34
+HALF_SPACE_SOURCE = """
+struct HalfSpaceOperator
+{
+    static constexpr l3k::KernelParams params{.dimension = 3, .n_equations = 4, .n_unknowns = 1};
+
+    template < typename In, typename Out >
+    L3K_HD void operator()(const In& in, Out& out) const
+    {
+        auto& [operators, rhs] = out;
+        auto& [A0, Ax, Ay, Az] = operators;
+        if (in.point.space.x() < %r)
+            return;
+        Ax(0, 0) = 1.;
+        Ay(1, 0) = 1.;
+        Az(2, 0) = 1.;
+        A0(3, 0) = 1.;
+        rhs[3]   = 1.;
+    }
+};
+""" % HALF_SPACE_X
+
+
+def test_one_failing_column_of_elements_among_healthy_ones(ctx):
+    """An operator that vanishes on the elements of the first of three element layers in x (all their quadrature points have
+    x < 1/3 < 0.34 < the first quadrature point of the next layer, 1/3 + 0.113 / 3): those elements stop at their first pivot,
+    l3k_condense_global reports it, and the global system holds the healthy elements' contributions only -- finite, exactly zero in
+    the rows and columns that only failed elements touch, the dense Schur complement of the healthy elements elsewhere.  The
+    reference element systems are the tensor products of the oracle's 1-D tables on the (undistorted) box elements."""
+    import scipy.sparse as sp
+    from l3ster_amd import plugin
+    p, U, R = 2, 1, 1
+    kid = plugin.compile_kernel("HalfSpaceOperator", HALF_SPACE_SOURCE, 1079, shapes=[(2, 3, 1)])
+    ne = (3, 2, 2)
+    part = system.CubePartition(ne, p)
+    nq = system.n_qps1d(p, 1)
+    centre_x = part.elem_verts[:, :, 0].mean(axis=1)
+    failed = centre_x < 1 / 3
+    assert failed.sum() == 4 and (~failed).sum() == 8
+    assert part.elem_verts[failed][:, :, 0].max() < HALF_SPACE_X < 1 / 3 + (1 - np.sqrt(0.6)) / 6
+    mf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, U), kid)
+    n = part.n_local_nodes
+    rp, ci = system.condensed_graph(part.elem_nodes, p, U, [0])
+    vals = torch.zeros(len(ci), dtype=torch.float64, device="cuda")
+    rhs = torch.zeros((R, n), dtype=torch.float64, device="cuda")
+    with pytest.raises(system.L3KError, match="non-positive pivot in the element-internal block"):
+        mf.condense_global(torch.as_tensor(rp, device="cuda"), torch.as_tensor(ci, device="cuda"), vals, rhs)
+    torch.cuda.synchronize()
+    assert torch.isfinite(vals).all() and torch.isfinite(rhs).all()
+    Sg = sp.csr_matrix((vals.cpu().numpy(), ci, rp), shape=(n, n)).toarray()
+    g = rhs.cpu().numpy()[0]
+    # the element systems of a box with edges h: 1-D mass and stiffness matrices from the oracle's basis and Gauss rule
+    I1, D1 = O.basis_1d(p, nq)
+    _, w = O.gl_rule(nq)
+    M1, S1, m1 = (I1 * w) @ I1.T, (D1 * w) @ D1.T, I1 @ w
+    k3 = lambda az, ay, ax: np.kron(az, np.kron(ay, ax))  # node ix + n iy + n^2 iz
+    h = 1.0 / np.asarray(ne)
+    jac = np.prod(h / 2)
+    K_box = jac * (k3(M1, M1, S1) * (2 / h[0]) ** 2 + k3(M1, S1, M1) * (2 / h[1]) ** 2 + k3(S1, M1, M1) * (2 / h[2]) ** 2 + k3(M1, M1, M1))
+    F_box = jac * np.kron(m1, np.kron(m1, m1))
+    A, f = np.zeros((n, n)), np.zeros(n)
+    for e in np.flatnonzero(~failed):
+        assert np.allclose(np.ptp(part.elem_verts[e], axis=0), h)
+        d = part.elem_nodes[e].astype(np.int64)
+        A[np.ix_(d, d)] += K_box
+        f[d] += F_box
+    _, internal = system.element_node_split(p)
+    i = np.unique(part.elem_nodes[~failed][:, internal].astype(np.int64).ravel())
+    touched = np.zeros(n, bool)
+    touched[part.elem_nodes[~failed].ravel()] = True
+    only_failed = ~touched
+    assert only_failed.sum() > 0 and len(i) == 8
+    b = np.setdiff1d(np.flatnonzero(touched), i)
+    S_ref, g_ref = np.zeros((n, n)), np.zeros(n)
+    X = np.linalg.solve(A[np.ix_(i, i)], np.concatenate([A[np.ix_(i, b)], f[i, None]], axis=1))
+    S_ref[np.ix_(b, b)] = A[np.ix_(b, b)] - A[np.ix_(b, i)] @ X[:, :len(b)]
+    g_ref[b] = f[b] - A[np.ix_(b, i)] @ X[:, -1]
+    assert not Sg[only_failed].any() and not Sg[:, only_failed].any() and not g[only_failed].any()  # exactly zero
+    assert np.abs(Sg[np.ix_(b, b)]).max() > 0.01
+    t = max(1e-12, 100 * np.linalg.cond(A[np.ix_(i, i)]) * 2.0 ** -52) * np.abs(A).max()  # (test_condense_global_vs_dense_schur)
+    assert np.abs(Sg - S_ref).max() <= t
+    assert np.abs(g - g_ref).max() <= t
+    # the local route names the same error
+    with pytest.raises(system.L3KError, match="non-positive pivot"):
+        mf.condense_local()
