@@ -313,8 +313,10 @@ int l3k_update_solution(l3k_ctx* ctx, l3k_mesh* mesh, const double* d_x, size_t 
  *   l3k_cg_*           : the fused vector kernels of one iteration for partitioned vectors; the caller all-reduces the
  *                        device scalar block s[8] (0 <r,z>, 1 <p,Ap>, 2 <r,z> new, 3 <r,r>) between them.  Protocol below
  *                        (l3k_cg_init, _dot_pap, _update_z, _update_px): init and update_z write LOCAL sums into s[2], s[3];
- *                        all-reduce them before the next call; after init also copy s[2] to s[0] once the reduced value is
- *                        in place. */
+ *                        all-reduce them before the next call.  init also stores its LOCAL s[2] in s[0] (all a single rank
+ *                        needs); a host that reduces across ranks copies s[2] to s[0] again once the reduced value is in
+ *                        place.  Slots written: init 0, 2, 3; dot_pap 1; update_z 2, 3; update_px 0.  No call writes any
+ *                        other slot: 4..7 are the caller's. */
 typedef struct
 {
     double tol;
@@ -337,7 +339,9 @@ int l3k_pcg_solve_cols(l3k_mf* mf, const double* d_b, size_t ldb, double* d_x, s
                        const l3k_cg_opts* opts, l3k_cg_result* results);
 /* The pieces of the iteration for hosts that reduce the scalars across ranks themselves (d_s: device block, 0 <r,z> old, 1 <p,Ap>,
  * 2 <r,z> new, 3 <r,r>).  The iteration keeps the preconditioned residual z = M^-1 r instead of r (9 instead of 11 vector passes):
- *   l3k_cg_init:      d_z holds A x0 on entry; z = minv (b - A x0), p = z, s[2] = <r,z>, s[3] = <r,r> (this rank's share)
+ *   l3k_cg_init:      d_z holds A x0 on entry; z = minv (b - A x0), p = z, s[2] = <r,z>, s[3] = <r,r> (this rank's share),
+ *                     s[0] <- s[2] (this rank's share as well: all-reduce s[2], s[3], then copy s[2] to s[0])
+ *   l3k_cg_dot_pap:   s[1] = <p, Ap> (this rank's share)
  *   l3k_cg_update_z:  alpha = s[0]/s[1]; z -= alpha minv Ap; s[2], s[3] as above (r = z / minv)
  *   l3k_cg_update_px: x += alpha p; beta = s[2]/s[0]; p = z + beta p; then s[0] <- s[2]
  * d_minv may be NULL (no preconditioner: z = r). */

@@ -1100,9 +1100,12 @@ int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, s
         return -1;
     }
     buf[0] = '\0';
-    // (with_energy: any non-null device pointer, nothing is launched)
+    // (with_energy: any non-null device pointer, nothing is launched; with boundary terms attached l3k_mf_energy_begin does not
+    // arm the accumulation, and the route says so)
     l3k::dev::ElemArgs a;
-    if (int rc = fillArgs(mf, which, ncols, a, with_energy ? reinterpret_cast< double* >(mf->ctx->red_ws) : mf->energy_target))
+    double* const      energy = with_energy ? (mf->boundary_terms.empty() ? reinterpret_cast< double* >(mf->ctx->red_ws) : nullptr)
+                                            : mf->energy_target;
+    if (int rc = fillArgs(mf, which, ncols, a, energy))
         return rc;
     if (mf->ctx->deterministic)
         a.energy = nullptr; // (forEachLaunchRange)

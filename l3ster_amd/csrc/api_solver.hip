@@ -30,12 +30,13 @@ __global__ __launch_bounds__(cg_threads) void cgDotKernel(const double* __restri
     if (threadIdx.x == 0)
         partial[blockIdx.x] = t;
 }
-// s[dst0] = sum partial[0][:], s[dst1] = sum partial[1][:] (dst1 < 0: one row); shift != 0: s[0] = s[2] first
+// s[dst0] = sum partial[0][:], s[dst1] = sum partial[1][:] (dst1 < 0: one row; dst0 < 0: no row, no other slot is written);
+// shift != 0: then s[0] = s[2]
 __global__ __launch_bounds__(cg_threads) void cgFinishKernel(const double* __restrict__ partial, int n_blocks, double* __restrict__ s,
                                                              int dst0, int dst1, int shift)
 {
     __shared__ double sh[cg_threads];
-    for (int row = 0; row < (dst1 >= 0 ? 2 : 1); ++row)
+    for (int row = 0; row < (dst0 < 0 ? 0 : dst1 >= 0 ? 2 : 1); ++row)
     {
         double acc = 0.;
         for (int i = threadIdx.x; i < n_blocks; i += cg_threads)
@@ -215,7 +216,7 @@ int l3k_cg_update_px(l3k_ctx* ctx, double* d_p, double* d_x, const double* d_z, 
     const int g = cgGrid(n);
     hipLaunchKernelGGL(cgUpdatePXKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_p, d_x, d_z, n, d_s);
     // <r,z> of this iteration becomes the old one: after every block has read alpha and beta
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, 0, d_s, 4, -1, 1);
+    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, 0, d_s, -1, -1, 1);
     L3K_HIP(hipGetLastError());
     return 0;
 }

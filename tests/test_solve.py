@@ -375,3 +375,254 @@ def test_config5_partitioned_pcg_advdiff_order4():
         num += np.sum((x.reshape(-1, U) - xr[rows]) ** 2)
         den += np.sum(xr[rows] ** 2)
     assert np.sqrt(num / den) < 1e-7
+
+
+# ------------------------------------------------------------------------------------------------ the driver l3k_pcg_solve
+_SMALL = {}
+
+
+def _small_problem(deterministic=False):
+    """A 2^3 order-2 perturbed cube, Diffusion3D with a source, Dirichlet mask (500 dofs), with its operator as a dense matrix:
+    column j is mf.apply on the unit vector e_j.  Cached per module; `deterministic`: on a context in deterministic mode."""
+    if deterministic in _SMALL:
+        return _SMALL[deterministic]
+    torch.cuda.set_device(0)
+    ctx = system.Context(0, torch.cuda.current_stream().cuda_stream)
+    if deterministic:
+        ctx.set_deterministic(True)
+    p, U = 2, 4
+    part = system.CubePartition(2, p, perturb=0.1)
+    mesh = system.DeviceMesh(ctx, part, U, part.dirichlet_mask(U))
+    mf = system.MatrixFreeSystem(mesh, system.KERNEL_DIFFUSION3D, [1.0, 1.0])
+    diag, rhs = mf.diag_rhs(None)
+    n = diag.numel()
+    assert n == 5 ** 3 * U
+    E, Y = torch.zeros(n, dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda")
+    A = np.empty((n, n))
+    for j in range(n):
+        E.zero_()
+        E[j] = 1.0
+        mf.apply(E[None, :], Y[None, :])
+        A[:, j] = Y.cpu().numpy()
+    assert np.abs(A - A.T).max() <= 1e-12 * np.abs(A).max()
+    A = 0.5 * (A + A.T)
+    minv = solve.jacobi_inverse_native(ctx, diag)
+    x0 = torch.as_tensor(0.1 * np.random.default_rng(7).standard_normal(n), device="cuda")
+    P = dict(ctx=ctx, mesh=mesh, mf=mf, A=A, b=rhs[0].contiguous(), minv=minv, x0=x0, n=n)
+    _SMALL[deterministic] = P
+    return P
+
+
+def _float64_cost(P):
+    """What float64 alone costs on this matrix: the distance between cg_ref.pcg_ref in longdouble and the same recurrence in
+    float64 numpy (both on the CPU, neither is the code under test), largest value over the first six steps.  Distances:
+    ||x_64 - x_ld|| / ||x_ld|| and |res_64 - res_ld| / ||b - A x0|| -- rounding errors of a residual are absolute (eps |A| |x|),
+    so they are measured against the residual the iteration starts from, not against the one it has reached."""
+    import cg_ref as R
+    if "cost" not in P:
+        A, b, x0, minv = P["A"], P["b"].cpu().numpy(), P["x0"].cpu().numpy(), P["minv"].cpu().numpy()
+        r0 = float(R.pcg_ref(A, b, x0, minv, 0)[1])
+        worst = 0.0
+        for k in range(1, 7):
+            x_ld, res_ld, _, _ = R.pcg_ref(A, b, x0, minv, k)
+            x_64, res_64, _, _ = R.pcg_ref(A, b, x0, minv, k, dtype=np.float64)
+            dx = float(np.linalg.norm((x_64.astype(R.LD) - x_ld).astype(np.float64)) / np.linalg.norm(x_ld.astype(np.float64)))
+            worst = max(worst, dx, abs(float(res_64) - float(res_ld)) / r0)
+        P["cost"], P["r0"] = worst, r0
+        print(f"float64 against longdouble over the first six steps: {worst:.3e}; bound 10x = {10 * worst:.3e}")
+    return P["cost"]
+
+
+def _true_residual(P, x, minv=None):
+    import cg_ref as R
+    r = P["b"].cpu().numpy().astype(R.LD) - P["A"].astype(R.LD) @ x.cpu().numpy().astype(R.LD)
+    return float(np.sqrt(np.sum(r * r)))
+
+
+@pytest.mark.gpu
+def test_first_pcg_steps_match_the_longdouble_recurrence():
+    """k = 1..6 iterations of l3k_pcg_solve from a non-zero start against k steps of Hestenes-Stiefel PCG in longdouble on the
+    dense operator: x, and achieved_tol against the true ||b - A x||.  A beta that is slightly off or a dot product that drops
+    entries shows here at once; in a converged solve it would not."""
+    import cg_ref as R
+    P = _small_problem()
+    # measured on this matrix: float64 against longdouble 1.232e-15 (largest of the six steps, both distances); the bound is
+    # 10x the value measured in this run, 1.232e-14 (the matrix comes from applies that scatter with atomics, so the last
+    # digits may move).  The factor 10 covers the different summation order on the device, which stayed below 1.5e-15 in x
+    # and 3e-17 in the residual.
+    bound = 10 * _float64_cost(P)
+    assert 1e-16 < bound < 1e-12
+    A, b, x0, minv = P["A"], P["b"].cpu().numpy(), P["x0"].cpu().numpy(), P["minv"].cpu().numpy()
+    for k in range(1, 7):
+        x_ld, res_ld, steps, _ = R.pcg_ref(A, b, x0, minv, k)
+        assert len(steps) == k
+        x = P["x0"].clone()
+        res = solve.pcg(P["mf"], P["b"], x, P["minv"], tol=0.0, max_iters=k, residual_scaling="none", throw_on_fail=False)
+        assert res.num_iters == k and not res.converged
+        dx = float(np.linalg.norm((x.cpu().numpy().astype(R.LD) - x_ld).astype(np.float64)) / np.linalg.norm(x_ld.astype(np.float64)))
+        dres = abs(res.tol - float(res_ld)) / P["r0"]
+        dtrue = abs(res.tol - _true_residual(P, x)) / P["r0"]
+        print(f"k={k}: x {dx:.3e} achieved_tol against pcg_ref {dres:.3e} against ||b - A x|| {dtrue:.3e} (bound {bound:.3e})")
+        assert dx <= bound and dres <= bound and dtrue <= bound
+
+
+@pytest.mark.gpu
+def test_pcg_residual_scaling_modes():
+    """residual_scaling "none" / "initial" / "rhs": achieved_tol is the true residual over 1, ||b - A x0||, ||b||, and the larger
+    the scale the fewer iterations reach one tolerance."""
+    P = _small_problem()
+    bound = 10 * _float64_cost(P)
+    bnorm = float(np.linalg.norm(P["b"].cpu().numpy()))
+    scales = {"none": 1.0, "initial": P["r0"], "rhs": bnorm}
+    its = {}
+    for mode, scale in scales.items():
+        x = P["x0"].clone()
+        res = solve.pcg(P["mf"], P["b"], x, P["minv"], tol=1e-3, residual_scaling=mode)
+        assert res.converged and res.tol <= 1e-3
+        true = _true_residual(P, x)
+        print(f"{mode}: scale {scale:.6e} iterations {res.num_iters} achieved {res.tol:.6e} true/scale {true / scale:.6e}")
+        assert abs(res.tol * scale - true) <= bound * P["r0"]
+        its[mode] = res.num_iters
+    order = sorted(scales, key=lambda m: scales[m])
+    assert len({round(scales[m], 6) for m in order}) == 3  # three different scales, or the test says nothing
+    assert its[order[0]] >= its[order[1]] >= its[order[2]] and its[order[0]] > its[order[2]]
+
+
+@pytest.mark.gpu
+def test_pcg_check_every_on_the_single_rank_driver():
+    """check_every = 7: the driver looks at the residual every 7th iteration only, so it stops at a multiple of 7 (or at
+    max_iters), with the iterate the every-iteration driver has at that count -- bit for bit on a context in deterministic mode
+    (no atomics in the apply, <p, A p> from the fixed-order dot product)."""
+    P = _small_problem(deterministic=True)
+    x1 = P["x0"].clone()
+    r1 = solve.pcg(P["mf"], P["b"], x1, P["minv"], tol=1e-8, residual_scaling="rhs")
+    x7 = P["x0"].clone()
+    r7 = solve.pcg(P["mf"], P["b"], x7, P["minv"], tol=1e-8, residual_scaling="rhs", check_every=7)
+    assert r7.converged and r7.num_iters % 7 == 0 and r1.num_iters <= r7.num_iters < r1.num_iters + 7
+    xs = P["x0"].clone()
+    rs = solve.pcg(P["mf"], P["b"], xs, P["minv"], tol=0.0, residual_scaling="rhs", max_iters=r7.num_iters, throw_on_fail=False)
+    assert rs.num_iters == r7.num_iters and torch.equal(xs, x7) and rs.tol == r7.tol
+    # max_iters that is no multiple of 7: the last iteration is checked as well
+    xm = P["x0"].clone()
+    rm = solve.pcg(P["mf"], P["b"], xm, P["minv"], tol=0.0, residual_scaling="rhs", max_iters=10, check_every=7, throw_on_fail=False)
+    xe = P["x0"].clone()
+    re = solve.pcg(P["mf"], P["b"], xe, P["minv"], tol=0.0, residual_scaling="rhs", max_iters=10, throw_on_fail=False)
+    assert rm.num_iters == 10 and torch.equal(xm, xe) and rm.tol == re.tol
+
+
+@pytest.mark.gpu
+def test_pcg_max_iters_reached():
+    P = _small_problem()
+    x = P["x0"].clone()
+    res = solve.pcg(P["mf"], P["b"], x, P["minv"], tol=1e-10, residual_scaling="rhs", max_iters=3, throw_on_fail=False)
+    assert res.converged is False and res.num_iters == 3 and res.tol > 1e-10
+    bnorm = float(np.linalg.norm(P["b"].cpu().numpy()))
+    assert abs(res.tol * bnorm - _true_residual(P, x)) <= 10 * _float64_cost(P) * P["r0"]
+    with pytest.raises(RuntimeError, match="failed to converge"):
+        solve.pcg(P["mf"], P["b"], P["x0"].clone(), P["minv"], tol=1e-10, residual_scaling="rhs", max_iters=3)
+
+
+@pytest.mark.gpu
+def test_pcg_null_opts_are_the_documented_defaults():
+    """opts == NULL through the raw C call behaves as {1e-6, 10000, 0, 1} (bit for bit on a deterministic context); d_minv ==
+    NULL is the preconditioner of ones."""
+    import ctypes as C
+    from l3ster_amd import capi
+    P = _small_problem(deterministic=True)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    xn, res = P["x0"].clone(), capi.CgResult()
+    capi.check(capi.load().l3k_pcg_solve(P["mf"]._h, vp(P["b"]), vp(xn), vp(P["minv"]), None, C.byref(res)))
+    xd = P["x0"].clone()
+    rd = solve.pcg(P["mf"], P["b"], xd, P["minv"], tol=1e-6, max_iters=10000, residual_scaling="none", check_every=1)
+    assert res.converged == 1 and res.iterations == rd.num_iters and res.achieved_tol == rd.tol and torch.equal(xn, xd)
+    assert res.achieved_tol <= 1e-6 and res.iterations > 3
+    # a tolerance ten times tighter takes more iterations: the 1e-6 above is the one that stopped the NULL run
+    rt = solve.pcg(P["mf"], P["b"], P["x0"].clone(), P["minv"], tol=1e-7, residual_scaling="none")
+    assert rt.num_iters > rd.num_iters
+    x_none, x_ones = P["x0"].clone(), P["x0"].clone()
+    r_none = solve.pcg(P["mf"], P["b"], x_none, None, tol=1e-6)
+    r_ones = solve.pcg(P["mf"], P["b"], x_ones, torch.ones_like(P["minv"]), tol=1e-6)
+    assert r_none.num_iters == r_ones.num_iters and r_none.tol == r_ones.tol and torch.equal(x_none, x_ones)
+
+
+@pytest.mark.gpu
+def test_pcg_start_vector_that_solves_the_system():
+    P = _small_problem()
+    x = P["x0"].clone()
+    assert solve.pcg(P["mf"], P["b"], x, P["minv"], tol=1e-12, residual_scaling="rhs").converged
+    before = x.clone()
+    res = solve.pcg(P["mf"], P["b"], x, P["minv"], tol=1e-10, residual_scaling="rhs")
+    assert res.converged and res.num_iters == 0 and torch.equal(x, before) and res.tol <= 1e-10
+    # b = 0 from x0 = 0 under "rhs" scaling: 0 / max(0, 1e-300), not 0 / 0
+    zero, x = torch.zeros_like(P["b"]), torch.zeros_like(P["b"])
+    res = solve.pcg(P["mf"], zero, x, P["minv"], tol=1e-6, residual_scaling="rhs")
+    assert res.converged and res.num_iters == 0 and res.tol == 0.0 and float(x.abs().max()) == 0.0
+
+
+@pytest.mark.gpu
+def test_native_pcg_past_the_grid_caps():
+    """One solve whose vectors are longer than one grid of the vector kernels (1024 blocks of 256 threads = 262 144 entries):
+    cube 12^3, order 4, U = 4.  l3k_pcg_solve and the partitioned form against the torch-op PCG (independent of the HIP vector
+    kernels), and the true residual recomputed with one apply."""
+    torch.cuda.set_device(0)
+    ctx = system.Context(0, torch.cuda.current_stream().cuda_stream)
+    p, U, tol = 4, 4, 1e-10
+    part = system.CubePartition(12, p, perturb=0.1)
+    mesh = system.DeviceMesh(ctx, part, U, part.dirichlet_mask(U))
+    mf = system.MatrixFreeSystem(mesh, system.KERNEL_DIFFUSION3D, [1.0, 1.0])
+    diag, rhs = mf.diag_rhs(None)
+    n = diag.numel()
+    assert n == 49 ** 3 * 4 == 470596 and n > 256 * 1024
+    minv = solve.jacobi_inverse_native(ctx, diag)
+    assert torch.equal(minv, solve.jacobi_inverse(diag))
+    b = rhs[0]
+    x1 = torch.zeros_like(diag)
+    r1 = solve.cg(lambda v, out: mf.apply(v[None, :], out[None, :]), b, x1, minv, tol=tol, residual_scaling="rhs")
+    x2 = torch.zeros_like(diag)
+    r2 = solve.pcg(mf, b, x2, minv, tol=tol, residual_scaling="rhs")
+    assert r2.converged and abs(r1.num_iters - r2.num_iters) <= 1
+    assert (x1 - x2).norm().item() < 1e-8 * x1.norm().item()
+
+    class Op:
+        def apply(self, X, Y):
+            mf.apply(X, Y)
+    x3 = torch.zeros_like(diag)
+    r3 = solve.pcg_distributed(Op(), ctx, b, x3, minv, tol=tol, residual_scaling="rhs")
+    assert abs(r3.num_iters - r2.num_iters) <= 1 and (x3 - x2).norm().item() < 1e-8 * x2.norm().item()
+    ax = torch.empty_like(diag)
+    for x in (x2, x3):
+        mf.apply(x[None, :], ax[None, :])
+        true = ((b - ax).norm() / b.norm()).item()
+        print(f"n={n}: iterations {r1.num_iters} / {r2.num_iters} / {r3.num_iters}, true residual {true:.3e}")
+        assert true <= 2 * tol
+
+
+@pytest.mark.gpu
+def test_apply_energy_with_a_boundary_term_takes_the_dot_product():
+    """With a boundary term attached the element kernel does not accumulate <x, A x> (the term's share would be missing):
+    l3k_mf_apply_energy is the apply followed by l3k_cg_dot_pap, and writes slot 1 alone."""
+    U, p = 4, 4
+    ctx = system.Context(0, torch.cuda.current_stream().cuda_stream)
+    ctx.set_tuning(generic_below=0)
+    part = system.CubePartition(5, p, perturb=0.1)
+    mesh = system.DeviceMesh(ctx, part, U, part.dirichlet_mask(U, sides=(4, 5)))
+    mf = system.MatrixFreeSystem(mesh, system.KERNEL_DIFFUSION3D, [0.7, 1.0])
+    assert " energy" in mf.route(with_energy=True)
+    mf.attach_boundary(system.BoundaryTerm(mesh, system.KERNEL_ROBIN3D, *part.boundary_sides([1]), kernel_params=[2.0, 0.7]))
+    assert "sumfactFastKernel" in mf.route(with_energy=True) and " energy" not in mf.route(with_energy=True), mf.route(with_energy=True)
+    X = torch.as_tensor(part.synthetic_vector(U), device="cuda")
+    Y = torch.full_like(X, 3.0)
+    S = torch.as_tensor(np.arange(8) + 7.5, device="cuda")
+    mf.apply_energy(X, Y, S)
+    Yr = torch.zeros_like(X)
+    mf.apply(X, Yr)
+    Y0 = torch.zeros_like(X)  # the boundary term is in: the operator without it gives another product
+    torch.cuda.synchronize()
+    want = float((X * Yr).sum())
+    assert float((Y - Yr).abs().max()) <= 1e-12 * float(Yr.abs().max())
+    assert abs(float(S[1]) - want) <= 1e-12 * abs(want)
+    h = S.cpu().numpy()
+    assert np.array_equal(np.delete(h, 1), np.delete(np.arange(8) + 7.5, 1))  # slots 0 and 2 (and 3..7) untouched
+    plain = system.MatrixFreeSystem(mesh, system.KERNEL_DIFFUSION3D, [0.7, 1.0])
+    plain.apply(X, Y0)
+    assert abs(float((X * Y0).sum()) - want) > 1e-6 * abs(want)
