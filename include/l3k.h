@@ -191,6 +191,10 @@ int l3k_mf_set_time(l3k_mf* mf, double time);
  * decided by the same code as the launch itself.  For run-time reports (bench.py prints it) and for tests that assert a route.
  * with_energy != 0: as inside l3k_mf_apply_energy / between l3k_mf_energy_begin and _end. */
 int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, size_t n);
+/* The variant of the single-wave element kernel that the calling thread launched last (0: none yet).  l3k_mf_route is made
+ * without the operands, so it cannot tell whether ghost rows directly behind the owned rows were recognised; this can.  Bits:
+ * 1 launched, 2 split-ghost, 4 affine, 8 energy, 16 multi-column, 32 strided-dofs, 64 dynamic batches, 128 right-hand side. */
+int l3k_last_fast_launch(unsigned* variant);
 
 /* Y <- alpha*A*X + beta*Y.  Operator::apply / applyImpl, algsys/MatrixFreeSystem.hpp:34-41,1020-1140, for a rank
  * without ghosts (n_ghost_nodes == 0): scale (:1038), gather with Dirichlet -> 0 (:421-467), sum-factorised element

@@ -106,6 +106,7 @@ SIGNATURES = {
     "l3k_ctx_get_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "l3k_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "l3k_mf_route": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "l3k_last_fast_launch": (C.c_int, [C.POINTER(C.c_uint)]),
     "l3k_ctx_synchronize": (C.c_int, [_vp]),
     "l3k_ctx_destroy": (C.c_int, [_vp]),
     "l3k_mesh_create": (C.c_int, [_vp, C.POINTER(MeshDesc), C.POINTER(_vp)]),

@@ -1092,6 +1092,55 @@ int l3k_mf_set_time(l3k_mf* mf, double time)
     return 0;
 }
 
+extern "C++" int checkApplyOperands(const l3k_mf* mf, int ncols, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, const double* d_y,
+                       size_t ldy, const double* d_yghost, size_t ldyg)
+{
+    const l3k_mesh* m = mf->mesh;
+    if (mf->kp.n_fields > 0 && !mf->fields)
+    {
+        setError("kernel reads %d external fields but l3k_mf_set_fields was not called", mf->kp.n_fields);
+        return -1;
+    }
+    if (ncols < 1 || ncols > mf->n_rhs)
+    {
+        // algsys/MatrixFreeSystem.hpp:1035-1037
+        setError("number of columns (%d) must be in [1, n_rhs = %d]", ncols, mf->n_rhs);
+        return -1;
+    }
+    if (ldx < size_t(m->nOwnedDofs()) || ldy < size_t(m->nOwnedDofs()))
+    {
+        setError("leading dimension smaller than the number of owned dofs");
+        return -1;
+    }
+    // the kernels move a node's dofs with 16-byte accesses (and run 18 % slower when a node's row straddles a 32-byte
+    // boundary: profiles/r01_kbench_vector_alignment.log)
+    const auto misaligned = [](const void* p, size_t ld, int nc) {
+        return reinterpret_cast< uintptr_t >(p) % 16 != 0 || (nc > 1 && (ld * sizeof(double)) % 16 != 0);
+    };
+    // only the one-wave kernel uses 16-byte accesses: it takes dense dof layouts with an even number of unknowns
+    // (FastCfg::feasible); every other shape runs the generic kernel with 8-byte accesses
+    if (mf->dense && mf->kp.n_unknowns % 2 == 0 &&
+        (misaligned(d_x, ldx, ncols) || misaligned(d_y, ldy, ncols) ||
+         (m->n_ghost_nodes > 0 && d_xghost && misaligned(d_xghost, ldxg, ncols)) ||
+         (m->n_ghost_nodes > 0 && d_yghost && misaligned(d_yghost, ldyg, ncols))))
+    {
+        setError("vectors must be 16-byte aligned (columns too: even leading dimensions); 32-byte alignment is faster");
+        return -1;
+    }
+    return 0;
+}
+
+int l3k_last_fast_launch(unsigned* variant)
+{
+    if (!variant)
+    {
+        setError("l3k_last_fast_launch: null argument");
+        return -1;
+    }
+    *variant = l3k::dev::lastFastLaunch();
+    return 0;
+}
+
 int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, size_t n)
 {
     if (!mf || !buf || n == 0)
@@ -1177,29 +1226,11 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     if (a.elem_count > 0 && (a.energy || mf->energy_target)) // (armed but ncols > 1: a.energy is null, never "fused")
         ++mf->energy_expected;
     const l3k_mesh* m = mf->mesh;
-    if (ldx < size_t(m->nOwnedDofs()) || ldy < size_t(m->nOwnedDofs()))
-    {
-        setError("leading dimension smaller than the number of owned dofs");
-        return -1;
-    }
+    if (int rc = checkApplyOperands(mf, ncols, d_x, ldx, d_xghost, ldxg, d_y, ldy, d_yghost, ldyg))
+        return rc;
     if (m->n_ghost_nodes > 0 && (which == 1 || which == 2) && (!d_xghost || !d_yghost))
     {
         setError("mesh has ghost nodes: border elements need the ghost import/export buffers");
-        return -1;
-    }
-    // the kernels move a node's dofs with 16-byte accesses (and run 18 % slower when a node's row straddles a 32-byte
-    // boundary: profiles/r01_kbench_vector_alignment.log)
-    const auto misaligned = [](const void* p, size_t ld, int nc) {
-        return reinterpret_cast< uintptr_t >(p) % 16 != 0 || (nc > 1 && (ld * sizeof(double)) % 16 != 0);
-    };
-    // only the one-wave kernel uses 16-byte accesses: it takes dense dof layouts with an even number of unknowns
-    // (FastCfg::feasible); every other shape runs the generic kernel with 8-byte accesses
-    if (mf->dense && mf->kp.n_unknowns % 2 == 0 &&
-        (misaligned(d_x, ldx, ncols) || misaligned(d_y, ldy, ncols) ||
-         (m->n_ghost_nodes > 0 && d_xghost && misaligned(d_xghost, ldxg, ncols)) ||
-         (m->n_ghost_nodes > 0 && d_yghost && misaligned(d_yghost, ldyg, ncols))))
-    {
-        setError("vectors must be 16-byte aligned (columns too: even leading dimensions); 32-byte alignment is faster");
         return -1;
     }
     a.x     = d_x;
@@ -1343,6 +1374,14 @@ int l3k_mf_apply(l3k_mf* mf, const double* d_x, size_t ldx, double* d_y, size_t 
         setError("l3k_mf_apply is the single-rank form; this mesh has ghost nodes: use the split-phase entry points");
         return -1;
     }
+    if (!d_x || !d_y)
+    {
+        setError("l3k_mf_apply: null argument");
+        return -1;
+    }
+    // (a refused call leaves y as it was: the refusals come before the scaling pass)
+    if (int rc = checkApplyOperands(mf, ncols, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0))
+        return rc;
     if (int rc = l3k_mf_scale(mf, d_y, ldy, ncols, beta))
         return rc;
     if (int rc = l3k_mf_apply_elems(mf, 2, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0, ncols, alpha, beta))

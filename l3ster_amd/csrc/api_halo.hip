@@ -734,6 +734,8 @@ int l3k_mf_apply_dist(l3k_mf* mf, l3k_halo* h, const double* d_x, size_t ldx, do
     hipStream_t  s   = mf->ctx->stream;
     const size_t ldg = size_t(std::max< int64_t >(h->n_ghost_dofs, 1));
     double *     xg = h->xg.ptr, *yg = h->yg.ptr;
+    if (int rc = checkApplyOperands(mf, ncols, d_x, ldx, xg, ldg, d_y, ldy, yg, ldg)) // (a refused call leaves y as it was)
+        return rc;
     if (int rc = l3k_mf_scale(mf, d_y, ldy, ncols, beta)) // (:1038)
         return rc;
     L3K_HIP(hipMemsetAsync(yg, 0, sizeof(double) * ldg * ncols, s)); // export buffer <- 0 (:1048)

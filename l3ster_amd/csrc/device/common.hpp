@@ -183,6 +183,9 @@ template < typename K >
 struct ResidualId;
 
 void setError(const char* fmt, ...);
+// the variant of the calling thread's last launch of the single-wave kernel: the bits of l3k_last_fast_launch (include/l3k.h)
+void     noteFastLaunch(unsigned variant);
+unsigned lastFastLaunch();
 // compute units of the current device (cached per device)
 int deviceComputeUnits();
 // lets `fn` take `bytes` of dynamic LDS on the current device (hipFuncSetAttribute, once per function and device; thread-safe)

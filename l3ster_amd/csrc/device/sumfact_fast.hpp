@@ -1413,6 +1413,8 @@ int launchFastKernel(const ElemArgs& a, const FastRoute& r, const void* kparam_b
         setError("hipMemsetAsync(work counters) failed");
         return -3;
     }
+    noteFastLaunch(1u | (r.split ? 2u : 0u) | (r.affine ? 4u : 0u) | (r.energy ? 8u : 0u) | (r.multi ? 16u : 0u) | (r.strided ? 32u : 0u) |
+                   (r.dynamic ? 64u : 0u) | (RHS ? 128u : 0u));
     return launchKernel(RHS ? "sumfactFastKernel (rhs)" : "sumfactFastKernel", fastKernel< K, P, NQ, RHS >(r), dim3(r.grid), dim3(64),
                         FastCfg< K, P, NQ >::lds, stream, a, functorFrom< K >(kparam_blob), r.n_batches, r.xcd_chunk, tab);
 }

@@ -141,4 +141,13 @@ const char* lastError()
 {
     return g_error.c_str();
 }
+thread_local unsigned g_fast_launch = 0;
+void                  noteFastLaunch(unsigned variant)
+{
+    g_fast_launch = variant;
+}
+unsigned lastFastLaunch()
+{
+    return g_fast_launch;
+}
 } // namespace l3k::dev

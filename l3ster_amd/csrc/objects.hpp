@@ -288,6 +288,10 @@ struct KernelMeta
 const KernelMeta* findKernel(int id);
 const KernelMeta* findResidual(int id);
 } // namespace l3k::api
+// api.hip: the refusals of an apply that its operands alone decide (fields set, number of columns, leading dimensions, alignment
+// of x, y and, where given, the ghost buffers): 0, or -1 with the error set.  The apply entry points call it before their first launch
+int checkApplyOperands(const l3k_mf* mf, int ncols, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, const double* d_y,
+                       size_t ldy, const double* d_yghost, size_t ldyg);
 // api_assembled.hip: `count` element matrices from the tiled layout of l3k_local_assemble_tiled to the row-major one, on stream s
 int launchTiledToRowMajor(int U, int N1, int64_t count, const double* d_Kt, double* d_K, hipStream_t s);
 // ... and the upper triangles overwritten by the mirrored lower ones (bitwise symmetric matrices, as the reference's)

@@ -94,6 +94,14 @@ def instances():
     return out
 
 
+def last_fast_launch():
+    """The variant of the single-wave element kernel this thread launched last, as a set of names (l3k_last_fast_launch)."""
+    v = C.c_uint(0)
+    check(capi.load().l3k_last_fast_launch(C.byref(v)))
+    names = ["launched", "split-ghost", "affine", "energy", "multi-column", "strided-dofs", "dynamic", "rhs"]
+    return {n for i, n in enumerate(names) if v.value >> i & 1}
+
+
 # ------------------------------------------------------------------------------------------------------- mesh
 class CubePartition:
     """One rank's block of a structured order-p hex mesh of [0,1]^3 (host arrays, reference numbering conventions)."""
@@ -429,8 +437,8 @@ class BoundaryTerm:
         """Y += alpha * A_b X"""
         nc, ldx = MatrixFreeSystem._cols(X)
         _, ldy = MatrixFreeSystem._cols(Y)
-        ldxg = XG.shape[1] if XG is not None else 0
-        ldyg = YG.shape[1] if YG is not None else 0
+        ldxg = MatrixFreeSystem._cols(XG)[1] if XG is not None else 0
+        ldyg = MatrixFreeSystem._cols(YG)[1] if YG is not None else 0
         check(capi.load().l3k_bnd_apply(self._h, which, _ptr(X), ldx, _ptr(XG), ldxg, _ptr(Y), ldy, _ptr(YG), ldyg, nc,
                                         alpha))
         return Y
@@ -651,8 +659,9 @@ class MatrixFreeSystem:
         """beta must be the value scale() was called with (see l3k_mf_scale in include/l3k.h)."""
         nc, ldx = self._cols(X)
         _, ldy = self._cols(Y)
-        ldxg = XG.shape[1] if XG is not None else 0
-        ldyg = YG.shape[1] if YG is not None else 0
+        # (the stride between the columns, not the number of ghost rows: the ghost rows may be a view behind the owned rows)
+        ldxg = self._cols(XG)[1] if XG is not None else 0
+        ldyg = self._cols(YG)[1] if YG is not None else 0
         check(capi.load().l3k_mf_apply_elems(self._h, which, _ptr(X), ldx, _ptr(XG), ldxg, _ptr(Y), ldy, _ptr(YG), ldyg,
                                              nc, alpha, beta))
 
