@@ -27,6 +27,29 @@ def oracle_mesh(part, nq, dofs_per_node, field_inds, dirichlet=None, fields=None
                       dirichlet, fields)
 
 
+def csr_graph(part, dofs_per_node, field_inds, drop=None):
+    """CSR graph of the rank-local matrix over all local dofs (n = n_local_nodes * dofs_per_node rows): the dofs
+    node * dofs_per_node + field_inds[u] of every element coupled with each other (what the reference's sparsity graph holds for
+    one domain kernel; the rows of dofs outside field_inds are empty), columns ascending -- built on the host like the caller's
+    Tpetra graph would be.  `drop(rows, cols)` gets the entries in CSR order (int64 arrays) and returns a boolean array: the
+    entries to leave out of the graph.  Returns (row_ptr int64, col_ind int32, n)."""
+    import scipy.sparse as sp
+    dofs = (part.elem_nodes.astype(np.int64)[:, :, None] * dofs_per_node + np.asarray(field_inds, dtype=np.int64)[None, None, :]).reshape(part.n_elems, -1)
+    nd = dofs.shape[1]
+    rows = np.repeat(dofs, nd, axis=1).ravel()
+    cols = np.tile(dofs, (1, nd)).ravel()
+    n = part.n_local_nodes * dofs_per_node
+    G = sp.coo_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n)).tocsr()
+    G.sort_indices()
+    row_ptr, col_ind = G.indptr.astype(np.int64), G.indices.astype(np.int32)
+    if drop is not None:
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(row_ptr))
+        keep = ~np.asarray(drop(rows, col_ind.astype(np.int64)), dtype=bool)
+        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=n))]).astype(np.int64)
+        col_ind = col_ind[keep]
+    return row_ptr, col_ind, n
+
+
 def rel_err(a, b):
     return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from helpers import HEX, SingleElementMesh
+from helpers import HEX, SingleElementMesh, csr_graph
 from l3ster_amd import system
 
 torch = pytest.importorskip("torch")
@@ -262,20 +262,6 @@ def test_config3_stored_row_major_order6_vs_oracle_and_rate(ctx):
     assert rate > 60_000, rate
 
 
-def _csr_graph(part, dpn, field_inds):
-    """CSR graph of the rank-local matrix: row / column dofs of every element coupled (what the reference's sparsity graph
-    holds for one domain kernel), columns ascending -- built on the host like the caller's Tpetra graph would be."""
-    import scipy.sparse as sp
-    dofs = (part.elem_nodes.astype(np.int64)[:, :, None] * dpn + np.asarray(field_inds)[None, None, :]).reshape(part.n_elems, -1)
-    nd = dofs.shape[1]
-    rows = np.repeat(dofs, nd, axis=1).ravel()
-    cols = np.tile(dofs, (1, nd)).ravel()
-    n = part.n_local_nodes * dpn
-    G = sp.coo_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n)).tocsr()
-    G.sort_indices()
-    return G.indptr.astype(np.int64), G.indices.astype(np.int32), n
-
-
 @pytest.mark.parametrize("mode", ["node_rows", "per_entry", "global"])
 @pytest.mark.parametrize("kid,p,vo,R,kpar", [(system.KERNEL_DIFFUSION3D, 2, 1, 2, [0.7, 1.3]), (system.KERNEL_MASS3D, 3, 2, 1, None),
                                              (system.KERNEL_DIFFUSION3D, 4, 1, 1, [1.0, 1.0])])
@@ -298,7 +284,7 @@ def test_assembled_scatter_vs_oracle_dense(ctx, kid, p, vo, R, kpar, mode, reque
     mask = part.dirichlet_mask(U) if U == 4 else None
     mesh = system.DeviceMesh(ctx, part, U, mask)
     mf = system.MatrixFreeSystem(mesh, kid, kpar, asm_opts=(vo, 0, 0), n_rhs=R)
-    row_ptr, col_ind, n = _csr_graph(part, U, np.arange(U))
+    row_ptr, col_ind, n = csr_graph(part, U, np.arange(U))
     RP, CI = torch.as_tensor(row_ptr, device="cuda"), torch.as_tensor(col_ind, device="cuda")
 
     def assemble(skip):
