@@ -365,6 +365,76 @@ int l3k_mf_energy_end(l3k_mf* mf, const double* d_x, int* fused);
 int l3k_cg_update_z(l3k_ctx* ctx, double* d_z, const double* d_ap, const double* d_minv, int64_t n, double* d_s);
 int l3k_cg_update_px(l3k_ctx* ctx, double* d_p, double* d_x, const double* d_z, int64_t n, double* d_s);
 
+/* ---- Chebyshev-Jacobi preconditioner, matrix-free -------------------------------------------------------------------
+ * Ifpack2ChebyshevPreconditioner (solve/Ifpack2Preconditioners.hpp:26-36,107-131: degree, cond_est, max_power_iters,
+ * boost_factor; its diag_threshold is the threshold of l3k_jacobi_inverse).  The reference builds it from an assembled CRS
+ * matrix; its arithmetic needs y <- A x and diag(A) only, so here it sits on the matrix-free apply.  Ifpack2 is not part of
+ * the reference tree: the arithmetic is the textbook Chebyshev iteration with Jacobi scaling.  With
+ *     theta = (lambda_max + lambda_min) / 2, delta = (lambda_max - lambda_min) / 2, sigma = theta / delta, rho_0 = 1 / sigma,
+ * z <- p(D^-1 A) D^-1 r is
+ *     w = D^-1 r / theta, z = w
+ *     k = 1 .. degree - 1:  rho' = 1 / (2 sigma - rho);  w = rho' rho w + (2 rho' / delta) D^-1 (r - A z);  z += w;  rho = rho'
+ * (degree 1 is Jacobi scaled by 1 / theta; degree d costs d - 1 applies).  The coefficients are computed on the host once, in
+ * l3k_cheb_create.  Rows with minv == 0 are frozen as in l3k_pcg_solve: w = z = 0 is stored there (not 0 * something: a
+ * non-finite A z cannot reach them), they are zero in the power-iteration vectors and left out of <r, r>; x keeps its value.
+ *
+ * lambda_max: opts->lambda_max if > 0 (Ifpack2's "chebyshev: max eigenvalue"; no power iteration, no boost), else boost_factor
+ * times the estimate of max_power_iters (>= 1) steps of the power method on D^-1 A, run inside l3k_cheb_create:
+ *     start   v_i = h(i) * 2^-31 - 1 in [-1, 1) on rows with minv != 0, else 0, where for the row index i
+ *             h = (uint32) i;  h ^= h >> 16;  h *= 0x7feb352d;  h ^= h >> 15;  h *= 0x846ca68b;  h ^= h >> 16   (mod 2^32)
+ *             x = v * (1 / sqrt(<v, v>))
+ *     step    y = D^-1 (A x);  lambda = <x, y>;  x = y * (1 / sqrt(<y, y>))     (the estimate is the lambda of the last step)
+ * The dot products are the fixed-order two-stage reductions of the PCG: two creations give the same estimate bit for bit (on a
+ * context in deterministic mode, where the apply is reproducible too).  The estimate is read back once, at the end of creation;
+ * an estimate that is not finite and positive is an error (the operator or the diagonal is unusable).  lambda_min =
+ * lambda_max / cond_est.
+ *
+ * l3k_cheb_create: d_minv (required) is the output of l3k_jacobi_inverse; the object keeps the pointer, the caller keeps the array
+ * (and mf) alive.  opts == NULL: {1, 30., 10, 1.1, 0.}.  Single-rank systems only, like l3k_pcg_solve.  Errors (-1): null
+ * arguments, degree < 1, cond_est <= 1, boost_factor < 1, max_power_iters < 1 without lambda_max, a mesh with ghost nodes, an
+ * unusable estimate.
+ * l3k_pcg_solve_cheb: Hestenes-Stiefel PCG that keeps r itself (M^-1 is not diagonal: r cannot be recovered from z); options,
+ * residual scalings, check_every and the result as l3k_pcg_solve; <p, Ap> from l3k_mf_apply_energy; one allocation per solve
+ * (r, z, p, Ap, w, s[8]).  An iteration is 1 + (degree - 1) applies and 14 + 7 (degree - 1) vector passes (reads + writes of a
+ * vector): cgUpdateRXKernel 7 (x, r, p, Ap, minv in; x, r out), chebFirstKernel 4 (r, minv in; w, z out), every chebStepKernel 7
+ * (r, Az, minv, w, z in; w, z out), cgUpdatePKernel 3 (z, p in; p out) -- against the 9 of an iteration of l3k_pcg_solve.     */
+typedef struct l3k_cheb l3k_cheb;
+typedef struct
+{
+    int    degree;          /* >= 1; degree d costs d - 1 applies per application              */
+    double cond_est;        /* lambda_min = lambda_max / cond_est            (default 30)      */
+    int    max_power_iters; /* power iterations on D^-1 A for lambda_max     (default 10)      */
+    double boost_factor;    /* lambda_max = boost_factor * estimate          (default 1.1)     */
+    double lambda_max;      /* > 0: take this value, run no power iteration                    */
+} l3k_cheb_opts;
+typedef struct
+{
+    double lambda_max, lambda_min, lambda_est; /* lambda_est: the power method's estimate (= lambda_max where that was given) */
+    int    degree, power_iters, applies_per_call;
+} l3k_cheb_info;
+int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
+int l3k_cheb_info_get(const l3k_cheb* c, l3k_cheb_info* out);
+/* z <- p(D^-1 A) D^-1 r.  r and z must not overlap (z is written before r is read for the last time); z is a vector of
+ * l3k_mf_apply and is aligned as that call asks (it refuses a misaligned one), r is read 8 bytes at a time. */
+int l3k_cheb_apply(l3k_cheb* c, const double* d_r, double* d_z);
+int l3k_cheb_destroy(l3k_cheb* c);
+int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result);
+/* The pieces for hosts that iterate partitioned vectors themselves (explicit coefficients; the applies in between and the
+ * all-reduces of the scalar block s[8], slots as above, are the caller's; d_minv may be NULL = no frozen rows, 1 in the products):
+ *   l3k_cheb_first:   w = z = c0 minv r                                  (c0 = 1 / theta)
+ *   l3k_cheb_step:    w = a w + b minv (r - Az); z += w                  (a = rho' rho, b = 2 rho' / delta; d_az holds A z)
+ *                     both: d_s != NULL: s[2] = <r, z> (this rank's share) -- pass it on the last step of an application,
+ *                     NULL on the others
+ *   l3k_cg_update_rx: alpha = s[0]/s[1]; x += alpha p; r -= alpha Ap (frozen rows: r = 0, x untouched); s[3] = <r, r>
+ *   l3k_cg_update_p:  beta = s[2]/s[0]; p = z + beta p; then s[0] <- s[2]
+ * Slots written: cheb_first and cheb_step 2 (none with d_s == NULL); update_rx 3; update_p 0.  No call writes any other slot. */
+int l3k_cheb_first(l3k_ctx* ctx, const double* d_r, const double* d_minv, double c0, double* d_w, double* d_z, int64_t n, double* d_s);
+int l3k_cheb_step(l3k_ctx* ctx, const double* d_r, const double* d_az, const double* d_minv, double a, double b, double* d_w,
+                  double* d_z, int64_t n, double* d_s);
+int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, const double* d_ap, const double* d_minv, int64_t n,
+                     double* d_s);
+int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, double* d_s);
+
 /* ---- LocalAssembly --------------------------------------------------------------------------------------------------
  * assembleLocalSystem for a batch of elements, algsys/AssembleLocalSystem.hpp:234-256: K_e row-major [Nd][Nd],
  * F_e column-major [Nd][n_rhs] per element, elements [first, first+count).  d_K may be NULL (then only the checksum

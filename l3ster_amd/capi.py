@@ -34,6 +34,17 @@ class CgResult(C.Structure):
     _fields_ = [("achieved_tol", C.c_double), ("iterations", C.c_int), ("converged", C.c_int)]
 
 
+class ChebOpts(C.Structure):
+    """l3k_cheb_opts (Ifpack2ChebyshevPreconditioner::Options, solve/Ifpack2Preconditioners.hpp:107-118)"""
+    _fields_ = [("degree", C.c_int), ("cond_est", C.c_double), ("max_power_iters", C.c_int), ("boost_factor", C.c_double),
+                ("lambda_max", C.c_double)]
+
+
+class ChebInfo(C.Structure):
+    _fields_ = [("lambda_max", C.c_double), ("lambda_min", C.c_double), ("lambda_est", C.c_double), ("degree", C.c_int),
+                ("power_iters", C.c_int), ("applies_per_call", C.c_int)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -175,6 +186,15 @@ SIGNATURES = {
     "l3k_mf_energy_end": (C.c_int, [_vp, _vp, c_int_p]),
     "l3k_cg_update_z": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_px": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "l3k_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
+    "l3k_cheb_info_get": (C.c_int, [_vp, C.POINTER(ChebInfo)]),
+    "l3k_cheb_apply": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_cheb_destroy": (C.c_int, [_vp]),
+    "l3k_pcg_solve_cheb": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_cheb_first": (C.c_int, [_vp, _vp, _vp, C.c_double, _vp, _vp, C.c_int64, _vp]),
+    "l3k_cheb_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, C.c_int64, _vp]),
+    "l3k_cg_update_rx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "l3k_cg_update_p": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

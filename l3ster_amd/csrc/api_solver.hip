@@ -1,6 +1,8 @@
 // api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the single-rank driver.
 #include "objects.hpp"
 
+#include "host/chebyshev.hpp"
+
 namespace
 {
 // ---- fused vector kernels of the Jacobi-PCG iteration (solve/BelosSolvers.hpp:116-122 "Block CG" with one column +
@@ -134,6 +136,162 @@ inline int cgGrid(int64_t n)
 {
     const int64_t g = (n + cg_threads - 1) / cg_threads;
     return int(g < 1 ? 1 : (g > cg_blocks ? cg_blocks : g));
+}
+// ---- Chebyshev-Jacobi preconditioner (solve/Ifpack2Preconditioners.hpp:26-36,107-131; include/l3k.h: l3k_cheb_create) and the
+// vector kernels of the PCG that keeps r itself.  A row is live where minv != 0, tested on the BITS of minv: the library is built
+// with -ffinite-math-only and without signed zeros, under which m != 0. ? m * e : 0. may be folded to m * e -- and a non-finite e
+// (A z on a frozen row) would get through.  Frozen rows are stored as 0.
+__device__ __forceinline__ bool liveRow(double m)
+{
+    return (__double_as_longlong(m) & 0x7fffffffffffffffLL) != 0;
+}
+template < int n_rows >
+__device__ __forceinline__ void storePartials(const double (&acc)[n_rows], double* __restrict__ sh, double* __restrict__ partial)
+{
+    for (int k = 0; k < n_rows; ++k)
+    {
+        if (k)
+            __syncthreads();
+        const double t = blockSum(acc[k], sh);
+        if (threadIdx.x == 0)
+            partial[k * gridDim.x + blockIdx.x] = t;
+    }
+}
+// w = z = c0 minv r (2 reads, 2 writes); with_dot: partial <r, z> (a polynomial of degree 1 ends here)
+template < bool with_dot >
+__global__ __launch_bounds__(cg_threads) void chebFirstKernel(const double* __restrict__ r, const double* __restrict__ minv, double c0,
+                                                              double* __restrict__ w, double* __restrict__ z, int64_t n,
+                                                              double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            acc[1] = {0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
+        const double ri = __builtin_nontemporal_load(r + i);
+        const double wi = liveRow(m) ? c0 * (m * ri) : 0.;
+        __builtin_nontemporal_store(wi, w + i);
+        __builtin_nontemporal_store(wi, z + i);
+        if constexpr (with_dot)
+            acc[0] += liveRow(m) ? ri * wi : 0.;
+    }
+    if constexpr (with_dot)
+        storePartials(acc, sh, partial);
+}
+// w = a w + b minv (r - Az); z += w (5 reads, 2 writes: the 7 vector passes of an inner apply); with_dot: the last step of an
+// application also leaves the partials of <r, z>, so the outer iteration has no pass of its own for that dot product
+template < bool with_dot >
+__global__ __launch_bounds__(cg_threads) void chebStepKernel(const double* __restrict__ r, const double* __restrict__ az,
+                                                             const double* __restrict__ minv, double a, double b, double* __restrict__ w,
+                                                             double* __restrict__ z, int64_t n, double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            acc[1] = {0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        const double m    = minv ? __builtin_nontemporal_load(minv + i) : 1.;
+        const double ri   = __builtin_nontemporal_load(r + i);
+        const double wn   = a * __builtin_nontemporal_load(w + i) + b * (m * (ri - __builtin_nontemporal_load(az + i)));
+        const double zn   = __builtin_nontemporal_load(z + i) + wn;
+        const bool   live = liveRow(m);
+        __builtin_nontemporal_store(live ? wn : 0., w + i);
+        __builtin_nontemporal_store(live ? zn : 0., z + i);
+        if constexpr (with_dot)
+            acc[0] += live ? ri * zn : 0.;
+    }
+    if constexpr (with_dot)
+        storePartials(acc, sh, partial);
+}
+// r = b - A x0 on the live rows (r holds A x0 on entry), 0 on the frozen ones; partial <r, r>
+__global__ __launch_bounds__(cg_threads) void cgInitRKernel(double* __restrict__ r, const double* __restrict__ b,
+                                                            const double* __restrict__ minv, int64_t n, double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            acc[1] = {0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
+        const double d  = __builtin_nontemporal_load(b + i) - __builtin_nontemporal_load(r + i);
+        const double ri = liveRow(m) ? d : 0.;
+        __builtin_nontemporal_store(ri, r + i);
+        acc[0] += ri * ri;
+    }
+    storePartials(acc, sh, partial);
+}
+// alpha = s[0]/s[1]; x += alpha p; r -= alpha Ap; partial <r, r> over the live rows (frozen rows: r = 0, x is not written).
+// Reads x, r, p, Ap and the mask minv, writes x, r
+__global__ __launch_bounds__(cg_threads) void cgUpdateRXKernel(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+                                                               const double* __restrict__ ap, const double* __restrict__ minv, int64_t n,
+                                                               const double* __restrict__ s, double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    const double      alpha  = s[0] / s[1];
+    double            acc[1] = {0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
+        const double xn = __builtin_nontemporal_load(x + i) + alpha * __builtin_nontemporal_load(p + i);
+        const double rn = __builtin_nontemporal_load(r + i) - alpha * __builtin_nontemporal_load(ap + i);
+        const double ri = liveRow(m) ? rn : 0.;
+        if (liveRow(m))
+            __builtin_nontemporal_store(xn, x + i);
+        __builtin_nontemporal_store(ri, r + i);
+        acc[0] += ri * ri;
+    }
+    storePartials(acc, sh, partial);
+}
+// beta = s[2]/s[0]; p = z + beta p (the shift s[0] <- s[2] follows in cgFinishKernel, after every block has read beta)
+__global__ __launch_bounds__(cg_threads) void cgUpdatePKernel(double* __restrict__ p, const double* __restrict__ z, int64_t n,
+                                                              const double* __restrict__ s)
+{
+    const double beta = s[2] / s[0];
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+        __builtin_nontemporal_store(__builtin_nontemporal_load(z + i) + beta * __builtin_nontemporal_load(p + i), p + i);
+}
+// power method on D^-1 A.  Start vector (include/l3k.h): y_i = h(i) * 2^-31 - 1 on the live rows; partial <y, y>
+__global__ __launch_bounds__(cg_threads) void powerStartKernel(double* __restrict__ y, const double* __restrict__ minv, int64_t n,
+                                                               double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            acc[1] = {0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        uint32_t h = uint32_t(uint64_t(i));
+        h ^= h >> 16;
+        h *= 0x7feb352du;
+        h ^= h >> 15;
+        h *= 0x846ca68bu;
+        h ^= h >> 16;
+        const double yi = liveRow(__builtin_nontemporal_load(minv + i)) ? double(h) * 0x1p-31 - 1. : 0.;
+        __builtin_nontemporal_store(yi, y + i);
+        acc[0] += yi * yi;
+    }
+    storePartials(acc, sh, partial);
+}
+// y = minv (A x) in place (y holds A x on entry); partials <x, y>, <y, y>
+__global__ __launch_bounds__(cg_threads) void powerStepKernel(double* __restrict__ y, const double* __restrict__ minv,
+                                                              const double* __restrict__ x, int64_t n, double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            acc[2] = {0., 0.};
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    {
+        const double m  = __builtin_nontemporal_load(minv + i);
+        const double yn = m * __builtin_nontemporal_load(y + i);
+        const double yi = liveRow(m) ? yn : 0.;
+        __builtin_nontemporal_store(yi, y + i);
+        acc[0] += __builtin_nontemporal_load(x + i) * yi;
+        acc[1] += yi * yi;
+    }
+    storePartials(acc, sh, partial);
+}
+// ... followed by the rescale x = y * s^-1/2 with s = <y, y> read from the device block
+__global__ __launch_bounds__(cg_threads) void powerScaleKernel(double* __restrict__ x, const double* __restrict__ y, int64_t n,
+                                                               const double* __restrict__ s)
+{
+    const double f = 1. / sqrt(s[1]);
+    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+        __builtin_nontemporal_store(__builtin_nontemporal_load(y + i) * f, x + i);
 }
 } // namespace
 
@@ -309,6 +467,290 @@ int l3k_pcg_solve_cols(l3k_mf* mf, const double* d_b, size_t ldb, double* d_x, s
     for (int c = 0; c < ncols; ++c)
         if (int rc = l3k_pcg_solve(mf, d_b + ldb * c, d_x + ldx * c, d_minv, opts, results + c))
             return rc;
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------ Chebyshev-Jacobi
+} // extern "C"
+// the object behind l3k_cheb (include/l3k.h): coefficients, the caller's minv, and two vectors of its own -- x and y of the power
+// method during creation, w and A z of l3k_cheb_apply afterwards
+struct l3k_cheb
+{
+    l3k_mf*               mf;
+    const double*         minv;
+    l3k_cheb_info         info;
+    l3k::host::ChebCoeffs coef;
+    DevBuf< double >      work; // w | az | s[8]
+    int64_t               n, ld; // owned dofs; distance between the vectors (a multiple of 4: the applies want aligned columns)
+};
+namespace
+{
+template < typename Kernel, typename... Args >
+int launchWithDot(l3k_ctx* ctx, Kernel with_dot, Kernel without, int64_t n, double* d_s, int dst, Args... args)
+{
+    const int g = cgGrid(n);
+    hipLaunchKernelGGL(d_s ? with_dot : without, dim3(g), dim3(cg_threads), 0, ctx->stream, args..., n, ctx->red_ws);
+    if (d_s)
+        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, dst, -1, 0);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+// z <- p(D^-1 A) D^-1 r with the caller's w and az (n doubles each); d_s != nullptr: s[2] = <r, z> from the last kernel
+int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, double* d_s)
+{
+    l3k_ctx*     ctx = c->mf->ctx;
+    const int    d   = c->info.degree;
+    const size_t ld  = size_t(c->n);
+    if (int rc = l3k_cheb_first(ctx, r, c->minv, c->coef.c0, w, z, c->n, d == 1 ? d_s : nullptr))
+        return rc;
+    for (int k = 1; k < d; ++k)
+    {
+        if (int rc = l3k_mf_apply(c->mf, z, ld, az, ld, 1, 1., 0.))
+            return rc;
+        if (int rc = l3k_cheb_step(ctx, r, az, c->minv, c->coef.a[k - 1], c->coef.b[k - 1], w, z, c->n, k == d - 1 ? d_s : nullptr))
+            return rc;
+    }
+    return 0;
+}
+const char* const cheb_single_rank =
+    "%s serves single-rank systems; this mesh has ghost nodes: partitioned systems iterate with l3k_cheb_first / l3k_cheb_step / "
+    "l3k_cg_update_rx / l3k_cg_update_p and their own applies and all-reduces (pcg_distributed in l3ster_amd/solve.py)";
+} // namespace
+extern "C" {
+int l3k_cheb_first(l3k_ctx* ctx, const double* d_r, const double* d_minv, double c0, double* d_w, double* d_z, int64_t n, double* d_s)
+{
+    if (!ctx || !d_r || !d_w || !d_z)
+    {
+        setError("l3k_cheb_first: null argument");
+        return -1;
+    }
+    if (int rc = cgWorkspace(ctx))
+        return rc;
+    return launchWithDot(ctx, chebFirstKernel< true >, chebFirstKernel< false >, n, d_s, 2, d_r, d_minv, c0, d_w, d_z);
+}
+int l3k_cheb_step(l3k_ctx* ctx, const double* d_r, const double* d_az, const double* d_minv, double a, double b, double* d_w,
+                  double* d_z, int64_t n, double* d_s)
+{
+    if (!ctx || !d_r || !d_az || !d_w || !d_z)
+    {
+        setError("l3k_cheb_step: null argument");
+        return -1;
+    }
+    if (int rc = cgWorkspace(ctx))
+        return rc;
+    return launchWithDot(ctx, chebStepKernel< true >, chebStepKernel< false >, n, d_s, 2, d_r, d_az, d_minv, a, b, d_w, d_z);
+}
+int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, const double* d_ap, const double* d_minv, int64_t n,
+                     double* d_s)
+{
+    if (!ctx || !d_x || !d_r || !d_p || !d_ap || !d_s)
+    {
+        setError("l3k_cg_update_rx: null argument");
+        return -1;
+    }
+    if (int rc = cgWorkspace(ctx))
+        return rc;
+    const int g = cgGrid(n);
+    hipLaunchKernelGGL(cgUpdateRXKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_x, d_r, d_p, d_ap, d_minv, n, d_s, ctx->red_ws);
+    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, 3, -1, 0);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, double* d_s)
+{
+    if (!ctx || !d_p || !d_z || !d_s)
+    {
+        setError("l3k_cg_update_p: null argument");
+        return -1;
+    }
+    hipLaunchKernelGGL(cgUpdatePKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, ctx->stream, d_p, d_z, n, d_s);
+    // <r,z> of this iteration becomes the old one: after every block has read beta (as in l3k_cg_update_px)
+    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, 0, d_s, -1, -1, 1);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!mf || !d_minv || !out)
+    {
+        setError("l3k_cheb_create: null argument");
+        return -1;
+    }
+    if (mf->mesh->n_ghost_nodes != 0)
+    {
+        setError(cheb_single_rank, "l3k_cheb_create");
+        return -1;
+    }
+    const l3k_cheb_opts o = opts ? *opts : l3k_cheb_opts{1, 30., 10, 1.1, 0.};
+    if (const char* why = l3k::host::chebCheckOpts(o.degree, &o.cond_est, o.max_power_iters, &o.boost_factor, &o.lambda_max))
+    {
+        setError("l3k_cheb_create: %s", why);
+        return -1;
+    }
+    if (int rc = cgWorkspace(mf->ctx))
+        return rc;
+    auto c  = std::make_unique< l3k_cheb >();
+    c->mf   = mf;
+    c->minv = d_minv;
+    c->n    = mf->mesh->nOwnedDofs();
+    c->ld   = (c->n + 3) / 4 * 4;
+    if (int rc = c->work.alloc(size_t(2 * c->ld + 8)))
+        return rc;
+    l3k_ctx*      ctx = mf->ctx;
+    hipStream_t   st  = ctx->stream;
+    const int64_t n   = c->n;
+    const int     g   = cgGrid(n);
+    double *      x = c->work.ptr, *y = x + c->ld, *s = y + c->ld;
+    double        est   = o.lambda_max;
+    int           steps = 0;
+    if (!(o.lambda_max > 0.))
+    {
+        hipLaunchKernelGGL(powerStartKernel, dim3(g), dim3(cg_threads), 0, st, y, d_minv, n, ctx->red_ws);
+        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 1, -1, 0);
+        for (; steps < o.max_power_iters; ++steps)
+        {
+            hipLaunchKernelGGL(powerScaleKernel, dim3(g), dim3(cg_threads), 0, st, x, y, n, s);
+            L3K_HIP(hipGetLastError());
+            if (int rc = l3k_mf_apply(mf, x, size_t(n), y, size_t(n), 1, 1., 0.))
+                return rc;
+            hipLaunchKernelGGL(powerStepKernel, dim3(g), dim3(cg_threads), 0, st, y, d_minv, x, n, ctx->red_ws);
+            hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 0, 1, 0);
+        }
+        L3K_HIP(hipGetLastError());
+        L3K_HIP(hipMemcpyAsync(&est, s, sizeof est, hipMemcpyDeviceToHost, st)); // (the one readback of the creation)
+        L3K_HIP(hipStreamSynchronize(st));
+        if (!l3k::host::chebFinite(&est) || !(est > 0.))
+        {
+            setError("l3k_cheb_create: the power method on D^-1 A gave the eigenvalue estimate %g after %d steps; it must be finite and "
+                     "positive (is the operator positive definite, and minv its inverse diagonal with at least one non-zero row?)",
+                     est, steps);
+            return -1;
+        }
+    }
+    c->info.lambda_est       = est;
+    c->info.lambda_max       = o.lambda_max > 0. ? o.lambda_max : o.boost_factor * est;
+    c->info.lambda_min       = c->info.lambda_max / o.cond_est;
+    c->info.degree           = o.degree;
+    c->info.power_iters      = steps;
+    c->info.applies_per_call = o.degree - 1;
+    c->coef                  = l3k::host::chebCoeffs(c->info.lambda_max, c->info.lambda_min, o.degree);
+    *out                     = c.release();
+    return 0;
+}
+int l3k_cheb_info_get(const l3k_cheb* c, l3k_cheb_info* out)
+{
+    if (!c || !out)
+    {
+        setError("l3k_cheb_info_get: null argument");
+        return -1;
+    }
+    *out = c->info;
+    return 0;
+}
+int l3k_cheb_apply(l3k_cheb* c, const double* d_r, double* d_z)
+{
+    if (!c || !d_r || !d_z)
+    {
+        setError("l3k_cheb_apply: null argument");
+        return -1;
+    }
+    if (d_r < d_z + c->n && d_z < d_r + c->n) // (z is written before r is read for the last time)
+    {
+        setError("l3k_cheb_apply: r and z overlap");
+        return -1;
+    }
+    return chebApply(c, d_r, d_z, c->work.ptr, c->work.ptr + c->ld, nullptr);
+}
+int l3k_cheb_destroy(l3k_cheb* c)
+{
+    delete c;
+    return 0;
+}
+int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!mf || !d_b || !d_x || !c || !result)
+    {
+        setError("l3k_pcg_solve_cheb: null argument");
+        return -1;
+    }
+    if (mf->mesh->n_ghost_nodes != 0)
+    {
+        setError(cheb_single_rank, "l3k_pcg_solve_cheb");
+        return -1;
+    }
+    if (c->mf != mf)
+    {
+        setError("l3k_pcg_solve_cheb: the preconditioner was created for another system");
+        return -1;
+    }
+    const l3k_cg_opts o = opts ? *opts : l3k_cg_opts{1e-6, 10000, 0, 1};
+    l3k_ctx*          ctx = mf->ctx;
+    hipStream_t       st  = ctx->stream;
+    const int64_t     n = c->n, ld = c->ld;
+    DevBuf< double >  work; // r | z | p | ap (A z inside the preconditioner) | w | s[8]
+    if (int rc = work.alloc(size_t(5 * ld + 8)))
+        return rc;
+    double *r = work.ptr, *z = r + ld, *p = z + ld, *ap = p + ld, *w = ap + ld, *s = w + ld;
+    double  h[4];
+    const auto scalars = [&]() -> int {
+        L3K_HIP(hipMemcpyAsync(h, s, sizeof h, hipMemcpyDeviceToHost, st));
+        L3K_HIP(hipStreamSynchronize(st));
+        return 0;
+    };
+    // r = b - A x0 (0 on the frozen rows), s[3] = <r, r>
+    if (int rc = l3k_mf_apply(mf, d_x, size_t(n), r, size_t(n), 1, 1., 0.))
+        return rc;
+    const int g = cgGrid(n);
+    hipLaunchKernelGGL(cgInitRKernel, dim3(g), dim3(cg_threads), 0, st, r, d_b, c->minv, n, ctx->red_ws);
+    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 3, -1, 0);
+    L3K_HIP(hipGetLastError());
+    double scale = 1.;
+    if (o.residual_scaling == 2)
+    {
+        if (int rc = l3k_cg_dot_pap(ctx, d_b, d_b, n, s)) // s[1] = <b, b> (scratch use of the slot)
+            return rc;
+    }
+    if (int rc = scalars())
+        return rc;
+    const double rr0 = std::sqrt(h[3]);
+    if (o.residual_scaling == 1)
+        scale = rr0 > 0. ? rr0 : 1.;
+    else if (o.residual_scaling == 2)
+        scale = std::sqrt(h[1]) > 1e-300 ? std::sqrt(h[1]) : 1e-300;
+    double    res   = rr0 / scale;
+    int       it    = 0;
+    const int every = o.check_every > 0 ? o.check_every : 1;
+    if (res > o.tol && it < o.max_iters)
+    {
+        // z = M^-1 r, s[2] = <r, z>; p = z; s[0] <- s[2]
+        if (int rc = chebApply(c, r, z, w, ap, s))
+            return rc;
+        L3K_HIP(hipMemcpyAsync(p, z, size_t(n) * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, 0, s, -1, -1, 1);
+        L3K_HIP(hipGetLastError());
+    }
+    while (res > o.tol && it < o.max_iters)
+    {
+        if (int rc = l3k_mf_apply_energy(mf, p, ap, s)) // ap = A p, s[1] = <p, A p>
+            return rc;
+        if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, c->minv, n, s))
+            return rc;
+        ++it;
+        if (it % every == 0 || it == o.max_iters)
+        {
+            if (int rc = scalars())
+                return rc;
+            res = std::sqrt(h[3]) / scale;
+        }
+        if (res <= o.tol || it >= o.max_iters) // (x is final: no preconditioner application for a direction nobody takes)
+            break;
+        if (int rc = chebApply(c, r, z, w, ap, s)) // (ap is free until the next apply: it holds A z in here)
+            return rc;
+        if (int rc = l3k_cg_update_p(ctx, p, z, n, s))
+            return rc;
+    }
+    result->achieved_tol = res;
+    result->iterations   = it;
+    result->converged    = res <= o.tol;
     return 0;
 }
 } // extern "C"

@@ -24,11 +24,16 @@ class IterSolveResult:
         return f"IterSolveResult(tol={self.tol:.3e}, num_iters={self.num_iters}, converged={self.converged})"
 
 
-def cg(apply, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None, throw_on_fail=True):
+def cg(apply, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None, throw_on_fail=True,
+       precond=None):
     """Solves A x = b for one column (1-D tensors over the OWNED rows of this rank); x holds the initial guess and the
     result.  apply(p, out) computes out <- A p.  Options mirror IterSolverOpts (solve/SolverInterface.hpp:26-37):
     residual_scaling in {"none", "initial", "rhs"}.  `group`: torch.distributed group for the dot products of a
-    partitioned vector (None = single rank)."""
+    partitioned vector (None = single rank).  `precond`: a callable z = precond(r) in place of the diagonal minv (a
+    symmetric positive definite M^-1, e.g. chebyshev_reference behind a lambda)."""
+    if precond is not None and minv is not None:
+        raise ValueError("give minv or precond, not both")
+    prec = precond if precond is not None else (lambda r: r * minv) if minv is not None else None
 
     def dot(u, v):
         s = torch.dot(u, v)
@@ -41,7 +46,7 @@ def cg(apply, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="non
     r = b - r
     rr0 = dot(r, r) ** 0.5
     scale = {"none": 1.0, "initial": rr0 if rr0 > 0 else 1.0, "rhs": max(dot(b, b) ** 0.5, 1e-300)}[residual_scaling]
-    z = r * minv if minv is not None else r.clone()
+    z = prec(r) if prec is not None else r.clone()
     p = z.clone()
     rz = dot(r, z)
     ap = torch.empty_like(b)
@@ -56,7 +61,7 @@ def cg(apply, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="non
         it += 1
         if res <= tol:
             break
-        z = r * minv if minv is not None else r
+        z = prec(r) if prec is not None else r
         rz_new = dot(r, z)
         p.mul_(rz_new / rz).add_(z)
         rz = rz_new
@@ -64,6 +69,109 @@ def cg(apply, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="non
     if throw_on_fail and not converged:
         raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
     return IterSolveResult(res, it, converged)
+
+
+def chebyshev_coefficients(lambda_max, lambda_min, degree):
+    """c0 and the (a_k, b_k) of the recurrence below, in the arithmetic of the library's host routine
+    (csrc/host/chebyshev.hpp): the same doubles."""
+    theta, delta = (lambda_max + lambda_min) / 2.0, (lambda_max - lambda_min) / 2.0
+    sigma = theta / delta
+    rho, steps = 1.0 / sigma, []
+    for _ in range(1, degree):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        steps.append((rho_new * rho, 2.0 * rho_new / delta))
+        rho = rho_new
+    return 1.0 / theta, steps
+
+
+def chebyshev_reference(apply, minv, r, lambda_max, cond_est, degree):
+    """z = p(D^-1 A) D^-1 r in torch ops: the Chebyshev iteration with Jacobi scaling that Ifpack2ChebyshevPreconditioner
+    (solve/Ifpack2Preconditioners.hpp:26-36,107-131) stands for, as l3k_cheb_apply runs it (include/l3k.h): lambda_min =
+    lambda_max / cond_est, w = z = D^-1 r / theta, then degree - 1 steps w = a w + b D^-1 (r - A z), z += w.  Rows with
+    minv == 0 are frozen: w = z = 0.  apply(v, out) computes out <- A v."""
+    if degree < 1 or not cond_est > 1:
+        raise ValueError("degree >= 1 and cond_est > 1")
+    c0, steps = chebyshev_coefficients(lambda_max, lambda_max / cond_est, degree)
+    live, zero = minv != 0, torch.zeros_like(r)
+    w = torch.where(live, c0 * (minv * r), zero)
+    z = w.clone()
+    az = torch.empty_like(r)
+    for a, b in steps:
+        apply(z, az)
+        w = torch.where(live, a * w + b * (minv * (r - az)), zero)
+        z = torch.where(live, z + w, zero)
+    return z
+
+
+def power_start_vector(n, device="cpu"):
+    """The start vector of the power method in l3k_cheb_create before its normalisation (include/l3k.h): lowbias32 of the
+    row index mapped to [-1, 1), bit for bit (uint32 arithmetic carried in int64)."""
+    m32 = 0xFFFFFFFF
+    h = torch.arange(n, dtype=torch.int64, device=device) & m32
+    h = h ^ (h >> 16)
+    h = (h * 0x7FEB352D) & m32  # (int64 products wrap modulo 2^64: the low 32 bits are those of the uint32 product)
+    h = h ^ (h >> 15)
+    h = (h * 0x846CA68B) & m32
+    h = h ^ (h >> 16)
+    return h.to(torch.float64) * 2.0 ** -31 - 1.0
+
+
+def _overlap(u, v, n):
+    """Do the n doubles at u and at v share memory?"""
+    return abs(u.data_ptr() - v.data_ptr()) < 8 * n
+
+
+class ChebyshevPreconditioner:
+    """Handle of l3k_cheb_create: the matrix-free Chebyshev-Jacobi preconditioner of a single-rank MatrixFreeSystem
+    (options of Ifpack2ChebyshevOpts; its diag_threshold is jacobi_inverse's threshold).  `minv` (1-D device tensor
+    over the owned dofs) and the system are kept alive here.  lambda_max=None: estimated by max_power_iters steps of the
+    power method and multiplied by boost_factor."""
+
+    def __init__(self, system, minv, degree=1, cond_est=30., max_power_iters=10, boost_factor=1.1, lambda_max=None):
+        import ctypes as C
+        from . import capi
+        self.system, self.minv = system, minv
+        if minv is None or minv.numel() != system.mesh.n_owned_dofs or not minv.is_contiguous():
+            raise capi.L3KError("minv must be a contiguous tensor over the owned dofs of the system")
+        opts = capi.ChebOpts(int(degree), float(cond_est), int(max_power_iters), float(boost_factor),
+                             0.0 if lambda_max is None else float(lambda_max))
+        self._h = C.c_void_p()
+        capi.check(capi.load().l3k_cheb_create(system._h, C.c_void_p(minv.data_ptr()), C.byref(opts), C.byref(self._h)))
+
+    @property
+    def info(self):
+        """lambda_max, lambda_min, lambda_est, degree, power_iters, applies_per_call (l3k_cheb_info)"""
+        import ctypes as C
+        import types
+        from . import capi
+        i = capi.ChebInfo()
+        capi.check(capi.load().l3k_cheb_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.ChebInfo._fields_})
+
+    def apply(self, r, z):
+        """z <- p(D^-1 A) D^-1 r (l3k_cheb_apply); r, z: distinct 1-D device tensors over the owned dofs.  z goes through
+        l3k_mf_apply, which refuses a vector that is not aligned as the system's kernel needs it."""
+        import ctypes as C
+        from . import capi
+        n = self.system.mesh.n_owned_dofs
+        if r.numel() != n or z.numel() != n or not (r.is_contiguous() and z.is_contiguous()):
+            raise capi.L3KError("r and z must be contiguous tensors over the owned dofs of the system")
+        if _overlap(r, z, n):  # (the first kernel writes z before the steps read r: the result would be silently wrong)
+            raise capi.L3KError("r and z must be distinct vectors that do not overlap")
+        capi.check(capi.load().l3k_cheb_apply(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(z.data_ptr())))
+        return z
+
+    def close(self):
+        if getattr(self, "_h", None):
+            from . import capi
+            capi.load().l3k_cheb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
 
 
 def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
@@ -79,13 +187,36 @@ def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
 _SCALING = {"none": 0, "initial": 1, "rhs": 2}
 
 
-def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", check_every=1, throw_on_fail=True):
+def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", check_every=1, throw_on_fail=True,
+        precond=None):
     """Jacobi-PCG entirely behind the C ABI (l3k_pcg_solve): apply, fused vector updates and reductions run on the
     context's stream, the host only reads 32 bytes per convergence check.  Single rank; `system` is a
-    l3ster_amd.system.MatrixFreeSystem, b / x / minv 1-D device tensors over its owned dofs."""
+    l3ster_amd.system.MatrixFreeSystem, b / x / minv 1-D device tensors over its owned dofs.  `precond`: a
+    ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb; a multivector b then solves
+    its columns one after the other, as l3k_pcg_solve_cols does."""
     import ctypes as C
     from . import capi
     opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
+    if precond is not None:
+        if minv is not None:
+            raise capi.L3KError("give minv or precond (which carries its own minv), not both")
+        if precond.system is not system:
+            raise capi.L3KError("the preconditioner was created for another system")
+        n = system.mesh.n_owned_dofs
+        cols = [(b, x)] if b.dim() == 1 else list(zip(b, x))
+        if x.shape != b.shape or any(bc.stride(0) != 1 or xc.stride(0) != 1 or bc.numel() != n for bc, xc in cols):
+            raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")
+        if any(_overlap(bc, xc, n) for bc, xc in cols):
+            raise capi.L3KError("b and x must not share memory")
+        out = []
+        for bc, xc in cols:
+            res = capi.CgResult()
+            capi.check(capi.load().l3k_pcg_solve_cheb(system._h, C.c_void_p(bc.data_ptr()), C.c_void_p(xc.data_ptr()), precond._h,
+                                                      C.byref(opts), C.byref(res)))
+            out.append(IterSolveResult(res.achieved_tol, res.iterations, bool(res.converged)))
+        if throw_on_fail and not all(r.converged for r in out):
+            raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
+        return out[0] if b.dim() == 1 else out
     if b.dim() == 2:  # a multivector (ncols, ld) of right-hand sides: the columns one after the other (l3k_pcg_solve_cols)
         nc = b.shape[0]
         if x.shape != b.shape or b.stride(1) != 1 or x.stride(1) != 1:
@@ -107,10 +238,14 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
 
 
 def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None,
-                    throw_on_fail=True, allreduce=None, check_every=1):
+                    throw_on_fail=True, allreduce=None, check_every=1, precond=None):
     """The same iteration for a partitioned system: `op.apply(X, Y)` is a DistributedOperator over this rank's owned
     rows; the fused l3k_cg_* kernels keep the scalars in a device block that is all-reduced between them (two small
-    all-reduces per iteration, as Belos does)."""
+    all-reduces per iteration, as Belos does).  `precond`: the Chebyshev-Jacobi preconditioner over minv in place of
+    the diagonal one; the iteration is then _pcg_distributed_chebyshev's (see there)."""
+    if precond is not None:
+        return _pcg_distributed_chebyshev(op, ctx, b, x, minv, precond, tol, max_iters, residual_scaling, group, throw_on_fail,
+                                          allreduce, check_every)
     import ctypes as C
     from . import capi
     lib = capi.load()
@@ -164,3 +299,119 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
     if throw_on_fail and not converged:
         raise RuntimeError("Solver failed to converge")
     return IterSolveResult(res, it, converged)
+
+
+def _pcg_distributed_chebyshev(op, ctx, b, x, minv, precond, tol, max_iters, residual_scaling, group, throw_on_fail, allreduce,
+                               check_every):
+    """pcg_distributed with the Chebyshev-Jacobi preconditioner over minv (required): `precond` is a dict of
+    ChebyshevPreconditioner's options (degree, cond_est, max_power_iters, boost_factor, lambda_max) or an object whose
+    .info has lambda_max, lambda_min and degree (a ChebyshevPreconditioner's numbers on another operator).  The
+    iteration is that of l3k_pcg_solve_cheb with the exported pieces (l3k_cheb_first / _step, l3k_cg_update_rx /
+    _update_p): the inner applies go through op.apply and need no reduction, the outer scalars and -- without
+    lambda_max -- <x, y> and <y, y> of the power method go through the same reduction hook.  The power method starts
+    from power_start_vector over this rank's rows."""
+    import ctypes as C
+    import inspect
+    from . import capi
+    lib = capi.load()
+    if minv is None:
+        raise capi.L3KError("pcg_distributed(precond=...) needs minv: the preconditioner is a polynomial in D^-1 A")
+    n = b.numel()
+    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    s = torch.zeros(8, dtype=torch.float64, device=b.device)
+    r, z, p, ap, w = (torch.empty_like(b) for _ in range(5))
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    fuse_energy = "energy" in inspect.signature(op.apply).parameters
+
+    def reduce(view):
+        if allreduce is not None:
+            allreduce(view)
+        elif multi:
+            dist.all_reduce(view, op=dist.ReduceOp.SUM, group=group)
+
+    c0, steps = _distributed_chebyshev(precond, op, minv, reduce)
+
+    def cheb():  # z = M^-1 r, reduced s[2] = <r, z> (the last kernel of the application leaves the local sum)
+        capi.check(lib.l3k_cheb_first(ctx._h, vp(r), vp(minv), c0, vp(w), vp(z), n, vp(None if steps else s)))
+        for k, (ca, cb) in enumerate(steps):
+            op.apply(z[None, :], ap[None, :])  # (ap is free here: it holds A z)
+            capi.check(lib.l3k_cheb_step(ctx._h, vp(r), vp(ap), vp(minv), ca, cb, vp(w), vp(z), n,
+                                         vp(s if k == len(steps) - 1 else None)))
+        reduce(s[2:3])
+
+    op.apply(x[None, :], r[None, :])
+    r.copy_(torch.where(minv != 0, b - r, torch.zeros_like(b)))  # (frozen rows: out of the residual from the start)
+    s[3] = torch.dot(r, r)
+    reduce(s[3:4])
+    bb = torch.dot(b, b).reshape(1)
+    reduce(bb)
+    rr0 = s[3].item() ** 0.5
+    scale = {"none": 1.0, "initial": rr0 if rr0 > 0 else 1.0, "rhs": max(bb.item() ** 0.5, 1e-300)}[residual_scaling]
+    res, it = rr0 / scale, 0
+    if res > tol and it < max_iters:
+        cheb()
+        p.copy_(z)
+        s[0] = s[2]
+    while res > tol and it < max_iters:
+        if fuse_energy:  # as in pcg_distributed: every rank takes the same route to <p, A p>, decided at the first apply
+            op.apply(p[None, :], ap[None, :], energy=s)
+            if it == 0:
+                n_not = torch.tensor([0.0 if op.energy_fused else 1.0], dtype=torch.float64, device=b.device)
+                reduce(n_not)
+                fuse_energy = n_not.item() == 0.0
+            elif not op.energy_fused:
+                raise RuntimeError("the element kernels stopped accumulating <p, A p>")
+        else:
+            op.apply(p[None, :], ap[None, :])
+        if not fuse_energy:
+            capi.check(lib.l3k_cg_dot_pap(ctx._h, vp(p), vp(ap), n, vp(s)))
+        reduce(s[1:2])
+        capi.check(lib.l3k_cg_update_rx(ctx._h, vp(x), vp(r), vp(p), vp(ap), vp(minv), n, vp(s)))
+        reduce(s[3:4])
+        it += 1
+        if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
+            res = s[3].item() ** 0.5 / scale
+        if res <= tol or it >= max_iters:  # (x is final: no preconditioner application for a direction nobody takes)
+            break
+        cheb()
+        capi.check(lib.l3k_cg_update_p(ctx._h, vp(p), vp(z), n, vp(s)))
+    converged = res <= tol
+    if throw_on_fail and not converged:
+        raise RuntimeError("Solver failed to converge")
+    return IterSolveResult(res, it, converged)
+
+
+def _distributed_chebyshev(precond, op, minv, reduce):
+    """(c0, [(a_k, b_k)]) of pcg_distributed's preconditioner; runs the power method on D^-1 A through op.apply where no
+    lambda_max is given (<x, y> and <y, y> reduced across the ranks)."""
+    info = getattr(precond, "info", None)
+    if info is not None:
+        return chebyshev_coefficients(info.lambda_max, info.lambda_min, info.degree)
+    o = dict(degree=1, cond_est=30.0, max_power_iters=10, boost_factor=1.1, lambda_max=None)
+    unknown = set(precond) - set(o)
+    if unknown:
+        raise ValueError(f"unknown Chebyshev options {sorted(unknown)}")
+    o.update(precond)
+    if o["degree"] < 1 or not o["cond_est"] > 1 or not o["boost_factor"] >= 1:
+        raise ValueError("Chebyshev options: degree >= 1, cond_est > 1, boost_factor >= 1")
+    lam = o["lambda_max"]
+    if lam is None:
+        if o["max_power_iters"] < 1:
+            raise ValueError("max_power_iters < 1 and no lambda_max given")
+        live = minv != 0
+        y = torch.where(live, power_start_vector(minv.numel(), minv.device), torch.zeros_like(minv))
+        t = torch.zeros(2, dtype=torch.float64, device=minv.device)
+        t[1] = torch.dot(y, y)
+        reduce(t[1:2])
+        ax = torch.empty_like(minv)
+        for _ in range(o["max_power_iters"]):
+            xv = y * (1.0 / torch.sqrt(t[1]))
+            op.apply(xv[None, :], ax[None, :])
+            y = torch.where(live, minv * ax, torch.zeros_like(minv))
+            t[0], t[1] = torch.dot(xv, y), torch.dot(y, y)
+            reduce(t)
+        est = t[0].item()
+        if not (est > 0 and est < float("inf")):
+            raise RuntimeError(f"the power method on D^-1 A gave the eigenvalue estimate {est}: it must be finite and positive")
+        lam = o["boost_factor"] * est
+    return chebyshev_coefficients(lam, lam / o["cond_est"], o["degree"])
