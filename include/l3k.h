@@ -310,7 +310,7 @@ int l3k_update_solution(l3k_ctx* ctx, l3k_mesh* mesh, const double* d_x, size_t 
  *   l3k_pcg_solve      : single rank (no ghost nodes); x holds the initial guess and the result; d_minv may be NULL;
  *                        residual_scaling 0 none / 1 initial residual / 2 norm of b (IterSolverOpts,
  *                        solve/SolverInterface.hpp:26-37); check_every = iterations between convergence checks (each is
- *                        one 32-byte device-to-host copy)
+ *                        one 32-byte device-to-host copy).  opts == NULL: {1e-6, 10000, 0, 1}.
  *                        Rows with minv == 0 (a preconditioner zeroed on constrained dofs; damping 0) are frozen: x keeps
  *                        its initial value there and the row is left out of the residual norm (the iteration keeps
  *                        z = M^-1 r, from which r cannot be recovered where minv = 0)

@@ -21,24 +21,51 @@ __device__ __forceinline__ double blockSum(double v, double* sh)
     }
     return sh[0];
 }
+// the rows of a thread: firstRow(), firstRow() + rowStep(), ... < n
+__device__ __forceinline__ int64_t firstRow()
+{
+    return int64_t(blockIdx.x) * cg_threads + threadIdx.x;
+}
+__device__ __forceinline__ int64_t rowStep()
+{
+    return int64_t(gridDim.x) * cg_threads;
+}
+// A row is live where minv != 0, frozen otherwise.  For every double -- NaN and both zeros included -- liveRow(m) and m != 0.
+// agree; the test is on the BITS of minv because the library is built with -ffinite-math-only and without signed zeros, under
+// which m != 0. ? m * e : 0. may be folded to m * e -- and a non-finite e (A z on a frozen row) would get through.
+__device__ __forceinline__ bool liveRow(double m)
+{
+    return (__double_as_longlong(m) & 0x7fffffffffffffffLL) != 0;
+}
+// block sums of acc[0 .. n_rows) in a fixed order: partial[k * gridDim.x + blockIdx.x]
+template < int n_rows >
+__device__ __forceinline__ void storePartials(const double (&acc)[n_rows], double* __restrict__ sh, double* __restrict__ partial)
+{
+    for (int k = 0; k < n_rows; ++k)
+    {
+        if (k)
+            __syncthreads();
+        const double t = blockSum(acc[k], sh);
+        if (threadIdx.x == 0)
+            partial[k * gridDim.x + blockIdx.x] = t;
+    }
+}
 __global__ __launch_bounds__(cg_threads) void cgDotKernel(const double* __restrict__ u, const double* __restrict__ v, int64_t n,
                                                           double* __restrict__ partial)
 {
     __shared__ double sh[cg_threads];
-    double            acc = 0.;
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
-        acc += __builtin_nontemporal_load(u + i) * __builtin_nontemporal_load(v + i);
-    const double t = blockSum(acc, sh);
-    if (threadIdx.x == 0)
-        partial[blockIdx.x] = t;
+    double            acc[1] = {0.};
+    for (int64_t i = firstRow(); i < n; i += rowStep())
+        acc[0] += __builtin_nontemporal_load(u + i) * __builtin_nontemporal_load(v + i);
+    storePartials(acc, sh, partial);
 }
-// s[dst0] = sum partial[0][:], s[dst1] = sum partial[1][:] (dst1 < 0: one row; dst0 < 0: no row, no other slot is written);
-// shift != 0: then s[0] = s[2]
+// the finish stage of a reduction: s[dst0] = sum partial[0][:], s[dst1] = sum partial[1][:] (dst1 < 0: one row; no other slot is
+// written)
 __global__ __launch_bounds__(cg_threads) void cgFinishKernel(const double* __restrict__ partial, int n_blocks, double* __restrict__ s,
-                                                             int dst0, int dst1, int shift)
+                                                             int dst0, int dst1)
 {
     __shared__ double sh[cg_threads];
-    for (int row = 0; row < (dst0 < 0 ? 0 : dst1 >= 0 ? 2 : 1); ++row)
+    for (int row = 0; row < (dst1 >= 0 ? 2 : 1); ++row)
     {
         double acc = 0.;
         for (int i = threadIdx.x; i < n_blocks; i += cg_threads)
@@ -48,49 +75,45 @@ __global__ __launch_bounds__(cg_threads) void cgFinishKernel(const double* __res
         if (threadIdx.x == 0)
             s[row == 0 ? dst0 : dst1] = t;
     }
-    if (shift && threadIdx.x == 0)
-        s[0] = s[2];
+}
+// the shift: <r,z> of this iteration becomes the old one.  A launch of its own AFTER the vector kernel that divides by s[0]:
+// every block of that kernel must have read alpha and beta first
+__global__ void cgShiftKernel(double* __restrict__ s)
+{
+    s[0] = s[2];
 }
 // The iteration keeps the PRECONDITIONED residual z = M^-1 r instead of r (Jacobi: r = z / minv element-wise), and x moves in the
 // p pass: 9 vector passes per iteration instead of 11 (the vector kernels run at the HBM rate, so passes are what counts):
 //   z pass:  alpha = s[0]/s[1]; z -= alpha minv Ap; partial <r, z>, <r, r> with r = z / minv     reads z, Ap, minv; writes z
 //   p pass:  x += alpha p; beta = s[2]/s[0]; p = z + beta p                                       reads z, p, x;   writes p, x
-// (round 2: x += alpha p and r -= alpha Ap in one pass over x, r, p, Ap, minv, then p = minv r + beta p over r, minv, p.)
 // The same iterates in exact arithmetic; in floating point z is updated where r was (one rounding of minv * Ap more, one of
 // minv * r less).  Rows with minv == 0 (a preconditioner zeroed on constrained dofs, l3k_jacobi_inverse with damping 0) are FROZEN:
 // z = p = 0 there, x keeps its initial value, and -- since r cannot be recovered from z = 0 -- they are left out of <r, r>, i.e.
 // the convergence test runs over the rows the iteration can change (include/l3k.h: l3k_pcg_solve).
 __global__ __launch_bounds__(cg_threads) void cgUpdateZKernel(double* __restrict__ z, const double* __restrict__ ap,
-                                                              const double* __restrict__ minv, int64_t n,
-                                                              const double* __restrict__ s, double* __restrict__ partial)
+                                                              const double* __restrict__ minv, const double* __restrict__ s,
+                                                              int64_t n, double* __restrict__ partial)
 {
     __shared__ double sh[cg_threads];
-    const double      alpha = s[0] / s[1];
-    double            rz = 0., rr = 0.;
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    const double      alpha  = s[0] / s[1];
+    double            acc[2] = {0., 0.}; // <r, z>, <r, r>
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         // (every array is streamed once and is far larger than the caches: non-temporal loads and stores, +3-6 % of HBM rate)
         const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
         const double zi = __builtin_nontemporal_load(z + i) - alpha * (m * __builtin_nontemporal_load(ap + i));
-        const double ri = minv ? (m != 0. ? zi / m : 0.) : zi; // (0 / 0 on a frozen row would poison both sums)
+        const double ri = minv ? (liveRow(m) ? zi / m : 0.) : zi; // (0 / 0 on a frozen row would poison both sums)
         __builtin_nontemporal_store(zi, z + i);
-        rz += ri * zi;
-        rr += ri * ri;
+        acc[0] += ri * zi;
+        acc[1] += ri * ri;
     }
-    const double a = blockSum(rz, sh);
-    __syncthreads();
-    const double b = blockSum(rr, sh);
-    if (threadIdx.x == 0)
-    {
-        partial[blockIdx.x]             = a;
-        partial[gridDim.x + blockIdx.x] = b;
-    }
+    storePartials(acc, sh, partial);
 }
 __global__ __launch_bounds__(cg_threads) void cgUpdatePXKernel(double* __restrict__ p, double* __restrict__ x, const double* __restrict__ z,
                                                                int64_t n, const double* __restrict__ s)
 {
     const double alpha = s[0] / s[1], beta = s[2] / s[0];
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double pi = __builtin_nontemporal_load(p + i);
         __builtin_nontemporal_store(__builtin_nontemporal_load(x + i) + alpha * pi, x + i);
@@ -103,25 +126,18 @@ __global__ __launch_bounds__(cg_threads) void cgInitKernel(double* __restrict__ 
                                                            double* __restrict__ partial)
 {
     __shared__ double sh[cg_threads];
-    double            rz = 0., rr = 0.;
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    double            acc[2] = {0., 0.}; // <r, z>, <r, r>
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
-        const double m  = minv ? minv[i] : 1.;
-        const double ri = m != 0. ? __builtin_nontemporal_load(b + i) - __builtin_nontemporal_load(r + i) : 0.; // (frozen rows: out of the residual norm from the start, as in the z pass)
+        const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
+        const double ri = liveRow(m) ? __builtin_nontemporal_load(b + i) - __builtin_nontemporal_load(r + i) : 0.; // (frozen rows: out of the residual norm from the start, as in the z pass)
         const double zi = m * ri;
         __builtin_nontemporal_store(zi, r + i);
         __builtin_nontemporal_store(zi, p + i);
-        rz += ri * zi;
-        rr += ri * ri;
+        acc[0] += ri * zi;
+        acc[1] += ri * ri;
     }
-    const double a = blockSum(rz, sh);
-    __syncthreads();
-    const double c = blockSum(rr, sh);
-    if (threadIdx.x == 0)
-    {
-        partial[blockIdx.x]             = a;
-        partial[gridDim.x + blockIdx.x] = c;
-    }
+    storePartials(acc, sh, partial);
 }
 // NativeJacobiImpl::init (solve/NativePreconditioners.hpp:75-96): sign(d) * damping / max(|d|, threshold)
 __global__ void jacobiInverseKernel(const double* __restrict__ d, int64_t n, double damping, double threshold, double* __restrict__ out)
@@ -138,25 +154,7 @@ inline int cgGrid(int64_t n)
     return int(g < 1 ? 1 : (g > cg_blocks ? cg_blocks : g));
 }
 // ---- Chebyshev-Jacobi preconditioner (solve/Ifpack2Preconditioners.hpp:26-36,107-131; include/l3k.h: l3k_cheb_create) and the
-// vector kernels of the PCG that keeps r itself.  A row is live where minv != 0, tested on the BITS of minv: the library is built
-// with -ffinite-math-only and without signed zeros, under which m != 0. ? m * e : 0. may be folded to m * e -- and a non-finite e
-// (A z on a frozen row) would get through.  Frozen rows are stored as 0.
-__device__ __forceinline__ bool liveRow(double m)
-{
-    return (__double_as_longlong(m) & 0x7fffffffffffffffLL) != 0;
-}
-template < int n_rows >
-__device__ __forceinline__ void storePartials(const double (&acc)[n_rows], double* __restrict__ sh, double* __restrict__ partial)
-{
-    for (int k = 0; k < n_rows; ++k)
-    {
-        if (k)
-            __syncthreads();
-        const double t = blockSum(acc[k], sh);
-        if (threadIdx.x == 0)
-            partial[k * gridDim.x + blockIdx.x] = t;
-    }
-}
+// vector kernels of the PCG that keeps r itself.  Frozen rows (liveRow) are stored as 0.
 // w = z = c0 minv r (2 reads, 2 writes); with_dot: partial <r, z> (a polynomial of degree 1 ends here)
 template < bool with_dot >
 __global__ __launch_bounds__(cg_threads) void chebFirstKernel(const double* __restrict__ r, const double* __restrict__ minv, double c0,
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(cg_threads) void chebFirstKernel(const double* __re
 {
     __shared__ double sh[cg_threads];
     double            acc[1] = {0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
         const double ri = __builtin_nontemporal_load(r + i);
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(cg_threads) void chebStepKernel(const double* __res
 {
     __shared__ double sh[cg_threads];
     double            acc[1] = {0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double m    = minv ? __builtin_nontemporal_load(minv + i) : 1.;
         const double ri   = __builtin_nontemporal_load(r + i);
@@ -208,7 +206,7 @@ __global__ __launch_bounds__(cg_threads) void cgInitRKernel(double* __restrict__
 {
     __shared__ double sh[cg_threads];
     double            acc[1] = {0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
         const double d  = __builtin_nontemporal_load(b + i) - __builtin_nontemporal_load(r + i);
@@ -221,13 +219,13 @@ __global__ __launch_bounds__(cg_threads) void cgInitRKernel(double* __restrict__
 // alpha = s[0]/s[1]; x += alpha p; r -= alpha Ap; partial <r, r> over the live rows (frozen rows: r = 0, x is not written).
 // Reads x, r, p, Ap and the mask minv, writes x, r
 __global__ __launch_bounds__(cg_threads) void cgUpdateRXKernel(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
-                                                               const double* __restrict__ ap, const double* __restrict__ minv, int64_t n,
-                                                               const double* __restrict__ s, double* __restrict__ partial)
+                                                               const double* __restrict__ ap, const double* __restrict__ minv,
+                                                               const double* __restrict__ s, int64_t n, double* __restrict__ partial)
 {
     __shared__ double sh[cg_threads];
     const double      alpha  = s[0] / s[1];
     double            acc[1] = {0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double m  = minv ? __builtin_nontemporal_load(minv + i) : 1.;
         const double xn = __builtin_nontemporal_load(x + i) + alpha * __builtin_nontemporal_load(p + i);
@@ -240,12 +238,12 @@ __global__ __launch_bounds__(cg_threads) void cgUpdateRXKernel(double* __restric
     }
     storePartials(acc, sh, partial);
 }
-// beta = s[2]/s[0]; p = z + beta p (the shift s[0] <- s[2] follows in cgFinishKernel, after every block has read beta)
+// beta = s[2]/s[0]; p = z + beta p (the shift s[0] <- s[2] follows in cgShiftKernel, after every block has read beta)
 __global__ __launch_bounds__(cg_threads) void cgUpdatePKernel(double* __restrict__ p, const double* __restrict__ z, int64_t n,
                                                               const double* __restrict__ s)
 {
     const double beta = s[2] / s[0];
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
         __builtin_nontemporal_store(__builtin_nontemporal_load(z + i) + beta * __builtin_nontemporal_load(p + i), p + i);
 }
 // power method on D^-1 A.  Start vector (include/l3k.h): y_i = h(i) * 2^-31 - 1 on the live rows; partial <y, y>
@@ -254,7 +252,7 @@ __global__ __launch_bounds__(cg_threads) void powerStartKernel(double* __restric
 {
     __shared__ double sh[cg_threads];
     double            acc[1] = {0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         uint32_t h = uint32_t(uint64_t(i));
         h ^= h >> 16;
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(cg_threads) void powerStepKernel(double* __restrict
 {
     __shared__ double sh[cg_threads];
     double            acc[2] = {0., 0.};
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
     {
         const double m  = __builtin_nontemporal_load(minv + i);
         const double yn = m * __builtin_nontemporal_load(y + i);
@@ -290,15 +288,11 @@ __global__ __launch_bounds__(cg_threads) void powerScaleKernel(double* __restric
                                                                const double* __restrict__ s)
 {
     const double f = 1. / sqrt(s[1]);
-    for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
+    for (int64_t i = firstRow(); i < n; i += rowStep())
         __builtin_nontemporal_store(__builtin_nontemporal_load(y + i) * f, x + i);
 }
-} // namespace
-
-extern "C" {
-
-// ------------------------------------------------------------------------------------------------ Jacobi-PCG
-static int cgWorkspace(l3k_ctx* ctx)
+// ------------------------------------------------------------------------------------------------ launches
+int cgWorkspace(l3k_ctx* ctx)
 {
     if (!ctx->red_ws) // (allocated by l3k_ctx_create on the context's device)
     {
@@ -307,6 +301,105 @@ static int cgWorkspace(l3k_ctx* ctx)
     }
     return 0;
 }
+// the slots of s that the finish stage of a reduction writes (cgFinishKernel)
+struct Slots
+{
+    int dst0, dst1 = -1;
+};
+// One reducing pass over n rows: kernel(args..., n, partials), then the finish stage into s[to.dst0] (and s[to.dst1]).  d_s == nullptr:
+// the kernel alone (an instance that leaves no partials)
+template < typename... Params, typename... Args >
+int launchReduce(l3k_ctx* ctx, void (*kernel)(Params...), int64_t n, double* d_s, Slots to, Args... args)
+{
+    if (int rc = cgWorkspace(ctx))
+        return rc;
+    const int g = cgGrid(n);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(cg_threads), 0, ctx->stream, args..., n, ctx->red_ws);
+    if (d_s)
+        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, to.dst0, to.dst1);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+// s[0] <- s[2], enqueued behind the vector kernel that read s[0] (cgShiftKernel)
+int launchShift(l3k_ctx* ctx, double* d_s)
+{
+    hipLaunchKernelGGL(cgShiftKernel, dim3(1), dim3(1), 0, ctx->stream, d_s);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------ single-rank drivers
+// What l3k_pcg_solve and l3k_pcg_solve_cheb share around their loop bodies
+constexpr l3k_cg_opts cg_default_opts{1e-6, 10000, 0, 1}; // (opts == NULL, include/l3k.h)
+const char* const     pcg_single_rank =
+    "%s is the single-rank solver; partitioned systems iterate with the l3k_cg_* pieces and an all-reduce of the scalar block "
+    "between them (l3ster_amd/solve.py)";
+const char* const cheb_single_rank =
+    "%s serves single-rank systems; this mesh has ghost nodes: partitioned systems iterate with l3k_cheb_first / l3k_cheb_step / "
+    "l3k_cg_update_rx / l3k_cg_update_p and their own applies and all-reduces (pcg_distributed in l3ster_amd/solve.py)";
+int singleRankOnly(const l3k_mf* mf, const char* message, const char* who)
+{
+    if (mf->mesh->n_ghost_nodes != 0)
+    {
+        setError(message, who);
+        return -1;
+    }
+    return 0;
+}
+struct CgDriver
+{
+    l3k_cg_opts o;
+    l3k_ctx*    ctx;
+    double*     s; // the device block
+    double      h[4] = {}, scale = 1., res = 0.;
+    int         it = 0;
+
+    int readScalars() // (the 32 bytes of a convergence check)
+    {
+        L3K_HIP(hipMemcpyAsync(h, s, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        L3K_HIP(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+    // with s[3] = <r, r> of the initial residual on the stream: the residual scale and the first scaled residual
+    int start(const double* d_b, int64_t n)
+    {
+        if (o.residual_scaling == 2)
+            if (int rc = l3k_cg_dot_pap(ctx, d_b, d_b, n, s)) // s[1] = <b, b> (scratch use of the slot)
+                return rc;
+        if (int rc = readScalars())
+            return rc;
+        const double rr0 = std::sqrt(h[3]);
+        if (o.residual_scaling == 1)
+            scale = rr0 > 0. ? rr0 : 1.;
+        else if (o.residual_scaling == 2)
+            scale = std::sqrt(h[1]) > 1e-300 ? std::sqrt(h[1]) : 1e-300;
+        res = rr0 / scale;
+        return 0;
+    }
+    bool running() const { return res > o.tol && it < o.max_iters; }
+    // one more iteration is on the stream: <r, r> is read every check_every iterations and after the last one
+    int afterIteration()
+    {
+        ++it;
+        if (it % (o.check_every > 0 ? o.check_every : 1) == 0 || it == o.max_iters)
+        {
+            if (int rc = readScalars())
+                return rc;
+            res = std::sqrt(h[3]) / scale;
+        }
+        return 0;
+    }
+    void report(l3k_cg_result* result) const
+    {
+        result->achieved_tol = res;
+        result->iterations   = it;
+        result->converged    = res <= o.tol;
+    }
+};
+} // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ Jacobi-PCG
 int l3k_jacobi_inverse(l3k_ctx* ctx, const double* d_diag, int64_t n, double damping, double threshold, double* d_minv)
 {
     if (!ctx || (n > 0 && (!d_diag || !d_minv)))
@@ -326,13 +419,9 @@ int l3k_cg_init(l3k_ctx* ctx, double* d_r, const double* d_b, double* d_p, const
         setError("l3k_cg_init: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
+    if (int rc = launchReduce(ctx, cgInitKernel, n, d_s, {2, 3}, d_r, d_b, d_p, d_minv))
         return rc;
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgInitKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_r, d_b, d_p, d_minv, n, ctx->red_ws);
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, 2, 3, 1);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return launchShift(ctx, d_s); // (this rank's <r,z> is the old one of the first iteration)
 }
 int l3k_cg_dot_pap(l3k_ctx* ctx, const double* d_p, const double* d_ap, int64_t n, double* d_s)
 {
@@ -341,13 +430,7 @@ int l3k_cg_dot_pap(l3k_ctx* ctx, const double* d_p, const double* d_ap, int64_t 
         setError("l3k_cg_dot_pap: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
-        return rc;
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgDotKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_p, d_ap, n, ctx->red_ws);
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, 1, -1, 0);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return launchReduce(ctx, cgDotKernel, n, d_s, {1}, d_p, d_ap);
 }
 int l3k_cg_update_z(l3k_ctx* ctx, double* d_z, const double* d_ap, const double* d_minv, int64_t n, double* d_s)
 {
@@ -356,13 +439,7 @@ int l3k_cg_update_z(l3k_ctx* ctx, double* d_z, const double* d_ap, const double*
         setError("l3k_cg_update_z: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
-        return rc;
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgUpdateZKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_z, d_ap, d_minv, n, d_s, ctx->red_ws);
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, 2, 3, 0);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return launchReduce(ctx, cgUpdateZKernel, n, d_s, {2, 3}, d_z, d_ap, d_minv, d_s);
 }
 int l3k_cg_update_px(l3k_ctx* ctx, double* d_p, double* d_x, const double* d_z, int64_t n, double* d_s)
 {
@@ -371,12 +448,8 @@ int l3k_cg_update_px(l3k_ctx* ctx, double* d_p, double* d_x, const double* d_z, 
         setError("l3k_cg_update_px: null argument");
         return -1;
     }
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgUpdatePXKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_p, d_x, d_z, n, d_s);
-    // <r,z> of this iteration becomes the old one: after every block has read alpha and beta
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, 0, d_s, -1, -1, 1);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(cgUpdatePXKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, ctx->stream, d_p, d_x, d_z, n, d_s);
+    return launchShift(ctx, d_s);
 }
 int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts,
                   l3k_cg_result* result)
@@ -386,48 +459,23 @@ int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_mi
         setError("l3k_pcg_solve: null argument");
         return -1;
     }
-    if (mf->mesh->n_ghost_nodes != 0)
-    {
-        setError("l3k_pcg_solve is the single-rank solver; partitioned systems iterate with the l3k_cg_* pieces and an "
-                 "all-reduce of the scalar block between them (l3ster_amd/solve.py)");
-        return -1;
-    }
-    const l3k_cg_opts o = opts ? *opts : l3k_cg_opts{1e-6, 10000, 0, 1};
-    l3k_ctx*          ctx = mf->ctx;
-    hipStream_t       st  = ctx->stream;
-    const int64_t     n   = mf->mesh->nOwnedDofs();
-    DevBuf< double >  work; // z (the preconditioned residual, in the array named r) | p | ap | s[8]
-    work.n = size_t(3 * n + 8);
-    L3K_HIP(hipMalloc(reinterpret_cast< void** >(&work.ptr), work.n * sizeof(double)));
+    if (int rc = singleRankOnly(mf, pcg_single_rank, "l3k_pcg_solve"))
+        return rc;
+    l3k_ctx*         ctx = mf->ctx;
+    const int64_t    n   = mf->mesh->nOwnedDofs();
+    DevBuf< double > work; // z (the preconditioned residual, in the array named r) | p | ap | s[8]
+    if (int rc = work.alloc(size_t(3 * n + 8)))
+        return rc;
     double *r = work.ptr, *p = r + n, *ap = p + n, *s = ap + n;
-    double  h[4];
-    const auto scalars = [&]() -> int {
-        L3K_HIP(hipMemcpyAsync(h, s, sizeof h, hipMemcpyDeviceToHost, st));
-        L3K_HIP(hipStreamSynchronize(st));
-        return 0;
-    };
+    CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // z = M^-1 (b - A x0), p = z
     if (int rc = l3k_mf_apply(mf, d_x, size_t(n), r, size_t(n), 1, 1., 0.))
         return rc;
     if (int rc = l3k_cg_init(ctx, r, d_b, p, d_minv, n, s))
         return rc;
-    double scale = 1.;
-    if (o.residual_scaling == 2)
-    {
-        if (int rc = l3k_cg_dot_pap(ctx, d_b, d_b, n, s)) // s[1] = <b, b> (scratch use of the slot)
-            return rc;
-    }
-    if (int rc = scalars())
+    if (int rc = cg.start(d_b, n))
         return rc;
-    const double rr0 = std::sqrt(h[3]);
-    if (o.residual_scaling == 1)
-        scale = rr0 > 0. ? rr0 : 1.;
-    else if (o.residual_scaling == 2)
-        scale = std::sqrt(h[1]) > 1e-300 ? std::sqrt(h[1]) : 1e-300;
-    double res = rr0 / scale;
-    int    it  = 0;
-    const int every = o.check_every > 0 ? o.check_every : 1;
-    while (res > o.tol && it < o.max_iters)
+    while (cg.running())
     {
         if (int rc = l3k_mf_apply_energy(mf, p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
@@ -435,17 +483,10 @@ int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_mi
             return rc;
         if (int rc = l3k_cg_update_px(ctx, p, d_x, r, n, s))
             return rc;
-        ++it;
-        if (it % every == 0 || it == o.max_iters)
-        {
-            if (int rc = scalars())
-                return rc;
-            res = std::sqrt(h[3]) / scale;
-        }
+        if (int rc = cg.afterIteration())
+            return rc;
     }
-    result->achieved_tol = res;
-    result->iterations   = it;
-    result->converged    = res <= o.tol;
+    cg.report(result);
     return 0;
 }
 // the same for a multivector of right-hand sides (the reference's systems carry n_rhs columns: Belos "Block CG" with block size 1
@@ -484,16 +525,6 @@ struct l3k_cheb
 };
 namespace
 {
-template < typename Kernel, typename... Args >
-int launchWithDot(l3k_ctx* ctx, Kernel with_dot, Kernel without, int64_t n, double* d_s, int dst, Args... args)
-{
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(d_s ? with_dot : without, dim3(g), dim3(cg_threads), 0, ctx->stream, args..., n, ctx->red_ws);
-    if (d_s)
-        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, dst, -1, 0);
-    L3K_HIP(hipGetLastError());
-    return 0;
-}
 // z <- p(D^-1 A) D^-1 r with the caller's w and az (n doubles each); d_s != nullptr: s[2] = <r, z> from the last kernel
 int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, double* d_s)
 {
@@ -511,9 +542,6 @@ int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, do
     }
     return 0;
 }
-const char* const cheb_single_rank =
-    "%s serves single-rank systems; this mesh has ghost nodes: partitioned systems iterate with l3k_cheb_first / l3k_cheb_step / "
-    "l3k_cg_update_rx / l3k_cg_update_p and their own applies and all-reduces (pcg_distributed in l3ster_amd/solve.py)";
 } // namespace
 extern "C" {
 int l3k_cheb_first(l3k_ctx* ctx, const double* d_r, const double* d_minv, double c0, double* d_w, double* d_z, int64_t n, double* d_s)
@@ -523,9 +551,7 @@ int l3k_cheb_first(l3k_ctx* ctx, const double* d_r, const double* d_minv, double
         setError("l3k_cheb_first: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
-        return rc;
-    return launchWithDot(ctx, chebFirstKernel< true >, chebFirstKernel< false >, n, d_s, 2, d_r, d_minv, c0, d_w, d_z);
+    return launchReduce(ctx, d_s ? chebFirstKernel< true > : chebFirstKernel< false >, n, d_s, {2}, d_r, d_minv, c0, d_w, d_z);
 }
 int l3k_cheb_step(l3k_ctx* ctx, const double* d_r, const double* d_az, const double* d_minv, double a, double b, double* d_w,
                   double* d_z, int64_t n, double* d_s)
@@ -535,9 +561,8 @@ int l3k_cheb_step(l3k_ctx* ctx, const double* d_r, const double* d_az, const dou
         setError("l3k_cheb_step: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
-        return rc;
-    return launchWithDot(ctx, chebStepKernel< true >, chebStepKernel< false >, n, d_s, 2, d_r, d_az, d_minv, a, b, d_w, d_z);
+    return launchReduce(ctx, d_s ? chebStepKernel< true > : chebStepKernel< false >, n, d_s, {2}, d_r, d_az, d_minv, a, b, d_w,
+                        d_z);
 }
 int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, const double* d_ap, const double* d_minv, int64_t n,
                      double* d_s)
@@ -547,13 +572,7 @@ int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, 
         setError("l3k_cg_update_rx: null argument");
         return -1;
     }
-    if (int rc = cgWorkspace(ctx))
-        return rc;
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgUpdateRXKernel, dim3(g), dim3(cg_threads), 0, ctx->stream, d_x, d_r, d_p, d_ap, d_minv, n, d_s, ctx->red_ws);
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, 3, -1, 0);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return launchReduce(ctx, cgUpdateRXKernel, n, d_s, {3}, d_x, d_r, d_p, d_ap, d_minv, d_s);
 }
 int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, double* d_s)
 {
@@ -563,10 +582,7 @@ int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, dou
         return -1;
     }
     hipLaunchKernelGGL(cgUpdatePKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, ctx->stream, d_p, d_z, n, d_s);
-    // <r,z> of this iteration becomes the old one: after every block has read beta (as in l3k_cg_update_px)
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, 0, d_s, -1, -1, 1);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return launchShift(ctx, d_s); // (as in l3k_cg_update_px)
 }
 int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
 {
@@ -575,11 +591,8 @@ int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts,
         setError("l3k_cheb_create: null argument");
         return -1;
     }
-    if (mf->mesh->n_ghost_nodes != 0)
-    {
-        setError(cheb_single_rank, "l3k_cheb_create");
-        return -1;
-    }
+    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_cheb_create"))
+        return rc;
     const l3k_cheb_opts o = opts ? *opts : l3k_cheb_opts{1, 30., 10, 1.1, 0.};
     if (const char* why = l3k::host::chebCheckOpts(o.degree, &o.cond_est, o.max_power_iters, &o.boost_factor, &o.lambda_max))
     {
@@ -598,24 +611,22 @@ int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts,
     l3k_ctx*      ctx = mf->ctx;
     hipStream_t   st  = ctx->stream;
     const int64_t n   = c->n;
-    const int     g   = cgGrid(n);
     double *      x = c->work.ptr, *y = x + c->ld, *s = y + c->ld;
     double        est   = o.lambda_max;
     int           steps = 0;
     if (!(o.lambda_max > 0.))
     {
-        hipLaunchKernelGGL(powerStartKernel, dim3(g), dim3(cg_threads), 0, st, y, d_minv, n, ctx->red_ws);
-        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 1, -1, 0);
+        if (int rc = launchReduce(ctx, powerStartKernel, n, s, {1}, y, d_minv))
+            return rc;
         for (; steps < o.max_power_iters; ++steps)
         {
-            hipLaunchKernelGGL(powerScaleKernel, dim3(g), dim3(cg_threads), 0, st, x, y, n, s);
+            hipLaunchKernelGGL(powerScaleKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, st, x, y, n, s);
             L3K_HIP(hipGetLastError());
             if (int rc = l3k_mf_apply(mf, x, size_t(n), y, size_t(n), 1, 1., 0.))
                 return rc;
-            hipLaunchKernelGGL(powerStepKernel, dim3(g), dim3(cg_threads), 0, st, y, d_minv, x, n, ctx->red_ws);
-            hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 0, 1, 0);
+            if (int rc = launchReduce(ctx, powerStepKernel, n, s, {0, 1}, y, d_minv, x))
+                return rc;
         }
-        L3K_HIP(hipGetLastError());
         L3K_HIP(hipMemcpyAsync(&est, s, sizeof est, hipMemcpyDeviceToHost, st)); // (the one readback of the creation)
         L3K_HIP(hipStreamSynchronize(st));
         if (!l3k::host::chebFinite(&est) || !(est > 0.))
@@ -672,85 +683,52 @@ int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, 
         setError("l3k_pcg_solve_cheb: null argument");
         return -1;
     }
-    if (mf->mesh->n_ghost_nodes != 0)
-    {
-        setError(cheb_single_rank, "l3k_pcg_solve_cheb");
-        return -1;
-    }
+    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_pcg_solve_cheb"))
+        return rc;
     if (c->mf != mf)
     {
         setError("l3k_pcg_solve_cheb: the preconditioner was created for another system");
         return -1;
     }
-    const l3k_cg_opts o = opts ? *opts : l3k_cg_opts{1e-6, 10000, 0, 1};
-    l3k_ctx*          ctx = mf->ctx;
-    hipStream_t       st  = ctx->stream;
-    const int64_t     n = c->n, ld = c->ld;
-    DevBuf< double >  work; // r | z | p | ap (A z inside the preconditioner) | w | s[8]
+    l3k_ctx*         ctx = mf->ctx;
+    const int64_t    n = c->n, ld = c->ld;
+    DevBuf< double > work; // r | z | p | ap (A z inside the preconditioner) | w | s[8]
     if (int rc = work.alloc(size_t(5 * ld + 8)))
         return rc;
     double *r = work.ptr, *z = r + ld, *p = z + ld, *ap = p + ld, *w = ap + ld, *s = w + ld;
-    double  h[4];
-    const auto scalars = [&]() -> int {
-        L3K_HIP(hipMemcpyAsync(h, s, sizeof h, hipMemcpyDeviceToHost, st));
-        L3K_HIP(hipStreamSynchronize(st));
-        return 0;
-    };
+    CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // r = b - A x0 (0 on the frozen rows), s[3] = <r, r>
     if (int rc = l3k_mf_apply(mf, d_x, size_t(n), r, size_t(n), 1, 1., 0.))
         return rc;
-    const int g = cgGrid(n);
-    hipLaunchKernelGGL(cgInitRKernel, dim3(g), dim3(cg_threads), 0, st, r, d_b, c->minv, n, ctx->red_ws);
-    hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, g, s, 3, -1, 0);
-    L3K_HIP(hipGetLastError());
-    double scale = 1.;
-    if (o.residual_scaling == 2)
-    {
-        if (int rc = l3k_cg_dot_pap(ctx, d_b, d_b, n, s)) // s[1] = <b, b> (scratch use of the slot)
-            return rc;
-    }
-    if (int rc = scalars())
+    if (int rc = launchReduce(ctx, cgInitRKernel, n, s, {3}, r, d_b, c->minv))
         return rc;
-    const double rr0 = std::sqrt(h[3]);
-    if (o.residual_scaling == 1)
-        scale = rr0 > 0. ? rr0 : 1.;
-    else if (o.residual_scaling == 2)
-        scale = std::sqrt(h[1]) > 1e-300 ? std::sqrt(h[1]) : 1e-300;
-    double    res   = rr0 / scale;
-    int       it    = 0;
-    const int every = o.check_every > 0 ? o.check_every : 1;
-    if (res > o.tol && it < o.max_iters)
+    if (int rc = cg.start(d_b, n))
+        return rc;
+    if (cg.running())
     {
         // z = M^-1 r, s[2] = <r, z>; p = z; s[0] <- s[2]
         if (int rc = chebApply(c, r, z, w, ap, s))
             return rc;
-        L3K_HIP(hipMemcpyAsync(p, z, size_t(n) * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, st, ctx->red_ws, 0, s, -1, -1, 1);
-        L3K_HIP(hipGetLastError());
+        L3K_HIP(hipMemcpyAsync(p, z, size_t(n) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        if (int rc = launchShift(ctx, s))
+            return rc;
     }
-    while (res > o.tol && it < o.max_iters)
+    while (cg.running())
     {
         if (int rc = l3k_mf_apply_energy(mf, p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
         if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, c->minv, n, s))
             return rc;
-        ++it;
-        if (it % every == 0 || it == o.max_iters)
-        {
-            if (int rc = scalars())
-                return rc;
-            res = std::sqrt(h[3]) / scale;
-        }
-        if (res <= o.tol || it >= o.max_iters) // (x is final: no preconditioner application for a direction nobody takes)
+        if (int rc = cg.afterIteration())
+            return rc;
+        if (cg.res <= cg.o.tol || cg.it >= cg.o.max_iters) // (x is final: no preconditioner application for a direction nobody takes)
             break;
         if (int rc = chebApply(c, r, z, w, ap, s)) // (ap is free until the next apply: it holds A z in here)
             return rc;
         if (int rc = l3k_cg_update_p(ctx, p, z, n, s))
             return rc;
     }
-    result->achieved_tol = res;
-    result->iterations   = it;
-    result->converged    = res <= o.tol;
+    cg.report(result);
     return 0;
 }
 } // extern "C"

@@ -6,6 +6,9 @@ Jacobi preconditioner (solve/NativePreconditioners.hpp:36-96); Belos is a third-
 pinned end to end (solution / error thresholds), not iterate by iterate.  Vector updates and dot
 products are torch ops (plumbing); the operator apply -- the hot path -- is the HIP kernel behind `apply`.
 """
+import ctypes as C
+import inspect
+
 import torch
 import torch.distributed as dist
 
@@ -128,7 +131,6 @@ class ChebyshevPreconditioner:
     power method and multiplied by boost_factor."""
 
     def __init__(self, system, minv, degree=1, cond_est=30., max_power_iters=10, boost_factor=1.1, lambda_max=None):
-        import ctypes as C
         from . import capi
         self.system, self.minv = system, minv
         if minv is None or minv.numel() != system.mesh.n_owned_dofs or not minv.is_contiguous():
@@ -141,7 +143,6 @@ class ChebyshevPreconditioner:
     @property
     def info(self):
         """lambda_max, lambda_min, lambda_est, degree, power_iters, applies_per_call (l3k_cheb_info)"""
-        import ctypes as C
         import types
         from . import capi
         i = capi.ChebInfo()
@@ -151,7 +152,6 @@ class ChebyshevPreconditioner:
     def apply(self, r, z):
         """z <- p(D^-1 A) D^-1 r (l3k_cheb_apply); r, z: distinct 1-D device tensors over the owned dofs.  z goes through
         l3k_mf_apply, which refuses a vector that is not aligned as the system's kernel needs it."""
-        import ctypes as C
         from . import capi
         n = self.system.mesh.n_owned_dofs
         if r.numel() != n or z.numel() != n or not (r.is_contiguous() and z.is_contiguous()):
@@ -176,7 +176,6 @@ class ChebyshevPreconditioner:
 
 def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
     """NativeJacobiImpl::init through the C ABI (l3k_jacobi_inverse)."""
-    import ctypes as C
     from . import capi
     out = torch.empty_like(diag)
     capi.check(capi.load().l3k_jacobi_inverse(ctx._h, C.c_void_p(diag.data_ptr()), diag.numel(), float(damping),
@@ -187,6 +186,21 @@ def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
 _SCALING = {"none": 0, "initial": 1, "rhs": 2}
 
 
+def _vp(t):
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _checked(results, throw_on_fail):
+    if throw_on_fail and not all(r.converged for r in results):
+        raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
+    return results
+
+
+def _from_c(results, throw_on_fail):
+    """capi.CgResult's as IterSolveResult's; raises if one of them did not converge"""
+    return _checked([IterSolveResult(r.achieved_tol, r.iterations, bool(r.converged)) for r in results], throw_on_fail)
+
+
 def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", check_every=1, throw_on_fail=True,
         precond=None):
     """Jacobi-PCG entirely behind the C ABI (l3k_pcg_solve): apply, fused vector updates and reductions run on the
@@ -194,8 +208,8 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
     l3ster_amd.system.MatrixFreeSystem, b / x / minv 1-D device tensors over its owned dofs.  `precond`: a
     ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb; a multivector b then solves
     its columns one after the other, as l3k_pcg_solve_cols does."""
-    import ctypes as C
     from . import capi
+    lib = capi.load()
     opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
     if precond is not None:
         if minv is not None:
@@ -208,54 +222,45 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
             raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")
         if any(_overlap(bc, xc, n) for bc, xc in cols):
             raise capi.L3KError("b and x must not share memory")
-        out = []
-        for bc, xc in cols:
-            res = capi.CgResult()
-            capi.check(capi.load().l3k_pcg_solve_cheb(system._h, C.c_void_p(bc.data_ptr()), C.c_void_p(xc.data_ptr()), precond._h,
-                                                      C.byref(opts), C.byref(res)))
-            out.append(IterSolveResult(res.achieved_tol, res.iterations, bool(res.converged)))
-        if throw_on_fail and not all(r.converged for r in out):
-            raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
+        res_c = (capi.CgResult * len(cols))()
+        for (bc, xc), res in zip(cols, res_c):
+            capi.check(lib.l3k_pcg_solve_cheb(system._h, _vp(bc), _vp(xc), precond._h, C.byref(opts), C.byref(res)))
+        out = _from_c(res_c, throw_on_fail)
         return out[0] if b.dim() == 1 else out
     if b.dim() == 2:  # a multivector (ncols, ld) of right-hand sides: the columns one after the other (l3k_pcg_solve_cols)
         nc = b.shape[0]
         if x.shape != b.shape or b.stride(1) != 1 or x.stride(1) != 1:
             raise capi.L3KError("b and x must be (ncols, ld) tensors of one shape with unit stride along rows")
         res_c = (capi.CgResult * nc)()
-        capi.check(capi.load().l3k_pcg_solve_cols(system._h, C.c_void_p(b.data_ptr()), b.stride(0) if nc > 1 else b.shape[1],
-                                                  C.c_void_p(x.data_ptr()), x.stride(0) if nc > 1 else x.shape[1], nc,
-                                                  C.c_void_p(0 if minv is None else minv.data_ptr()), C.byref(opts), res_c))
-        out = [IterSolveResult(r.achieved_tol, r.iterations, bool(r.converged)) for r in res_c]
-        if throw_on_fail and not all(r.converged for r in out):
-            raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
-        return out
+        capi.check(lib.l3k_pcg_solve_cols(system._h, _vp(b), b.stride(0) if nc > 1 else b.shape[1], _vp(x),
+                                          x.stride(0) if nc > 1 else x.shape[1], nc, _vp(minv), C.byref(opts), res_c))
+        return _from_c(res_c, throw_on_fail)
     res = capi.CgResult()
-    capi.check(capi.load().l3k_pcg_solve(system._h, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()),
-                                         C.c_void_p(0 if minv is None else minv.data_ptr()), C.byref(opts), C.byref(res)))
-    if throw_on_fail and not res.converged:
-        raise RuntimeError("Solver failed to converge")  # solve/BelosSolvers.hpp:103
-    return IterSolveResult(res.achieved_tol, res.iterations, bool(res.converged))
+    capi.check(lib.l3k_pcg_solve(system._h, _vp(b), _vp(x), _vp(minv), C.byref(opts), C.byref(res)))
+    return _from_c([res], throw_on_fail)[0]
 
 
 def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None,
                     throw_on_fail=True, allreduce=None, check_every=1, precond=None):
     """The same iteration for a partitioned system: `op.apply(X, Y)` is a DistributedOperator over this rank's owned
     rows; the fused l3k_cg_* kernels keep the scalars in a device block that is all-reduced between them (two small
-    all-reduces per iteration, as Belos does).  `precond`: the Chebyshev-Jacobi preconditioner over minv in place of
-    the diagonal one; the iteration is then _pcg_distributed_chebyshev's (see there)."""
-    if precond is not None:
-        return _pcg_distributed_chebyshev(op, ctx, b, x, minv, precond, tol, max_iters, residual_scaling, group, throw_on_fail,
-                                          allreduce, check_every)
-    import ctypes as C
+    all-reduces per iteration, as Belos does).
+
+    `precond`: the Chebyshev-Jacobi preconditioner over minv (required then) in place of the diagonal one: a dict of
+    ChebyshevPreconditioner's options (degree, cond_est, max_power_iters, boost_factor, lambda_max) or an object whose
+    .info has lambda_max, lambda_min and degree (a ChebyshevPreconditioner's numbers on another operator).  The
+    iteration is then that of l3k_pcg_solve_cheb with the exported pieces (l3k_cheb_first / _step, l3k_cg_update_rx /
+    _update_p): the inner applies go through op.apply and need no reduction, the outer scalars and -- without
+    lambda_max -- <x, y> and <y, y> of the power method go through the same reduction hook.  The power method starts
+    from power_start_vector over this rank's rows."""
     from . import capi
-    lib = capi.load()
-    n = b.numel()
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    if precond is not None and minv is None:
+        raise capi.L3KError("pcg_distributed(precond=...) needs minv: the preconditioner is a polynomial in D^-1 A")
+    lib, check, h, n = capi.load(), capi.check, ctx._h, b.numel()
     s = torch.zeros(8, dtype=torch.float64, device=b.device)
-    r, p, ap = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    import inspect
     fuse_energy = "energy" in inspect.signature(op.apply).parameters
+    it = 0
 
     def reduce(view):
         if allreduce is not None:  # pluggable (the threaded multi-rank emulation of the tests)
@@ -263,17 +268,8 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
         elif multi:
             dist.all_reduce(view, op=dist.ReduceOp.SUM, group=group)
 
-    op.apply(x[None, :], r[None, :])
-    capi.check(lib.l3k_cg_init(ctx._h, vp(r), vp(b), vp(p), vp(minv), n, vp(s)))
-    reduce(s[2:4])
-    s[0] = s[2]
-    bb = torch.dot(b, b).reshape(1)
-    reduce(bb)
-    h = s[:4].tolist()
-    rr0 = h[3] ** 0.5
-    scale = {"none": 1.0, "initial": rr0 if rr0 > 0 else 1.0, "rhs": max(bb.item() ** 0.5, 1e-300)}[residual_scaling]
-    res, it = rr0 / scale, 0
-    while res > tol and it < max_iters:
+    def apply_energy(p, ap):  # ap = A p, reduced s[1] = <p, A p>
+        nonlocal fuse_energy
         if fuse_energy:  # <p, A p> from the element kernels' quadrature stage where they can (l3k_mf_energy_*)
             op.apply(p[None, :], ap[None, :], energy=s)
             if it == 0:
@@ -287,98 +283,64 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
         else:
             op.apply(p[None, :], ap[None, :])
         if not fuse_energy:
-            capi.check(lib.l3k_cg_dot_pap(ctx._h, vp(p), vp(ap), n, vp(s)))
+            check(lib.l3k_cg_dot_pap(h, _vp(p), _vp(ap), n, _vp(s)))
         reduce(s[1:2])
-        capi.check(lib.l3k_cg_update_z(ctx._h, vp(r), vp(ap), vp(minv), n, vp(s)))  # (r holds z = M^-1 r: l3k.h)
+
+    def start():  # with the reduced <r, r> of the initial residual in s[3]: (residual scale, scaled residual)
+        bb = torch.dot(b, b).reshape(1)
+        reduce(bb)
+        rr0 = s[3].item() ** 0.5
+        scale = {"none": 1.0, "initial": rr0 if rr0 > 0 else 1.0, "rhs": max(bb.item() ** 0.5, 1e-300)}[residual_scaling]
+        return scale, rr0 / scale
+
+    if precond is None:  # the iteration of l3k_pcg_solve
+        r, p, ap = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
+        op.apply(x[None, :], r[None, :])
+        check(lib.l3k_cg_init(h, _vp(r), _vp(b), _vp(p), _vp(minv), n, _vp(s)))
         reduce(s[2:4])
-        capi.check(lib.l3k_cg_update_px(ctx._h, vp(p), vp(x), vp(r), n, vp(s)))
-        it += 1
-        if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
-            res = s[3].item() ** 0.5 / scale
-    converged = res <= tol
-    if throw_on_fail and not converged:
-        raise RuntimeError("Solver failed to converge")
-    return IterSolveResult(res, it, converged)
-
-
-def _pcg_distributed_chebyshev(op, ctx, b, x, minv, precond, tol, max_iters, residual_scaling, group, throw_on_fail, allreduce,
-                               check_every):
-    """pcg_distributed with the Chebyshev-Jacobi preconditioner over minv (required): `precond` is a dict of
-    ChebyshevPreconditioner's options (degree, cond_est, max_power_iters, boost_factor, lambda_max) or an object whose
-    .info has lambda_max, lambda_min and degree (a ChebyshevPreconditioner's numbers on another operator).  The
-    iteration is that of l3k_pcg_solve_cheb with the exported pieces (l3k_cheb_first / _step, l3k_cg_update_rx /
-    _update_p): the inner applies go through op.apply and need no reduction, the outer scalars and -- without
-    lambda_max -- <x, y> and <y, y> of the power method go through the same reduction hook.  The power method starts
-    from power_start_vector over this rank's rows."""
-    import ctypes as C
-    import inspect
-    from . import capi
-    lib = capi.load()
-    if minv is None:
-        raise capi.L3KError("pcg_distributed(precond=...) needs minv: the preconditioner is a polynomial in D^-1 A")
-    n = b.numel()
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    s = torch.zeros(8, dtype=torch.float64, device=b.device)
-    r, z, p, ap, w = (torch.empty_like(b) for _ in range(5))
-    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    fuse_energy = "energy" in inspect.signature(op.apply).parameters
-
-    def reduce(view):
-        if allreduce is not None:
-            allreduce(view)
-        elif multi:
-            dist.all_reduce(view, op=dist.ReduceOp.SUM, group=group)
-
-    c0, steps = _distributed_chebyshev(precond, op, minv, reduce)
-
-    def cheb():  # z = M^-1 r, reduced s[2] = <r, z> (the last kernel of the application leaves the local sum)
-        capi.check(lib.l3k_cheb_first(ctx._h, vp(r), vp(minv), c0, vp(w), vp(z), n, vp(None if steps else s)))
-        for k, (ca, cb) in enumerate(steps):
-            op.apply(z[None, :], ap[None, :])  # (ap is free here: it holds A z)
-            capi.check(lib.l3k_cheb_step(ctx._h, vp(r), vp(ap), vp(minv), ca, cb, vp(w), vp(z), n,
-                                         vp(s if k == len(steps) - 1 else None)))
-        reduce(s[2:3])
-
-    op.apply(x[None, :], r[None, :])
-    r.copy_(torch.where(minv != 0, b - r, torch.zeros_like(b)))  # (frozen rows: out of the residual from the start)
-    s[3] = torch.dot(r, r)
-    reduce(s[3:4])
-    bb = torch.dot(b, b).reshape(1)
-    reduce(bb)
-    rr0 = s[3].item() ** 0.5
-    scale = {"none": 1.0, "initial": rr0 if rr0 > 0 else 1.0, "rhs": max(bb.item() ** 0.5, 1e-300)}[residual_scaling]
-    res, it = rr0 / scale, 0
-    if res > tol and it < max_iters:
-        cheb()
-        p.copy_(z)
         s[0] = s[2]
-    while res > tol and it < max_iters:
-        if fuse_energy:  # as in pcg_distributed: every rank takes the same route to <p, A p>, decided at the first apply
-            op.apply(p[None, :], ap[None, :], energy=s)
-            if it == 0:
-                n_not = torch.tensor([0.0 if op.energy_fused else 1.0], dtype=torch.float64, device=b.device)
-                reduce(n_not)
-                fuse_energy = n_not.item() == 0.0
-            elif not op.energy_fused:
-                raise RuntimeError("the element kernels stopped accumulating <p, A p>")
-        else:
-            op.apply(p[None, :], ap[None, :])
-        if not fuse_energy:
-            capi.check(lib.l3k_cg_dot_pap(ctx._h, vp(p), vp(ap), n, vp(s)))
-        reduce(s[1:2])
-        capi.check(lib.l3k_cg_update_rx(ctx._h, vp(x), vp(r), vp(p), vp(ap), vp(minv), n, vp(s)))
+        scale, res = start()
+        while res > tol and it < max_iters:
+            apply_energy(p, ap)
+            check(lib.l3k_cg_update_z(h, _vp(r), _vp(ap), _vp(minv), n, _vp(s)))  # (r holds z = M^-1 r: l3k.h)
+            reduce(s[2:4])
+            check(lib.l3k_cg_update_px(h, _vp(p), _vp(x), _vp(r), n, _vp(s)))
+            it += 1
+            if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
+                res = s[3].item() ** 0.5 / scale
+    else:  # the iteration of l3k_pcg_solve_cheb
+        r, z, p, ap, w = (torch.empty_like(b) for _ in range(5))
+        c0, steps = _distributed_chebyshev(precond, op, minv, reduce)
+
+        def cheb():  # z = M^-1 r, reduced s[2] = <r, z> (the last kernel of the application leaves the local sum)
+            check(lib.l3k_cheb_first(h, _vp(r), _vp(minv), c0, _vp(w), _vp(z), n, _vp(None if steps else s)))
+            for k, (ca, cb) in enumerate(steps):
+                op.apply(z[None, :], ap[None, :])  # (ap is free here: it holds A z)
+                check(lib.l3k_cheb_step(h, _vp(r), _vp(ap), _vp(minv), ca, cb, _vp(w), _vp(z), n,
+                                        _vp(s if k == len(steps) - 1 else None)))
+            reduce(s[2:3])
+
+        op.apply(x[None, :], r[None, :])
+        r.copy_(torch.where(minv != 0, b - r, torch.zeros_like(b)))  # (frozen rows: out of the residual from the start)
+        s[3] = torch.dot(r, r)
         reduce(s[3:4])
-        it += 1
-        if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
-            res = s[3].item() ** 0.5 / scale
-        if res <= tol or it >= max_iters:  # (x is final: no preconditioner application for a direction nobody takes)
-            break
-        cheb()
-        capi.check(lib.l3k_cg_update_p(ctx._h, vp(p), vp(z), n, vp(s)))
-    converged = res <= tol
-    if throw_on_fail and not converged:
-        raise RuntimeError("Solver failed to converge")
-    return IterSolveResult(res, it, converged)
+        scale, res = start()
+        if res > tol and it < max_iters:
+            cheb()
+            p.copy_(z)
+            s[0] = s[2]
+        while res > tol and it < max_iters:
+            apply_energy(p, ap)
+            check(lib.l3k_cg_update_rx(h, _vp(x), _vp(r), _vp(p), _vp(ap), _vp(minv), n, _vp(s)))
+            reduce(s[3:4])
+            it += 1
+            if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
+                res = s[3].item() ** 0.5 / scale
+            if res <= tol or it >= max_iters:  # (x is final: no preconditioner application for a direction nobody takes)
+                break
+            cheb()
+            check(lib.l3k_cg_update_p(h, _vp(p), _vp(z), n, _vp(s)))
+    return _checked([IterSolveResult(res, it, res <= tol)], throw_on_fail)[0]
 
 
 def _distributed_chebyshev(precond, op, minv, reduce):
