@@ -435,6 +435,68 @@ int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, 
                      double* d_s);
 int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, double* d_s);
 
+/* ---- device CSR operator: the assembled and the condensed system in front of the solver -----------------------------------
+ * A square CSR matrix in the format l3k_assembled_scatter, l3k_assemble_global and l3k_condense_global fill: d_row_ptr int64
+ * [n + 1], d_col_ind int32 strictly ascending within a row, d_values double; single rank, rows and columns in the local dofs.
+ * The object keeps the three pointers and copies nothing: the caller keeps the arrays alive and may rewrite d_values between
+ * calls (a time loop assembles again), but not the graph.
+ *
+ * Nothing here accumulates atomically in floating point (one writer per row, a fixed butterfly over the lanes of a row, the
+ * two-stage reduction of the PCG for <x, A x>): applies, and the solves below, are bitwise reproducible on ANY context, in
+ * deterministic mode or not.
+ *
+ * l3k_csr_create: one validation pass on the device with a single readback (synchronises the context's stream).  Refused with
+ *   -1 and a message naming the first offence: row_ptr[0] != 0, a decreasing row_ptr, a column outside [0, n), columns not
+ *   strictly ascending within a row -- no later call can gather out of bounds.  The columns are only read once row_ptr has
+ *   passed.  lanes_per_row: the lanes of a wave64 that share a row, 4, 16 or 64; 0 = chosen from the mean length of the
+ *   non-empty rows (<= 8: 4, <= 64: 16, else 64).  Also -1: any other lanes_per_row, n < 0, n >= 2^31.
+ * l3k_csr_info_get: the statistics the validation pass gathered.
+ * l3k_csr_apply: y <- alpha A x + beta y for ncols columns (column c at + c * ld), tpetra_crsmatrix_t::apply as Belos calls it
+ *   under solve/BelosSolvers.hpp:116-122.  beta == 0: y is not read (a NaN in it does not survive); an empty row gives beta y.
+ *   Up to four columns share one pass over the matrix.  x and y must not overlap.
+ * l3k_csr_apply_energy: y <- A x and s[1] <- <x, A x> for one column in one pass (what l3k_mf_apply_energy is to the
+ *   matrix-free operator); no other slot of the scalar block s[8] is written.
+ * l3k_csr_diag: d_diag[i] = a_ii, 0 where the row stores none (getLocalDiagCopy, solve/NativePreconditioners.hpp:76);
+ *   d_minv[i] = sign(a_ii) damping / max(|a_ii|, threshold), the formula of l3k_jacobi_inverse, on every non-empty row and 0 on
+ *   an EMPTY row, so that the frozen-row rule of l3k_pcg_solve carries the internal dofs of a condensed graph and any skipped
+ *   rows: x keeps its value there.  Either output may be NULL.
+ * l3k_csr_dirichlet: DirichletBCAlgebraic::apply (bcs/DirichletBC.hpp:82-150) in place.  d_mask [n] flags the Dirichlet dofs,
+ *   d_bc_vals [ncols][ldg] holds the prescribed values, d_rhs [ncols][ldr] the right-hand sides.  A flagged row becomes the
+ *   identity row and its rhs the prescribed value; in every other row each entry in a flagged column j gives rhs_i -= a_ij g_j
+ *   (summed in a fixed order, one writer per row) and is set to 0.  A flagged row without a stored diagonal entry is refused
+ *   (-1, nothing written; the reference dereferences end() there): one readback, the call synchronises.  d_values is the
+ *   operator's own values array, passed again because this is the one call that writes the matrix.
+ *
+ * The solver on a CSR operator -- the loops are those of l3k_pcg_solve, l3k_cheb_create, l3k_cheb_apply and l3k_pcg_solve_cheb,
+ * run with l3k_csr_apply / l3k_csr_apply_energy in place of the matrix-free applies; options, results, frozen rows and vector
+ * passes as documented there; vectors have n entries:
+ * l3k_csr_pcg_solve, l3k_csr_pcg_solve_cols: Belos "Block CG" with NativeJacobi on the assembled matrix (solve/BelosSolvers.hpp:116-122).
+ * l3k_csr_cheb_create: Ifpack2ChebyshevPreconditioner on a matrix (solve/Ifpack2Preconditioners.hpp:107-131); d_minv from
+ *   l3k_csr_diag.  The object is an l3k_cheb: l3k_cheb_apply, l3k_cheb_info_get and l3k_cheb_destroy serve it.
+ * l3k_csr_pcg_solve_cheb: l3k_pcg_solve_cheb with a preconditioner created on this operator.                                  */
+typedef struct l3k_csr l3k_csr;
+typedef struct
+{
+    int64_t n, nnz, n_empty_rows, max_row_len;
+    double  mean_row_len;  /* of the non-empty rows; 0 if there is none */
+    int     lanes_per_row; /* in use: 4, 16 or 64                       */
+} l3k_csr_info;
+int l3k_csr_create(l3k_ctx* ctx, int64_t n, const int64_t* d_row_ptr, const int32_t* d_col_ind, const double* d_values,
+                   int lanes_per_row, l3k_csr** out);
+int l3k_csr_info_get(const l3k_csr* A, l3k_csr_info* out);
+int l3k_csr_apply(l3k_csr* A, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha, double beta);
+int l3k_csr_apply_energy(l3k_csr* A, const double* d_x, double* d_y, double* d_s);
+int l3k_csr_diag(l3k_csr* A, double* d_diag, double damping, double threshold, double* d_minv);
+int l3k_csr_dirichlet(l3k_csr* A, double* d_values, const uint8_t* d_mask, const double* d_bc_vals, size_t ldg, double* d_rhs,
+                      size_t ldr, int ncols);
+int l3k_csr_destroy(l3k_csr* A);
+int l3k_csr_pcg_solve(l3k_csr* A, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts,
+                      l3k_cg_result* result);
+int l3k_csr_pcg_solve_cols(l3k_csr* A, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                           const l3k_cg_opts* opts, l3k_cg_result* results);
+int l3k_csr_cheb_create(l3k_csr* A, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
+int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result);
+
 /* ---- LocalAssembly --------------------------------------------------------------------------------------------------
  * assembleLocalSystem for a batch of elements, algsys/AssembleLocalSystem.hpp:234-256: K_e row-major [Nd][Nd],
  * F_e column-major [Nd][n_rhs] per element, elements [first, first+count).  d_K may be NULL (then only the checksum

@@ -10,6 +10,7 @@
 //       .apply(halo, X, Y, ...)     ~ applyImpl of a partitioned system, exchange included    :1020-1140
 //       .scatterLocalSystems(...)   ~ scatterLocalSystem / assembleGlobalSystem             algsys/ScatterLocalSystem.hpp:24-54
 //   l3k::Halo                    ~ comm::ImportExportContext + comm::Import / comm::Export  comm/ImportExport.hpp:29-72,130-215
+//   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
 //   l3k::computeIntegral / computeNormL2 ~ post/Integral.hpp:113-128, post/NormL2.hpp:31-62 (one rank)
 // Errors: the reference throws std::runtime_error from util::throwingAssert (util/Assertion.hpp:88-95); so does this
@@ -412,6 +413,76 @@ public:
 
 private:
     l3k_mf* m_mf{};
+};
+
+// The assembled or condensed system in front of the solver: a square CSR matrix on the device (row_ptr int64 [n + 1], col_ind
+// int32 strictly ascending within a row, values -- the arrays assembleGlobal / l3k_condense_global fill).  Nothing is copied: the
+// caller keeps the arrays alive and may assemble the values again.  The constructor validates the graph on the device and throws
+// on one through which an apply could gather out of bounds.  Applies and solves are bitwise reproducible on any context.
+//   apply            ~ tpetra_crsmatrix_t::apply under Belos              solve/BelosSolvers.hpp:116-122
+//   diag             ~ getLocalDiagCopy + NativeJacobiImpl::init          solve/NativePreconditioners.hpp:75-96
+//   applyDirichlet   ~ DirichletBCAlgebraic::apply                        bcs/DirichletBC.hpp:82-150
+//   solve            ~ alg_sys.solve(CG{opts, NativeJacobiOpts{}}) on the assembled matrix
+class CsrOperator
+{
+public:
+    CsrOperator(Context& ctx, int64_t n, const int64_t* d_row_ptr, const int32_t* d_col_ind, double* d_values, int lanes_per_row = 0)
+        : m_values{d_values}
+    {
+        check(l3k_csr_create(ctx.get(), n, d_row_ptr, d_col_ind, d_values, lanes_per_row, &m_csr));
+    }
+    CsrOperator(const CsrOperator&)            = delete;
+    CsrOperator& operator=(const CsrOperator&) = delete;
+    ~CsrOperator() { l3k_csr_destroy(m_csr); }
+    l3k_csr_info info() const
+    {
+        l3k_csr_info i{};
+        check(l3k_csr_info_get(m_csr, &i));
+        return i;
+    }
+    // Y <- alpha*A*X + beta*Y; beta == 0: Y is not read
+    void apply(const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols = 1, double alpha = 1., double beta = 0.) const
+    {
+        check(l3k_csr_apply(m_csr, d_x, ldx, d_y, ldy, ncols, alpha, beta));
+    }
+    // Y <- A X and d_s[1] <- <X, A X> in one pass (d_s: 8 device doubles)
+    void applyEnergy(const double* d_x, double* d_y, double* d_s) const { check(l3k_csr_apply_energy(m_csr, d_x, d_y, d_s)); }
+    // the stored diagonal (0 where none) and / or minv = sign(d) damping / max(|d|, threshold), 0 on an empty row (frozen in the
+    // solve); either may be nullptr
+    void diag(double* d_diag, double* d_minv, double damping = 1., double threshold = 0.) const
+    {
+        check(l3k_csr_diag(m_csr, d_diag, damping, threshold, d_minv));
+    }
+    // in place: identity rows and prescribed values on the flagged dofs, rhs -= A_fd g and A_fd = 0 elsewhere; throws, with
+    // nothing changed, if a flagged row stores no diagonal entry
+    void applyDirichlet(const uint8_t* d_mask, const double* d_bc_vals, size_t ldg, double* d_rhs, size_t ldr, int ncols = 1) const
+    {
+        check(l3k_csr_dirichlet(m_csr, m_values, d_mask, d_bc_vals, ldg, d_rhs, ldr, ncols));
+    }
+    // d_x holds the initial guess and the result; d_minv from diag() (or nullptr); throws if not converged, like the reference
+    l3k_cg_result solve(const double* d_b, double* d_x, const double* d_minv, l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        l3k_cg_result res{};
+        check(l3k_csr_pcg_solve(m_csr, d_b, d_x, d_minv, &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    std::vector< l3k_cg_result > solve(const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                                       l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        std::vector< l3k_cg_result > res(static_cast< size_t >(ncols));
+        check(l3k_csr_pcg_solve_cols(m_csr, d_b, ldb, d_x, ldx, ncols, d_minv, &opts, res.data()));
+        for (const auto& r : res)
+            if (!r.converged)
+                throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    l3k_csr* get() const { return m_csr; }
+
+private:
+    l3k_csr* m_csr{};
+    double*  m_values{};
 };
 
 // convertMeshToOrder< order >(mesh_o1) for one rank's hexahedra (mesh/ConvertMeshToOrder.hpp:51-104), on the device:

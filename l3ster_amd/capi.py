@@ -45,6 +45,12 @@ class ChebInfo(C.Structure):
                 ("power_iters", C.c_int), ("applies_per_call", C.c_int)]
 
 
+class CsrInfo(C.Structure):
+    """l3k_csr_info: what the validation pass of l3k_csr_create gathered"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
+                ("mean_row_len", C.c_double), ("lanes_per_row", C.c_int)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -195,6 +201,18 @@ SIGNATURES = {
     "l3k_cheb_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_rx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_p": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "l3k_csr_create": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "l3k_csr_info_get": (C.c_int, [_vp, C.POINTER(CsrInfo)]),
+    "l3k_csr_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),
+    "l3k_csr_apply_energy": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "l3k_csr_diag": (C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
+    "l3k_csr_dirichlet": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int]),
+    "l3k_csr_destroy": (C.c_int, [_vp]),
+    "l3k_csr_pcg_solve": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_csr_pcg_solve_cols": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, _vp, C.POINTER(CgOpts),
+                                         C.POINTER(CgResult)]),
+    "l3k_csr_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
+    "l3k_csr_pcg_solve_cheb": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

@@ -1,5 +1,6 @@
-// api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the single-rank driver.
-#include "objects.hpp"
+// api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the single-rank drivers, written
+// once over the matrix-free operator and the device CSR operator (LinOp below).
+#include "reduce.hpp"
 
 #include "host/chebyshev.hpp"
 
@@ -8,19 +9,7 @@ namespace
 // ---- fused vector kernels of the Jacobi-PCG iteration (solve/BelosSolvers.hpp:116-122 "Block CG" with one column +
 // solve/NativePreconditioners.hpp:36-96).  Scalars live in a device array s: 0 <r,z>, 1 <p,Ap>, 2 <r,z> new, 3 <r,r>.
 // Every dot product is a two-stage reduction in a fixed order (bitwise reproducible for a given grid).
-constexpr int cg_threads = 256, cg_blocks = l3k_cg_blocks;
-__device__ __forceinline__ double blockSum(double v, double* sh)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = cg_threads / 2; w > 0; w >>= 1)
-    {
-        if (threadIdx.x < w)
-            sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
+using namespace l3k::red; // cg_threads, cg_blocks, liveRow, storePartials and the finish stage (reduce.hpp, shared with api_csr.hip)
 // the rows of a thread: firstRow(), firstRow() + rowStep(), ... < n
 __device__ __forceinline__ int64_t firstRow()
 {
@@ -30,26 +19,6 @@ __device__ __forceinline__ int64_t rowStep()
 {
     return int64_t(gridDim.x) * cg_threads;
 }
-// A row is live where minv != 0, frozen otherwise.  For every double -- NaN and both zeros included -- liveRow(m) and m != 0.
-// agree; the test is on the BITS of minv because the library is built with -ffinite-math-only and without signed zeros, under
-// which m != 0. ? m * e : 0. may be folded to m * e -- and a non-finite e (A z on a frozen row) would get through.
-__device__ __forceinline__ bool liveRow(double m)
-{
-    return (__double_as_longlong(m) & 0x7fffffffffffffffLL) != 0;
-}
-// block sums of acc[0 .. n_rows) in a fixed order: partial[k * gridDim.x + blockIdx.x]
-template < int n_rows >
-__device__ __forceinline__ void storePartials(const double (&acc)[n_rows], double* __restrict__ sh, double* __restrict__ partial)
-{
-    for (int k = 0; k < n_rows; ++k)
-    {
-        if (k)
-            __syncthreads();
-        const double t = blockSum(acc[k], sh);
-        if (threadIdx.x == 0)
-            partial[k * gridDim.x + blockIdx.x] = t;
-    }
-}
 __global__ __launch_bounds__(cg_threads) void cgDotKernel(const double* __restrict__ u, const double* __restrict__ v, int64_t n,
                                                           double* __restrict__ partial)
 {
@@ -58,23 +27,6 @@ __global__ __launch_bounds__(cg_threads) void cgDotKernel(const double* __restri
     for (int64_t i = firstRow(); i < n; i += rowStep())
         acc[0] += __builtin_nontemporal_load(u + i) * __builtin_nontemporal_load(v + i);
     storePartials(acc, sh, partial);
-}
-// the finish stage of a reduction: s[dst0] = sum partial[0][:], s[dst1] = sum partial[1][:] (dst1 < 0: one row; no other slot is
-// written)
-__global__ __launch_bounds__(cg_threads) void cgFinishKernel(const double* __restrict__ partial, int n_blocks, double* __restrict__ s,
-                                                             int dst0, int dst1)
-{
-    __shared__ double sh[cg_threads];
-    for (int row = 0; row < (dst1 >= 0 ? 2 : 1); ++row)
-    {
-        double acc = 0.;
-        for (int i = threadIdx.x; i < n_blocks; i += cg_threads)
-            acc += partial[row * n_blocks + i];
-        __syncthreads();
-        const double t = blockSum(acc, sh);
-        if (threadIdx.x == 0)
-            s[row == 0 ? dst0 : dst1] = t;
-    }
 }
 // the shift: <r,z> of this iteration becomes the old one.  A launch of its own AFTER the vector kernel that divides by s[0]:
 // every block of that kernel must have read alpha and beta first
@@ -292,20 +244,6 @@ __global__ __launch_bounds__(cg_threads) void powerScaleKernel(double* __restric
         __builtin_nontemporal_store(__builtin_nontemporal_load(y + i) * f, x + i);
 }
 // ------------------------------------------------------------------------------------------------ launches
-int cgWorkspace(l3k_ctx* ctx)
-{
-    if (!ctx->red_ws) // (allocated by l3k_ctx_create on the context's device)
-    {
-        setError("context without reduction workspace");
-        return -3;
-    }
-    return 0;
-}
-// the slots of s that the finish stage of a reduction writes (cgFinishKernel)
-struct Slots
-{
-    int dst0, dst1 = -1;
-};
 // One reducing pass over n rows: kernel(args..., n, partials), then the finish stage into s[to.dst0] (and s[to.dst1]).  d_s == nullptr:
 // the kernel alone (an instance that leaves no partials)
 template < typename... Params, typename... Args >
@@ -316,7 +254,7 @@ int launchReduce(l3k_ctx* ctx, void (*kernel)(Params...), int64_t n, double* d_s
     const int g = cgGrid(n);
     hipLaunchKernelGGL(kernel, dim3(g), dim3(cg_threads), 0, ctx->stream, args..., n, ctx->red_ws);
     if (d_s)
-        hipLaunchKernelGGL(cgFinishKernel, dim3(1), dim3(cg_threads), 0, ctx->stream, ctx->red_ws, g, d_s, to.dst0, to.dst1);
+        launchFinish(ctx, g, d_s, to);
     L3K_HIP(hipGetLastError());
     return 0;
 }
@@ -395,6 +333,30 @@ struct CgDriver
         result->converged    = res <= o.tol;
     }
 };
+// The operator of a single-rank solve: n rows, y <- A x, and y <- A x with s[1] <- <x, A x>, on the context's stream.  The PCG
+// loops, the power method and the Chebyshev recurrence below are written ONCE over this value; mfOp and csrOp make it
+struct LinOp
+{
+    l3k_ctx* ctx;
+    int64_t  n;
+    void*    object; // the l3k_mf or l3k_csr behind it
+    int (*apply_fn)(void*, const double*, double*, size_t);
+    int (*energy_fn)(void*, const double*, double*, double*);
+    int apply(const double* d_x, double* d_y) const { return apply_fn(object, d_x, d_y, size_t(n)); }
+    int applyEnergy(const double* d_x, double* d_y, double* d_s) const { return energy_fn(object, d_x, d_y, d_s); }
+};
+LinOp mfOp(l3k_mf* mf)
+{
+    return {mf->ctx, mf->mesh->nOwnedDofs(), mf,
+            [](void* o, const double* x, double* y, size_t n) { return l3k_mf_apply(static_cast< l3k_mf* >(o), x, n, y, n, 1, 1., 0.); },
+            [](void* o, const double* x, double* y, double* s) { return l3k_mf_apply_energy(static_cast< l3k_mf* >(o), x, y, s); }};
+}
+LinOp csrOp(l3k_csr* A)
+{
+    return {A->ctx, A->n, A,
+            [](void* o, const double* x, double* y, size_t n) { return l3k_csr_apply(static_cast< l3k_csr* >(o), x, n, y, n, 1, 1., 0.); },
+            [](void* o, const double* x, double* y, double* s) { return l3k_csr_apply_energy(static_cast< l3k_csr* >(o), x, y, s); }};
+}
 } // namespace
 
 extern "C" {
@@ -451,25 +413,21 @@ int l3k_cg_update_px(l3k_ctx* ctx, double* d_p, double* d_x, const double* d_z, 
     hipLaunchKernelGGL(cgUpdatePXKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, ctx->stream, d_p, d_x, d_z, n, d_s);
     return launchShift(ctx, d_s);
 }
-int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts,
-                  l3k_cg_result* result)
+} // extern "C"
+namespace
 {
-    if (!mf || !d_b || !d_x || !result)
-    {
-        setError("l3k_pcg_solve: null argument");
-        return -1;
-    }
-    if (int rc = singleRankOnly(mf, pcg_single_rank, "l3k_pcg_solve"))
-        return rc;
-    l3k_ctx*         ctx = mf->ctx;
-    const int64_t    n   = mf->mesh->nOwnedDofs();
+// the iteration of l3k_pcg_solve / l3k_csr_pcg_solve (include/l3k.h)
+int pcgSolve(const LinOp& A, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    l3k_ctx*         ctx = A.ctx;
+    const int64_t    n   = A.n;
     DevBuf< double > work; // z (the preconditioned residual, in the array named r) | p | ap | s[8]
     if (int rc = work.alloc(size_t(3 * n + 8)))
         return rc;
     double *r = work.ptr, *p = r + n, *ap = p + n, *s = ap + n;
     CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // z = M^-1 (b - A x0), p = z
-    if (int rc = l3k_mf_apply(mf, d_x, size_t(n), r, size_t(n), 1, 1., 0.))
+    if (int rc = A.apply(d_x, r))
         return rc;
     if (int rc = l3k_cg_init(ctx, r, d_b, p, d_minv, n, s))
         return rc;
@@ -477,7 +435,7 @@ int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_mi
         return rc;
     while (cg.running())
     {
-        if (int rc = l3k_mf_apply_energy(mf, p, ap, s)) // ap = A p, s[1] = <p, A p>
+        if (int rc = A.applyEnergy(p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
         if (int rc = l3k_cg_update_z(ctx, r, ap, d_minv, n, s)) // (r holds z = M^-1 r)
             return rc;
@@ -491,32 +449,76 @@ int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_mi
 }
 // the same for a multivector of right-hand sides (the reference's systems carry n_rhs columns: Belos "Block CG" with block size 1
 // iterates them one after the other, solve/BelosSolvers.hpp:116-122): column c of d_b / d_x at + c * ld; results[ncols]
-int l3k_pcg_solve_cols(l3k_mf* mf, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
-                       const l3k_cg_opts* opts, l3k_cg_result* results)
+int pcgCheckCols(const char* who, const void* object, size_t n, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols,
+                 const l3k_cg_result* results)
 {
-    if (!mf || !d_b || !d_x || !results || ncols < 1)
+    if (!object || !d_b || !d_x || !results || ncols < 1)
     {
-        setError("l3k_pcg_solve_cols: bad argument");
+        setError("%s: bad argument", who);
         return -1;
     }
-    const size_t n = size_t(mf->mesh->nOwnedDofs());
     if (ncols > 1 && (ldb < n || ldx < n))
     {
-        setError("l3k_pcg_solve_cols: leading dimension smaller than the number of owned dofs");
+        setError("%s: leading dimension smaller than the number of owned dofs", who);
         return -1;
     }
+    return 0;
+}
+int pcgSolveCols(const LinOp& A, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                 const l3k_cg_opts* opts, l3k_cg_result* results)
+{
     for (int c = 0; c < ncols; ++c)
-        if (int rc = l3k_pcg_solve(mf, d_b + ldb * c, d_x + ldx * c, d_minv, opts, results + c))
+        if (int rc = pcgSolve(A, d_b + ldb * c, d_x + ldx * c, d_minv, opts, results + c))
             return rc;
     return 0;
 }
+} // namespace
+extern "C" {
+int l3k_pcg_solve(l3k_mf* mf, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts,
+                  l3k_cg_result* result)
+{
+    if (!mf || !d_b || !d_x || !result)
+    {
+        setError("l3k_pcg_solve: null argument");
+        return -1;
+    }
+    if (int rc = singleRankOnly(mf, pcg_single_rank, "l3k_pcg_solve"))
+        return rc;
+    return pcgSolve(mfOp(mf), d_b, d_x, d_minv, opts, result);
+}
+int l3k_csr_pcg_solve(l3k_csr* A, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts,
+                      l3k_cg_result* result)
+{
+    if (!A || !d_b || !d_x || !result)
+    {
+        setError("l3k_csr_pcg_solve: null argument");
+        return -1;
+    }
+    return pcgSolve(csrOp(A), d_b, d_x, d_minv, opts, result);
+}
+int l3k_pcg_solve_cols(l3k_mf* mf, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                       const l3k_cg_opts* opts, l3k_cg_result* results)
+{
+    if (int rc = pcgCheckCols("l3k_pcg_solve_cols", mf, mf ? size_t(mf->mesh->nOwnedDofs()) : 0, d_b, ldb, d_x, ldx, ncols, results))
+        return rc;
+    if (int rc = singleRankOnly(mf, pcg_single_rank, "l3k_pcg_solve")) // (each column is an l3k_pcg_solve)
+        return rc;
+    return pcgSolveCols(mfOp(mf), d_b, ldb, d_x, ldx, ncols, d_minv, opts, results);
+}
+int l3k_csr_pcg_solve_cols(l3k_csr* A, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                           const l3k_cg_opts* opts, l3k_cg_result* results)
+{
+    if (int rc = pcgCheckCols("l3k_csr_pcg_solve_cols", A, A ? size_t(A->n) : 0, d_b, ldb, d_x, ldx, ncols, results))
+        return rc;
+    return pcgSolveCols(csrOp(A), d_b, ldb, d_x, ldx, ncols, d_minv, opts, results);
+}
 // ------------------------------------------------------------------------------------------------ Chebyshev-Jacobi
 } // extern "C"
-// the object behind l3k_cheb (include/l3k.h): coefficients, the caller's minv, and two vectors of its own -- x and y of the power
+// the object behind l3k_cheb (include/l3k.h): the operator it was created on, coefficients, the caller's minv, and two vectors of its own -- x and y of the power
 // method during creation, w and A z of l3k_cheb_apply afterwards
 struct l3k_cheb
 {
-    l3k_mf*               mf;
+    LinOp                 op; // the operator it was created on (mfOp or csrOp)
     const double*         minv;
     l3k_cheb_info         info;
     l3k::host::ChebCoeffs coef;
@@ -528,14 +530,13 @@ namespace
 // z <- p(D^-1 A) D^-1 r with the caller's w and az (n doubles each); d_s != nullptr: s[2] = <r, z> from the last kernel
 int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, double* d_s)
 {
-    l3k_ctx*     ctx = c->mf->ctx;
-    const int    d   = c->info.degree;
-    const size_t ld  = size_t(c->n);
+    l3k_ctx*  ctx = c->op.ctx;
+    const int d   = c->info.degree;
     if (int rc = l3k_cheb_first(ctx, r, c->minv, c->coef.c0, w, z, c->n, d == 1 ? d_s : nullptr))
         return rc;
     for (int k = 1; k < d; ++k)
     {
-        if (int rc = l3k_mf_apply(c->mf, z, ld, az, ld, 1, 1., 0.))
+        if (int rc = c->op.apply(z, az))
             return rc;
         if (int rc = l3k_cheb_step(ctx, r, az, c->minv, c->coef.a[k - 1], c->coef.b[k - 1], w, z, c->n, k == d - 1 ? d_s : nullptr))
             return rc;
@@ -584,31 +585,28 @@ int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, dou
     hipLaunchKernelGGL(cgUpdatePKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, ctx->stream, d_p, d_z, n, d_s);
     return launchShift(ctx, d_s); // (as in l3k_cg_update_px)
 }
-int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+} // extern "C"
+namespace
 {
-    if (!mf || !d_minv || !out)
-    {
-        setError("l3k_cheb_create: null argument");
-        return -1;
-    }
-    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_cheb_create"))
-        return rc;
+// l3k_cheb_create / l3k_csr_cheb_create (`who` in the messages): options, the power method on D^-1 A, the coefficients
+int chebCreate(const LinOp& A, const char* who, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
     const l3k_cheb_opts o = opts ? *opts : l3k_cheb_opts{1, 30., 10, 1.1, 0.};
     if (const char* why = l3k::host::chebCheckOpts(o.degree, &o.cond_est, o.max_power_iters, &o.boost_factor, &o.lambda_max))
     {
-        setError("l3k_cheb_create: %s", why);
+        setError("%s: %s", who, why);
         return -1;
     }
-    if (int rc = cgWorkspace(mf->ctx))
+    if (int rc = cgWorkspace(A.ctx))
         return rc;
     auto c  = std::make_unique< l3k_cheb >();
-    c->mf   = mf;
+    c->op   = A;
     c->minv = d_minv;
-    c->n    = mf->mesh->nOwnedDofs();
+    c->n    = A.n;
     c->ld   = (c->n + 3) / 4 * 4;
     if (int rc = c->work.alloc(size_t(2 * c->ld + 8)))
         return rc;
-    l3k_ctx*      ctx = mf->ctx;
+    l3k_ctx*      ctx = A.ctx;
     hipStream_t   st  = ctx->stream;
     const int64_t n   = c->n;
     double *      x = c->work.ptr, *y = x + c->ld, *s = y + c->ld;
@@ -622,7 +620,7 @@ int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts,
         {
             hipLaunchKernelGGL(powerScaleKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, st, x, y, n, s);
             L3K_HIP(hipGetLastError());
-            if (int rc = l3k_mf_apply(mf, x, size_t(n), y, size_t(n), 1, 1., 0.))
+            if (int rc = A.apply(x, y))
                 return rc;
             if (int rc = launchReduce(ctx, powerStepKernel, n, s, {0, 1}, y, d_minv, x))
                 return rc;
@@ -631,9 +629,9 @@ int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts,
         L3K_HIP(hipStreamSynchronize(st));
         if (!l3k::host::chebFinite(&est) || !(est > 0.))
         {
-            setError("l3k_cheb_create: the power method on D^-1 A gave the eigenvalue estimate %g after %d steps; it must be finite and "
+            setError("%s: the power method on D^-1 A gave the eigenvalue estimate %g after %d steps; it must be finite and "
                      "positive (is the operator positive definite, and minv its inverse diagonal with at least one non-zero row?)",
-                     est, steps);
+                     who, est, steps);
             return -1;
         }
     }
@@ -646,6 +644,28 @@ int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts,
     c->coef                  = l3k::host::chebCoeffs(c->info.lambda_max, c->info.lambda_min, o.degree);
     *out                     = c.release();
     return 0;
+}
+} // namespace
+extern "C" {
+int l3k_cheb_create(l3k_mf* mf, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!mf || !d_minv || !out)
+    {
+        setError("l3k_cheb_create: null argument");
+        return -1;
+    }
+    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_cheb_create"))
+        return rc;
+    return chebCreate(mfOp(mf), "l3k_cheb_create", d_minv, opts, out);
+}
+int l3k_csr_cheb_create(l3k_csr* A, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!A || !d_minv || !out)
+    {
+        setError("l3k_csr_cheb_create: null argument");
+        return -1;
+    }
+    return chebCreate(csrOp(A), "l3k_csr_cheb_create", d_minv, opts, out);
 }
 int l3k_cheb_info_get(const l3k_cheb* c, l3k_cheb_info* out)
 {
@@ -676,21 +696,19 @@ int l3k_cheb_destroy(l3k_cheb* c)
     delete c;
     return 0;
 }
-int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
+} // extern "C"
+namespace
 {
-    if (!mf || !d_b || !d_x || !c || !result)
+// the iteration of l3k_pcg_solve_cheb / l3k_csr_pcg_solve_cheb (include/l3k.h)
+int pcgSolveCheb(const LinOp& A, const char* who, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts,
+                 l3k_cg_result* result)
+{
+    if (c->op.object != A.object)
     {
-        setError("l3k_pcg_solve_cheb: null argument");
+        setError("%s: the preconditioner was created for another system", who);
         return -1;
     }
-    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_pcg_solve_cheb"))
-        return rc;
-    if (c->mf != mf)
-    {
-        setError("l3k_pcg_solve_cheb: the preconditioner was created for another system");
-        return -1;
-    }
-    l3k_ctx*         ctx = mf->ctx;
+    l3k_ctx*         ctx = A.ctx;
     const int64_t    n = c->n, ld = c->ld;
     DevBuf< double > work; // r | z | p | ap (A z inside the preconditioner) | w | s[8]
     if (int rc = work.alloc(size_t(5 * ld + 8)))
@@ -698,7 +716,7 @@ int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, 
     double *r = work.ptr, *z = r + ld, *p = z + ld, *ap = p + ld, *w = ap + ld, *s = w + ld;
     CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // r = b - A x0 (0 on the frozen rows), s[3] = <r, r>
-    if (int rc = l3k_mf_apply(mf, d_x, size_t(n), r, size_t(n), 1, 1., 0.))
+    if (int rc = A.apply(d_x, r))
         return rc;
     if (int rc = launchReduce(ctx, cgInitRKernel, n, s, {3}, r, d_b, c->minv))
         return rc;
@@ -715,7 +733,7 @@ int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, 
     }
     while (cg.running())
     {
-        if (int rc = l3k_mf_apply_energy(mf, p, ap, s)) // ap = A p, s[1] = <p, A p>
+        if (int rc = A.applyEnergy(p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
         if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, c->minv, n, s))
             return rc;
@@ -730,5 +748,27 @@ int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, 
     }
     cg.report(result);
     return 0;
+}
+} // namespace
+extern "C" {
+int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!mf || !d_b || !d_x || !c || !result)
+    {
+        setError("l3k_pcg_solve_cheb: null argument");
+        return -1;
+    }
+    if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_pcg_solve_cheb"))
+        return rc;
+    return pcgSolveCheb(mfOp(mf), "l3k_pcg_solve_cheb", d_b, d_x, c, opts, result);
+}
+int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!A || !d_b || !d_x || !c || !result)
+    {
+        setError("l3k_csr_pcg_solve_cheb: null argument");
+        return -1;
+    }
+    return pcgSolveCheb(csrOp(A), "l3k_csr_pcg_solve_cheb", d_b, d_x, c, opts, result);
 }
 } // extern "C"

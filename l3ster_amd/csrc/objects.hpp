@@ -252,6 +252,19 @@ struct l3k_mf
     }
 };
 
+// a square CSR matrix on the device (api_csr.hip): the caller's three arrays, validated once at creation, nothing copied
+struct l3k_csr
+{
+    l3k_ctx*        ctx;
+    int64_t         n;
+    const int64_t*  row_ptr;
+    const int32_t*  col_ind;
+    const double*   values;
+    int             lanes; // of a wave64 per row: 4, 16 or 64
+    l3k_csr_info    info;
+    DevBuf< unsigned long long > flag; // the word the checking kernels report through (validation, l3k_csr_dirichlet)
+};
+
 // a boundary equation kernel on a list of element sides (assembleProblem(kernel, boundary_ids) of the reference)
 struct l3k_bnd
 {

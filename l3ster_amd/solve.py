@@ -124,21 +124,32 @@ def _overlap(u, v, n):
     return abs(u.data_ptr() - v.data_ptr()) < 8 * n
 
 
+def _entry(system, name):
+    """(the entry point `name` for this kind of system, its number of rows): l3k_<name> for a MatrixFreeSystem,
+    l3k_csr_<name> for a system.CsrOperator -- the same loops inside the library on either operator"""
+    from . import capi
+    from .system import CsrOperator
+    if isinstance(system, CsrOperator):
+        return getattr(capi.load(), "l3k_csr_" + name), system.n
+    return getattr(capi.load(), "l3k_" + name), system.mesh.n_owned_dofs
+
+
 class ChebyshevPreconditioner:
-    """Handle of l3k_cheb_create: the matrix-free Chebyshev-Jacobi preconditioner of a single-rank MatrixFreeSystem
-    (options of Ifpack2ChebyshevOpts; its diag_threshold is jacobi_inverse's threshold).  `minv` (1-D device tensor
+    """Handle of l3k_cheb_create / l3k_csr_cheb_create: the Chebyshev-Jacobi preconditioner of a single-rank MatrixFreeSystem
+    or of a system.CsrOperator (options of Ifpack2ChebyshevOpts; its diag_threshold is jacobi_inverse's threshold).  `minv` (1-D device tensor
     over the owned dofs) and the system are kept alive here.  lambda_max=None: estimated by max_power_iters steps of the
     power method and multiplied by boost_factor."""
 
     def __init__(self, system, minv, degree=1, cond_est=30., max_power_iters=10, boost_factor=1.1, lambda_max=None):
         from . import capi
         self.system, self.minv = system, minv
-        if minv is None or minv.numel() != system.mesh.n_owned_dofs or not minv.is_contiguous():
+        create, self.n = _entry(system, "cheb_create")
+        if minv is None or minv.numel() != self.n or not minv.is_contiguous():
             raise capi.L3KError("minv must be a contiguous tensor over the owned dofs of the system")
         opts = capi.ChebOpts(int(degree), float(cond_est), int(max_power_iters), float(boost_factor),
                              0.0 if lambda_max is None else float(lambda_max))
         self._h = C.c_void_p()
-        capi.check(capi.load().l3k_cheb_create(system._h, C.c_void_p(minv.data_ptr()), C.byref(opts), C.byref(self._h)))
+        capi.check(create(system._h, C.c_void_p(minv.data_ptr()), C.byref(opts), C.byref(self._h)))
 
     @property
     def info(self):
@@ -153,7 +164,7 @@ class ChebyshevPreconditioner:
         """z <- p(D^-1 A) D^-1 r (l3k_cheb_apply); r, z: distinct 1-D device tensors over the owned dofs.  z goes through
         l3k_mf_apply, which refuses a vector that is not aligned as the system's kernel needs it."""
         from . import capi
-        n = self.system.mesh.n_owned_dofs
+        n = self.n
         if r.numel() != n or z.numel() != n or not (r.is_contiguous() and z.is_contiguous()):
             raise capi.L3KError("r and z must be contiguous tensors over the owned dofs of the system")
         if _overlap(r, z, n):  # (the first kernel writes z before the steps read r: the result would be silently wrong)
@@ -205,18 +216,18 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
         precond=None):
     """Jacobi-PCG entirely behind the C ABI (l3k_pcg_solve): apply, fused vector updates and reductions run on the
     context's stream, the host only reads 32 bytes per convergence check.  Single rank; `system` is a
-    l3ster_amd.system.MatrixFreeSystem, b / x / minv 1-D device tensors over its owned dofs.  `precond`: a
+    l3ster_amd.system.MatrixFreeSystem or a system.CsrOperator (an assembled or condensed matrix: l3k_csr_pcg_solve, the
+    same iteration on the CSR apply), b / x / minv 1-D device tensors over its owned dofs (the operator's rows).  `precond`: a
     ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb; a multivector b then solves
     its columns one after the other, as l3k_pcg_solve_cols does."""
     from . import capi
-    lib = capi.load()
     opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
     if precond is not None:
         if minv is not None:
             raise capi.L3KError("give minv or precond (which carries its own minv), not both")
         if precond.system is not system:
             raise capi.L3KError("the preconditioner was created for another system")
-        n = system.mesh.n_owned_dofs
+        solve_cheb, n = _entry(system, "pcg_solve_cheb")
         cols = [(b, x)] if b.dim() == 1 else list(zip(b, x))
         if x.shape != b.shape or any(bc.stride(0) != 1 or xc.stride(0) != 1 or bc.numel() != n for bc, xc in cols):
             raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")
@@ -224,7 +235,7 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
             raise capi.L3KError("b and x must not share memory")
         res_c = (capi.CgResult * len(cols))()
         for (bc, xc), res in zip(cols, res_c):
-            capi.check(lib.l3k_pcg_solve_cheb(system._h, _vp(bc), _vp(xc), precond._h, C.byref(opts), C.byref(res)))
+            capi.check(solve_cheb(system._h, _vp(bc), _vp(xc), precond._h, C.byref(opts), C.byref(res)))
         out = _from_c(res_c, throw_on_fail)
         return out[0] if b.dim() == 1 else out
     if b.dim() == 2:  # a multivector (ncols, ld) of right-hand sides: the columns one after the other (l3k_pcg_solve_cols)
@@ -232,11 +243,11 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
         if x.shape != b.shape or b.stride(1) != 1 or x.stride(1) != 1:
             raise capi.L3KError("b and x must be (ncols, ld) tensors of one shape with unit stride along rows")
         res_c = (capi.CgResult * nc)()
-        capi.check(lib.l3k_pcg_solve_cols(system._h, _vp(b), b.stride(0) if nc > 1 else b.shape[1], _vp(x),
+        capi.check(_entry(system, "pcg_solve_cols")[0](system._h, _vp(b), b.stride(0) if nc > 1 else b.shape[1], _vp(x),
                                           x.stride(0) if nc > 1 else x.shape[1], nc, _vp(minv), C.byref(opts), res_c))
         return _from_c(res_c, throw_on_fail)
     res = capi.CgResult()
-    capi.check(lib.l3k_pcg_solve(system._h, _vp(b), _vp(x), _vp(minv), C.byref(opts), C.byref(res)))
+    capi.check(_entry(system, "pcg_solve")[0](system._h, _vp(b), _vp(x), _vp(minv), C.byref(opts), C.byref(res)))
     return _from_c([res], throw_on_fail)[0]
 
 

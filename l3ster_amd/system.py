@@ -800,3 +800,87 @@ class MatrixFreeSystem:
     def new_ghost_buffer(self, ncols, like):
         import torch
         return torch.zeros((ncols, max(self.mesh.n_ghost_dofs, 1)), dtype=torch.float64, device=like.device)
+
+
+class CsrOperator:
+    """A square CSR matrix on the device in front of the solver (l3k_csr_create): row_ptr int64 [n + 1], col_ind int32 strictly
+    ascending within a row, values float64 -- the arrays assemble_global / condense_global fill.  Nothing is copied: the three
+    tensors are kept alive here, and `values` may be rewritten between calls (the graph may not).  Creation validates the graph
+    on the device and refuses one through which an apply could gather out of bounds.  n_owned_dofs = n, so solve.pcg and
+    solve.ChebyshevPreconditioner take it where they take a MatrixFreeSystem.  Applies and solves are bitwise reproducible on
+    any context.  lanes_per_row: 0 = chosen from the mean row length, else 4, 16 or 64."""
+
+    def __init__(self, ctx, row_ptr, col_ind, values, lanes_per_row=0):
+        import torch
+        if row_ptr.dtype != torch.int64 or col_ind.dtype != torch.int32 or values.dtype != torch.float64:
+            raise L3KError("CsrOperator: row_ptr is int64, col_ind int32 and values float64")
+        if row_ptr.dim() != 1 or row_ptr.numel() < 1 or not (row_ptr.is_contiguous() and col_ind.is_contiguous() and values.is_contiguous()):
+            raise L3KError("CsrOperator: row_ptr [n + 1], col_ind [nnz] and values [nnz] are contiguous 1-D tensors")
+        if col_ind.numel() != values.numel() or int(row_ptr[-1].item()) != col_ind.numel():
+            raise L3KError("CsrOperator: col_ind and values must have row_ptr[n] entries each")
+        self.ctx, self.row_ptr, self.col_ind, self.values = ctx, row_ptr, col_ind, values
+        self.n = self.n_owned_dofs = row_ptr.numel() - 1
+        self._h = C.c_void_p()
+        check(capi.load().l3k_csr_create(ctx._h, self.n, _ptr(row_ptr), _ptr(col_ind), _ptr(values), int(lanes_per_row),
+                                         C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and capi is not None:
+            capi.load().l3k_csr_destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """n, nnz, n_empty_rows, max_row_len, mean_row_len (of the non-empty rows), lanes_per_row (l3k_csr_info)"""
+        import types
+        i = capi.CsrInfo()
+        check(capi.load().l3k_csr_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.CsrInfo._fields_})
+
+    def apply(self, X, Y, alpha=1.0, beta=0.0):
+        """Y <- alpha A X + beta Y; X, Y: (ncols, ld) multivectors or 1-D vectors over the n rows (l3k_csr_apply)"""
+        if X.dim() == 1 and Y.dim() == 1:
+            X, Y2 = X[None, :], Y[None, :]
+        else:
+            Y2 = Y
+        nc, ldx = MatrixFreeSystem._cols(X)
+        nc2, ldy = MatrixFreeSystem._cols(Y2)
+        if nc != nc2 or X.shape[1] < self.n or Y2.shape[1] < self.n:
+            raise L3KError("X and Y must have the same number of columns and at least n rows")
+        check(capi.load().l3k_csr_apply(self._h, _ptr(X), ldx, _ptr(Y2), ldy, nc, alpha, beta))
+        return Y
+
+    def apply_energy(self, X, Y, S):
+        """Y <- A X (one column) and S[1] <- <X, A X> in one pass (l3k_csr_apply_energy): S is the PCG's scalar block (8 doubles)"""
+        if X.numel() != self.n or Y.numel() != self.n or S.numel() < 8 or not (X.is_contiguous() and Y.is_contiguous()):
+            raise L3KError("X and Y are contiguous vectors over the n rows, S has 8 entries")
+        check(capi.load().l3k_csr_apply_energy(self._h, _ptr(X), _ptr(Y), _ptr(S)))
+        return Y
+
+    def _diag(self, want_diag, want_minv, damping, threshold):
+        import torch
+        out = [torch.empty(self.n, dtype=torch.float64, device=self.values.device) if w else None for w in (want_diag, want_minv)]
+        check(capi.load().l3k_csr_diag(self._h, _ptr(out[0]), float(damping), float(threshold), _ptr(out[1])))
+        return out
+
+    def diag(self):
+        """The stored diagonal, 0 where a row has none (l3k_csr_diag)"""
+        return self._diag(True, False, 1.0, 0.0)[0]
+
+    def jacobi_inverse(self, damping=1.0, threshold=0.0):
+        """sign(a_ii) damping / max(|a_ii|, threshold) on the non-empty rows, 0 on the empty ones, which the PCG then leaves
+        alone (l3k_csr_diag)"""
+        return self._diag(False, True, damping, threshold)[1]
+
+    def dirichlet(self, mask, bc_vals, rhs):
+        """DirichletBCAlgebraic::apply in place (l3k_csr_dirichlet): mask uint8 [n]; bc_vals, rhs: (ncols, ld) or 1-D.  Rewrites
+        self.values and rhs; raises, with nothing changed, if a masked row stores no diagonal entry."""
+        import torch
+        if mask.dtype != torch.uint8 or mask.numel() != self.n or not mask.is_contiguous():
+            raise L3KError("mask must be a contiguous uint8 tensor over the n rows")
+        g, r = (bc_vals[None, :], rhs[None, :]) if rhs.dim() == 1 else (bc_vals, rhs)
+        nc, ldg = MatrixFreeSystem._cols(g)
+        nc2, ldr = MatrixFreeSystem._cols(r)
+        if nc != nc2 or g.shape[1] < self.n or r.shape[1] < self.n:
+            raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
+        check(capi.load().l3k_csr_dirichlet(self._h, _ptr(self.values), _ptr(mask), _ptr(g), ldg, _ptr(r), ldr, nc))
+        return rhs
