@@ -277,6 +277,7 @@ int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* en
     }
     return 0;
 }
+} // namespace
 const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols)
 {
     const auto* inst = l3k::dev::findInstance(mf->kernel_id, mf->mesh->order, mf->nq, ncols);
@@ -286,6 +287,8 @@ const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols)
                  mf->kernel_id, mf->mesh->order, mf->nq, ncols);
     return inst;
 }
+namespace
+{
 // How an apply of `ncols` columns is launched (l3k_mf_apply_elems launches the plan, l3k_mf_route describes it): through the
 // ncols-column instance; else, as the reference does when fewer columns than n_rhs are passed
 // (algsys/MatrixFreeSystem.hpp:1124-1138), through the single-column one -- for a dense dof layout all columns in one pass over
@@ -306,6 +309,55 @@ const l3k::dev::Instance* planColumns(const l3k_mf* mf, int ncols, ColumnPlan& p
     plan = inst && inst->apply_cols && mf->dense && !mf->ctx->deterministic && !mf->ctx->tune.column_by_column ? ColumnPlan::one_pass
                                                                                                             : ColumnPlan::per_column;
     return inst;
+}
+// LocalAssembly: mf->ws grown to the coefficient workspace of `count` elements; flag = its trailing double, which the assembly
+// kernels set on a degenerate element, cleared on the context's stream
+int assemblyWorkspace(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t count, double*& flag)
+{
+    const size_t need = inst->assemble_ws_doubles * size_t(count) + 1;
+    if (need > mf->ws_doubles)
+    {
+        if (mf->ws)
+            L3K_HIP(hipFree(mf->ws));
+        mf->ws = nullptr;
+        L3K_HIP(hipMalloc(reinterpret_cast< void** >(&mf->ws), need * sizeof(double)));
+        mf->ws_doubles = need;
+    }
+    flag = mf->ws + need - 1;
+    L3K_HIP(hipMemsetAsync(flag, 0, sizeof(double), mf->ctx->stream));
+    return 0;
+}
+// ... and the flag (or the two of a pipeline's halves) read back on s, which is synchronised: -2 if one is set.  The miss counter of
+// l3k_assemble_global rides on the same synchronisation
+int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_flag1 = nullptr, const unsigned long long* d_count = nullptr,
+                        int64_t* n_missing = nullptr)
+{
+    double             flags[2] = {0., 0.};
+    unsigned long long h        = 0;
+    L3K_HIP(hipMemcpyAsync(&flags[0], d_flag0, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (d_flag1)
+        L3K_HIP(hipMemcpyAsync(&flags[1], d_flag1, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (d_count)
+        L3K_HIP(hipMemcpyAsync(&h, d_count, sizeof h, hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipStreamSynchronize(s));
+    if (n_missing)
+        *n_missing = int64_t(h);
+    if (flags[0] != 0. || flags[1] != 0.)
+    {
+        setError("Encountered degenerate element ( |J| <= 0 )"); // algsys/AssembleLocalSystem.hpp:249
+        return -2;
+    }
+    return 0;
+}
+// F_e = sum_q w detJ B_q^T f_q into d_F: the sum-factorised RHS-mode kernel without Dirichlet lifting, element-local output
+void elementLocalRhs(l3k::dev::ElemArgs& a, double* d_F)
+{
+    a.dirichlet      = nullptr;
+    a.elem_flags     = nullptr;
+    a.dirichlet_vals = nullptr;
+    a.diag           = nullptr;
+    a.local_out      = 1;
+    a.y              = d_F; // unused for addressing in local_out mode, must be non-null
 }
 } // namespace
 
@@ -1478,7 +1530,7 @@ int l3k_mf_dirichlet_finalize(l3k_mf* mf, const double* d_dirichlet_vals, size_t
 }
 
 // K_e of [first, first + count) into d_K (row-major) through the tiled layout: sub-batches formed on the context's stream into one
-// of the system's two buffers, turned on the second stream (events order the reuse of the buffers, as in l3k_assemble_global)
+// of the system's two halves, turned on the second stream (runSubBatches, objects.hpp)
 static int assembleRowMajorViaTiled(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t first, int64_t count, double* d_K)
 {
     const l3k_mesh* m  = mf->mesh;
@@ -1494,75 +1546,38 @@ static int assembleRowMajorViaTiled(l3k_mf* mf, const l3k::dev::Instance* inst, 
     const size_t kd = size_t(nb) * mat, wd = inst->assemble_ws_doubles * size_t(nb) + 1;
     auto&        g  = mf->gasm;
     L3K_HIP(hipSetDevice(mf->ctx->device));
-    if (g.doubles < kd + wd)
-    {
-        for (int k = 0; k < 2; ++k)
-        {
-            if (g.buf[k])
-                L3K_HIP(hipFree(g.buf[k]));
-            g.buf[k] = nullptr;
-        }
-        g.doubles = 0;
-        for (int k = 0; k < 2; ++k)
-            L3K_HIP(hipMalloc(reinterpret_cast< void** >(&g.buf[k]), (kd + wd) * sizeof(double)));
-        g.doubles = kd + wd;
-    }
-    if (!g.second)
-    {
-        L3K_HIP(hipStreamCreateWithFlags(&g.second, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k)
-        {
-            L3K_HIP(hipEventCreateWithFlags(&g.formed[k], hipEventDisableTiming));
-            L3K_HIP(hipEventCreateWithFlags(&g.consumed[k], hipEventDisableTiming));
-        }
-    }
+    if (int rc = g.ensure(kd + wd, true))
+        return rc;
     hipStream_t sa   = mf->ctx->stream;
     const void* blob = mf->blob.empty() ? nullptr : mf->blob.data();
     // bitwise symmetric matrices, as the reference returns them: the x-major tiled layout and the one-pass mirroring transposition
     // (api_assembled.hip).  l3k_tuning::assemble_no_symmetrise: the plain tiled layout and the plain transposition (K[i][j] and
     // K[j][i] then differ by rounding) -- the cross-check of the former
     const bool sym = !mf->ctx->tune.assemble_no_symmetrise;
-    for (int k = 0; k < 2; ++k) // (the flags of degenerate elements: the trailing double of each coefficient workspace)
-        L3K_HIP(hipMemsetAsync(g.buf[k] + kd + inst->assemble_ws_doubles * size_t(nb), 0, sizeof(double), sa));
-    int64_t done  = 0;
-    int     n_sub = 0;
-    for (int i = 0; done < count; ++i, ++n_sub)
-    {
-        const int     k = i & 1;
-        const int64_t n = count - done < nb ? count - done : nb;
-        if (i >= 2)
-            L3K_HIP(hipStreamWaitEvent(sa, g.consumed[k], 0)); // the transposition of sub-batch i - 2 has read this buffer
-        l3k::dev::ElemArgs a;
-        if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
-            return rc;
-        a.elem_begin     = first + done;
-        a.elem_count     = n;
-        a.elem_begin_out = 0;
-        a.K              = g.buf[k];
-        a.K_tiled        = sym ? 2 : 1;
-        a.workspace      = g.buf[k] + kd + size_t(nb - n) * inst->assemble_ws_doubles; // (the flag keeps one position per buffer)
-        if (int rc = inst->assemble(a, blob, sa))
-            return rc;
-        L3K_HIP(hipEventRecord(g.formed[k], sa));
-        L3K_HIP(hipStreamWaitEvent(g.second, g.formed[k], 0));
-        if (int rc = sym ? launchTiledXToRowMajorSym(U, N1, n, g.buf[k], d_K + size_t(done) * mat, g.second)
-                         : launchTiledToRowMajor(U, N1, n, g.buf[k], d_K + size_t(done) * mat, g.second))
-            return rc;
-        L3K_HIP(hipEventRecord(g.consumed[k], g.second));
-        done += n;
-    }
-    for (int k = 0; k < 2 && k < n_sub; ++k)
-        L3K_HIP(hipStreamWaitEvent(sa, g.consumed[k], 0)); // later work on the context's stream sees the finished matrices
-    double flags[2] = {0., 0.};
+    // (the flags of degenerate elements: the trailing double of each half's coefficient workspace)
+    double* const flag[2] = {g.buf[0] + kd + wd - 1, g.buf[1] + kd + wd - 1};
     for (int k = 0; k < 2; ++k)
-        L3K_HIP(hipMemcpyAsync(&flags[k], g.buf[k] + kd + inst->assemble_ws_doubles * size_t(nb), sizeof(double), hipMemcpyDeviceToHost, sa));
-    L3K_HIP(hipStreamSynchronize(sa));
-    if (flags[0] != 0. || flags[1] != 0.)
-    {
-        setError("Encountered degenerate element ( |J| <= 0 )"); // algsys/AssembleLocalSystem.hpp:249
-        return -2;
-    }
-    return 0;
+        L3K_HIP(hipMemsetAsync(flag[k], 0, sizeof(double), sa));
+    if (int rc = runSubBatches(
+            g, sa, first, count, nb,
+            [&](int k, int64_t at, int64_t n) {
+                l3k::dev::ElemArgs a;
+                if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+                    return rc;
+                a.elem_begin     = at;
+                a.elem_count     = n;
+                a.elem_begin_out = 0;
+                a.K              = g.buf[k];
+                a.K_tiled        = sym ? 2 : 1;
+                a.workspace      = g.buf[k] + kd + size_t(nb - n) * inst->assemble_ws_doubles; // (the flag keeps one position per half)
+                return inst->assemble(a, blob, sa);
+            },
+            [&](int k, int64_t at, int64_t n) { // the transposition
+                double* out = d_K + size_t(at - first) * mat;
+                return sym ? launchTiledXToRowMajorSym(U, N1, n, g.buf[k], out, g.second) : launchTiledToRowMajor(U, N1, n, g.buf[k], out, g.second);
+            }))
+        return rc;
+    return readDegenerateFlags(sa, flag[0], flag[1]);
 }
 
 int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, double* d_F, double* d_checksum)
@@ -1575,11 +1590,8 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
     const l3k_mesh* m = mf->mesh;
     if (int rc = refuseQuads(m, "l3k_local_assemble"))
         return rc;
-    if (first < 0 || count < 0 || first + count > m->n_elems)
-    {
-        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
-        return -1;
-    }
+    if (int rc = checkRange(m, first, count))
+        return rc;
     if (count == 0)
         return 0;
     const auto* inst = instanceFor(mf, mf->n_rhs);
@@ -1612,40 +1624,20 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
     }
     if (a.K || d_checksum)
     {
-        const size_t need = inst->assemble_ws_doubles * size_t(count) + 1;
-        if (need > mf->ws_doubles)
-        {
-            if (mf->ws)
-                L3K_HIP(hipFree(mf->ws));
-            mf->ws = nullptr;
-            L3K_HIP(hipMalloc(reinterpret_cast< void** >(&mf->ws), need * sizeof(double)));
-            mf->ws_doubles = need;
-        }
+        double* flag = nullptr;
+        if (int rc = assemblyWorkspace(mf, inst, count, flag))
+            return rc;
         a.workspace = mf->ws;
-        double* flag = mf->ws + inst->assemble_ws_doubles * size_t(count);
-        L3K_HIP(hipMemsetAsync(flag, 0, sizeof(double), s));
         if (d_checksum)
             L3K_HIP(hipMemsetAsync(d_checksum, 0, sizeof(double) * size_t(count), s));
         if (int rc = inst->assemble(a, blob, s))
             return rc;
-        double degenerate = 0.;
-        L3K_HIP(hipMemcpyAsync(&degenerate, flag, sizeof(double), hipMemcpyDeviceToHost, s));
-        L3K_HIP(hipStreamSynchronize(s));
-        if (degenerate != 0.)
-        {
-            setError("Encountered degenerate element ( |J| <= 0 )"); // algsys/AssembleLocalSystem.hpp:249
-            return -2;
-        }
+        if (int rc = readDegenerateFlags(s, flag))
+            return rc;
     }
     if (d_F)
     {
-        // F_e = sum_q w detJ B_q^T f_q: the sum-factorised RHS-mode kernel without Dirichlet lifting, element-local output
-        a.dirichlet      = nullptr;
-        a.elem_flags     = nullptr;
-        a.dirichlet_vals = nullptr;
-        a.diag           = nullptr;
-        a.local_out      = 1;
-        a.y              = d_F; // unused for addressing in local_out mode, must be non-null
+        elementLocalRhs(a, d_F);
         if (int rc = inst->diag_rhs(a, blob, s))
             return rc;
     }
@@ -1662,11 +1654,8 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
     const l3k_mesh* m = mf->mesh;
     if (int rc = refuseQuads(m, "l3k_local_assemble_tiled"))
         return rc;
-    if (first < 0 || count < 0 || first + count > m->n_elems)
-    {
-        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
-        return -1;
-    }
+    if (int rc = checkRange(m, first, count))
+        return rc;
     if (count == 0)
         return 0;
     const auto* inst = instanceFor(mf, mf->n_rhs);
@@ -1685,35 +1674,19 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
     a.elem_begin_out = 0;
     a.K              = d_Kt;
     a.K_tiled        = 1;
-    hipStream_t  s    = mf->ctx->stream;
-    const size_t need = inst->assemble_ws_doubles * size_t(count) + 1;
-    if (need > mf->ws_doubles)
-    {
-        if (mf->ws)
-            L3K_HIP(hipFree(mf->ws));
-        mf->ws = nullptr;
-        L3K_HIP(hipMalloc(reinterpret_cast< void** >(&mf->ws), need * sizeof(double)));
-        mf->ws_doubles = need;
-    }
-    a.workspace  = mf->ws;
-    double* flag = mf->ws + inst->assemble_ws_doubles * size_t(count);
-    L3K_HIP(hipMemsetAsync(flag, 0, sizeof(double), s));
+    hipStream_t s    = mf->ctx->stream;
+    double*     flag = nullptr;
+    if (int rc = assemblyWorkspace(mf, inst, count, flag))
+        return rc;
+    a.workspace = mf->ws;
     if (int rc = inst->assemble(a, mf->blob.empty() ? nullptr : mf->blob.data(), s))
         return rc;
-    double degenerate = 0.;
-    L3K_HIP(hipMemcpyAsync(&degenerate, flag, sizeof(double), hipMemcpyDeviceToHost, s));
-    L3K_HIP(hipStreamSynchronize(s));
-    if (degenerate != 0.)
-    {
-        setError("Encountered degenerate element ( |J| <= 0 )"); // algsys/AssembleLocalSystem.hpp:249
-        return -2;
-    }
-    return 0;
+    return readDegenerateFlags(s, flag);
 }
 // assembleGlobalSystem (algsys/AssembleGlobalSystem.hpp:20-53: per element assembleLocalSystem -> scatterLocalSystem) for the
 // elements [first, first + count) as ONE call: sub-batches of element systems are formed into one of two workspace buffers on the
 // context's stream while the previous sub-batch is summed into the CSR values on a second stream -- the assembly kernels are
-// bound by the FP64 pipe, the scatter by the memory-side atomic units, so the two overlap (events order buffer reuse).
+// bound by the FP64 pipe, the scatter by the memory-side atomic units, so the two overlap (runSubBatches, objects.hpp).
 int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind,
                         double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes, int64_t* n_missing)
 {
@@ -1725,11 +1698,8 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
     const l3k_mesh* m = mf->mesh;
     if (int rc = refuseQuads(m, "l3k_assemble_global"))
         return rc;
-    if (first < 0 || count < 0 || first + count > m->n_elems)
-    {
-        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
-        return -1;
-    }
+    if (int rc = checkRange(m, first, count))
+        return rc;
     const int64_t n_local_dofs = (m->n_owned_nodes + m->n_ghost_nodes) * m->dofs_per_node;
     if (d_rhs && ldr < size_t(n_local_dofs))
     {
@@ -1760,107 +1730,47 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
         nb /= 2;
     const size_t kd = size_t(nb) * Nd * Nd, fd = d_rhs ? size_t(nb) * Nd * R : 0, wd = inst->assemble_ws_doubles * size_t(nb) + 1;
     auto&        g  = mf->gasm;
-    if (g.doubles < kd + fd + wd)
-    {
-        for (int k = 0; k < 2; ++k)
-        {
-            if (g.buf[k])
-                L3K_HIP(hipFree(g.buf[k]));
-            g.buf[k] = nullptr;
-        }
-        g.doubles = 0;
-        for (int k = 0; k < 2; ++k)
-            L3K_HIP(hipMalloc(reinterpret_cast< void** >(&g.buf[k]), (kd + fd + wd) * sizeof(double)));
-        g.doubles = kd + fd + wd;
-    }
-    if (!g.second)
-    {
-        L3K_HIP(hipStreamCreateWithFlags(&g.second, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k)
-        {
-            L3K_HIP(hipEventCreateWithFlags(&g.formed[k], hipEventDisableTiming));
-            L3K_HIP(hipEventCreateWithFlags(&g.consumed[k], hipEventDisableTiming));
-        }
-    }
-    struct Side
-    {
-        double *   K, *F, *ws;
-        hipEvent_t formed, consumed;
-    } side[2];
-    for (int k = 0; k < 2; ++k)
-        side[k] = Side{g.buf[k], g.buf[k] + kd, g.buf[k] + kd + fd, g.formed[k], g.consumed[k]};
-    struct
-    {
-        hipStream_t s;
-    } second{g.second};
+    if (int rc = g.ensure(kd + fd + wd, true))
+        return rc;
     hipStream_t         sa      = mf->ctx->stream;
     const void*         blob    = mf->blob.empty() ? nullptr : mf->blob.data();
     unsigned long long* d_count = n_missing ? mf->ctx->missCounter() : nullptr;
     if (d_count)
         L3K_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), sa));
-    // (the flags of degenerate elements: the trailing double of each coefficient workspace, set by the kernels, never cleared here)
-    for (auto& sd : side)
-        L3K_HIP(hipMemsetAsync(sd.ws + inst->assemble_ws_doubles * size_t(nb), 0, sizeof(double), sa));
-    int64_t done  = 0;
-    int     n_sub = 0;
-    for (int i = 0; done < count; ++i, ++n_sub)
-    {
-        Side&         sd = side[i & 1];
-        const int64_t n  = count - done < nb ? count - done : nb;
-        if (i >= 2)
-            L3K_HIP(hipStreamWaitEvent(sa, sd.consumed, 0)); // the scatter of sub-batch i - 2 has read this buffer
-        l3k::dev::ElemArgs a;
-        if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
-            return rc;
-        a.elem_begin     = first + done;
-        a.elem_count     = n;
-        a.elem_begin_out = 0;
-        a.K              = sd.K;
-        a.K_tiled        = tiled;
-        a.F              = d_rhs ? sd.F : nullptr;
-        a.checksum       = nullptr;
-        // (the kernels keep the degenerate-element flag behind the coefficients of THEIR elem_count elements: a short last
-        // sub-batch works in the tail of the buffer, so that the flag has one position per buffer)
-        a.workspace      = sd.ws + size_t(nb - n) * inst->assemble_ws_doubles;
-        if (int rc = inst->assemble(a, blob, sa))
-            return rc;
-        if (d_rhs)
-        {
-            L3K_HIP(hipMemsetAsync(sd.F, 0, sizeof(double) * size_t(n) * Nd * R, sa));
-            a.dirichlet      = nullptr;
-            a.elem_flags     = nullptr;
-            a.dirichlet_vals = nullptr;
-            a.diag           = nullptr;
-            a.local_out      = 1;
-            a.y              = sd.F;
-            if (int rc = inst->diag_rhs(a, blob, sa))
-                return rc;
-        }
-        L3K_HIP(hipEventRecord(sd.formed, sa));
-        L3K_HIP(hipStreamWaitEvent(second.s, sd.formed, 0));
-        if (int rc = launchAssembledScatter(mf, first + done, n, sd.K, d_rhs ? sd.F : nullptr, d_row_ptr, d_col_ind, d_values, d_rhs,
-                                            ldr, skip_dirichlet, d_count, second.s, tiled))
-            return rc;
-        L3K_HIP(hipEventRecord(sd.consumed, second.s));
-        done += n;
-    }
-    for (int k = 0; k < 2 && k < n_sub; ++k)
-        L3K_HIP(hipStreamWaitEvent(sa, side[k].consumed, 0)); // later work on the context's stream sees the finished values
-    double             flags[2] = {0., 0.};
-    unsigned long long h        = 0;
+    // (the flags of degenerate elements: the trailing double of each half's coefficient workspace, set by the kernels)
+    double* const flag[2] = {g.buf[0] + kd + fd + wd - 1, g.buf[1] + kd + fd + wd - 1};
     for (int k = 0; k < 2; ++k)
-        L3K_HIP(hipMemcpyAsync(&flags[k], side[k].ws + inst->assemble_ws_doubles * size_t(nb), sizeof(double), hipMemcpyDeviceToHost, sa));
-    if (d_count)
-        L3K_HIP(hipMemcpyAsync(&h, d_count, sizeof h, hipMemcpyDeviceToHost, sa));
-    L3K_HIP(hipStreamSynchronize(sa));
-    if (n_missing)
-        *n_missing = int64_t(h);
-    if (flags[0] != 0. || flags[1] != 0.)
-    {
-        setError("Encountered degenerate element ( |J| <= 0 )"); // algsys/AssembleLocalSystem.hpp:249
-        return -2;
-    }
-    return 0;
+        L3K_HIP(hipMemsetAsync(flag[k], 0, sizeof(double), sa));
+    if (int rc = runSubBatches(
+            g, sa, first, count, nb,
+            [&](int k, int64_t at, int64_t n) {
+                l3k::dev::ElemArgs a;
+                if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+                    return rc;
+                a.elem_begin     = at;
+                a.elem_count     = n;
+                a.elem_begin_out = 0;
+                a.K              = g.buf[k];
+                a.K_tiled        = tiled;
+                a.F              = d_rhs ? g.buf[k] + kd : nullptr;
+                a.checksum       = nullptr;
+                // (the kernels keep the degenerate-element flag behind the coefficients of THEIR elem_count elements: a short last
+                // sub-batch works in the tail of the half, so that the flag has one position per half)
+                a.workspace      = g.buf[k] + kd + fd + size_t(nb - n) * inst->assemble_ws_doubles;
+                if (int rc = inst->assemble(a, blob, sa))
+                    return rc;
+                if (!d_rhs)
+                    return 0;
+                L3K_HIP(hipMemsetAsync(a.F, 0, sizeof(double) * size_t(n) * Nd * R, sa));
+                elementLocalRhs(a, a.F);
+                return inst->diag_rhs(a, blob, sa);
+            },
+            [&](int k, int64_t at, int64_t n) {
+                return launchAssembledScatter(mf, at, n, g.buf[k], d_rhs ? g.buf[k] + kd : nullptr, d_row_ptr, d_col_ind, d_values, d_rhs, ldr,
+                                              skip_dirichlet, d_count, g.second, tiled);
+            }))
+        return rc;
+    return readDegenerateFlags(sa, flag[0], flag[1], d_count, n_missing);
 }
 // ------------------------------------------------------------------------------------------------ boundary terms
 int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kparam_blob, size_t kparam_bytes,

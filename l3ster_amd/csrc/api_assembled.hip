@@ -571,11 +571,8 @@ int l3k_assembled_scatter(l3k_mf* mf, int64_t first, int64_t count, const double
     const l3k_mesh* m = mf->mesh;
     if (int rc = refuseQuads(m, "l3k_assembled_scatter"))
         return rc;
-    if (first < 0 || count < 0 || first + count > m->n_elems)
-    {
-        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
-        return -1;
-    }
+    if (int rc = checkRange(m, first, count))
+        return rc;
     if ((d_K != nullptr) != (d_values != nullptr) || (d_K && (!d_row_ptr || !d_col_ind)))
     {
         setError("l3k_assembled_scatter: K needs values, row_ptr and col_ind (and the other way round)");

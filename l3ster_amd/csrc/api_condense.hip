@@ -131,23 +131,10 @@ struct CondShapeH // the host's view of CondShape
     }
 };
 
-int checkRange(const l3k_mesh* m, int64_t first, int64_t count)
-{
-    if (first < 0 || count < 0 || first + count > m->n_elems)
-    {
-        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
-        return -1;
-    }
-    return 0;
-}
 const l3k::dev::Instance* condInstance(const l3k_mf* mf, const char* what)
 {
-    const auto* inst = l3k::dev::findInstance(mf->kernel_id, mf->mesh->order, mf->nq, mf->n_rhs);
-    if (!inst)
-        setError("no device instantiation for kernel %d, order %d, nq %d, ncols %d: add it to L3K_FOR_EACH_INSTANCE "
-                 "(l3ster_amd/csrc/user_kernels.hpp) and rebuild",
-                 mf->kernel_id, mf->mesh->order, mf->nq, mf->n_rhs);
-    else if (!inst->condense)
+    const auto* inst = instanceFor(mf, mf->n_rhs);
+    if (inst && !inst->condense)
     {
         setError("%s: this shape has no condensation kernels", what);
         return nullptr;
@@ -169,34 +156,13 @@ int64_t subBatch(const CondShapeH& sh, int R, size_t bytes, int64_t count)
         nb /= 2;
     return nb;
 }
-// the system's condensation buffers: two halves of `doubles` (second stream and events on request)
+// the system's condensation buffers: two halves of `doubles` (second stream and events on request) and the pivot counter
 int ensureBufs(l3k_mf* mf, size_t doubles, bool two_streams)
 {
-    auto& g = mf->gcond;
-    if (g.doubles < doubles)
-    {
-        for (int k = 0; k < 2; ++k)
-        {
-            if (g.buf[k])
-                L3K_HIP(hipFree(g.buf[k]));
-            g.buf[k] = nullptr;
-        }
-        g.doubles = 0;
-        for (int k = 0; k < 2; ++k)
-            L3K_HIP(hipMalloc(reinterpret_cast< void** >(&g.buf[k]), doubles * sizeof(double)));
-        g.doubles = doubles;
-    }
-    if (!g.nfail)
-        L3K_HIP(hipMalloc(reinterpret_cast< void** >(&g.nfail), sizeof(unsigned)));
-    if (two_streams && !g.second)
-    {
-        L3K_HIP(hipStreamCreateWithFlags(&g.second, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k)
-        {
-            L3K_HIP(hipEventCreateWithFlags(&g.formed[k], hipEventDisableTiming));
-            L3K_HIP(hipEventCreateWithFlags(&g.consumed[k], hipEventDisableTiming));
-        }
-    }
+    if (int rc = mf->gcond.ensure(doubles, two_streams))
+        return rc;
+    if (!mf->cond_nfail)
+        L3K_HIP(hipMalloc(reinterpret_cast< void** >(&mf->cond_nfail), sizeof(unsigned)));
     return 0;
 }
 // the pieces of a half for nb elements
@@ -232,7 +198,7 @@ CondenseArgs condArgs(const l3k_mf* mf, const Half& h, int R, int64_t n)
     a.F     = h.F;
     a.Rd    = h.Rd;
     a.fail  = h.fail;
-    a.nfail = mf->gcond.nfail;
+    a.nfail = mf->cond_nfail;
     a.count = n;
     a.n_rhs = R;
     return a;
@@ -240,7 +206,7 @@ CondenseArgs condArgs(const l3k_mf* mf, const Half& h, int R, int64_t n)
 int readPivotFlag(l3k_mf* mf, hipStream_t s)
 {
     unsigned h = 0;
-    L3K_HIP(hipMemcpyAsync(&h, mf->gcond.nfail, sizeof h, hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipMemcpyAsync(&h, mf->cond_nfail, sizeof h, hipMemcpyDeviceToHost, s));
     L3K_HIP(hipStreamSynchronize(s));
     if (h)
     {
@@ -319,7 +285,7 @@ int l3k_condense_local(l3k_mf* mf, int64_t first, int64_t count, double* d_S, do
     if (int rc = ensureBufs(mf, nb * perElem(sh, R), false))
         return rc;
     hipStream_t s = mf->ctx->stream;
-    L3K_HIP(hipMemsetAsync(mf->gcond.nfail, 0, sizeof(unsigned), s));
+    L3K_HIP(hipMemsetAsync(mf->cond_nfail, 0, sizeof(unsigned), s));
     const Half h = halfOf(mf->gcond.buf[0], sh, R, nb);
     for (int64_t done = 0; done < count;)
     {
@@ -378,38 +344,27 @@ int l3k_condense_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
     unsigned long long* d_count = n_missing ? mf->ctx->missCounter() : nullptr;
     if (d_count)
         L3K_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), sa));
-    L3K_HIP(hipMemsetAsync(g.nfail, 0, sizeof(unsigned), sa));
-    int64_t done  = 0;
-    int     n_sub = 0, rc = 0;
-    for (int i = 0; done < count; ++i, ++n_sub)
-    {
-        const int     k = i & 1;
-        const int64_t n = count - done < nb ? count - done : nb;
-        const Half    h = halfOf(g.buf[k], sh, R, nb);
-        if (i >= 2)
-            L3K_HIP(hipStreamWaitEvent(sa, g.consumed[k], 0)); // the scatter of sub-batch i - 2 has read this half
-        if ((rc = formSystems(mf, h, sh, R, first + done, n)))
-            break; // (a degenerate element: -2 once the scatters in flight are done)
-        CondenseArgs a = condArgs(mf, h, R, n);
-        a.mirror       = 1;
-        if ((rc = inst->condense(a, sa)))
-            break;
-        L3K_HIP(hipEventRecord(g.formed[k], sa));
-        L3K_HIP(hipStreamWaitEvent(g.second, g.formed[k], 0));
-        if ((rc = launchCondensedScatter(mf, first + done, n, h, sh, d_row_ptr, d_col_ind, d_values, d_rhs, ldr, skip_dirichlet, d_count,
-                                         g.second)))
-            break;
-        L3K_HIP(hipEventRecord(g.consumed[k], g.second));
-        done += n;
-    }
-    for (int k = 0; k < 2 && k < n_sub; ++k)
-        L3K_HIP(hipStreamWaitEvent(sa, g.consumed[k], 0)); // later work on the context's stream sees the finished values
+    L3K_HIP(hipMemsetAsync(mf->cond_nfail, 0, sizeof(unsigned), sa));
+    // (a degenerate element ends the loop: -2 once the scatters in flight are done)
+    if (int rc = runSubBatches(
+            g, sa, first, count, nb,
+            [&](int k, int64_t at, int64_t n) {
+                const Half h = halfOf(g.buf[k], sh, R, nb);
+                if (int rc = formSystems(mf, h, sh, R, at, n))
+                    return rc;
+                CondenseArgs a = condArgs(mf, h, R, n);
+                a.mirror       = 1;
+                return inst->condense(a, sa);
+            },
+            [&](int k, int64_t at, int64_t n) {
+                return launchCondensedScatter(mf, at, n, halfOf(g.buf[k], sh, R, nb), sh, d_row_ptr, d_col_ind, d_values, d_rhs, ldr,
+                                              skip_dirichlet, d_count, g.second);
+            }))
+        return rc;
     unsigned long long hcount = 0;
     if (d_count)
         L3K_HIP(hipMemcpyAsync(&hcount, d_count, sizeof hcount, hipMemcpyDeviceToHost, sa));
     L3K_HIP(hipStreamSynchronize(sa));
-    if (rc)
-        return rc;
     if (n_missing)
         *n_missing = int64_t(hcount);
     return readPivotFlag(mf, sa);
@@ -445,7 +400,7 @@ int l3k_condensed_recover(l3k_mf* mf, int64_t first, int64_t count, double* d_x,
     if (int rc = ensureBufs(mf, nb * perElem(sh, R), false))
         return rc;
     hipStream_t s = mf->ctx->stream;
-    L3K_HIP(hipMemsetAsync(mf->gcond.nfail, 0, sizeof(unsigned), s));
+    L3K_HIP(hipMemsetAsync(mf->cond_nfail, 0, sizeof(unsigned), s));
     const Half h = halfOf(mf->gcond.buf[0], sh, R, nb);
     for (int64_t done = 0; done < count;)
     {

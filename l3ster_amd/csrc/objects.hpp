@@ -176,18 +176,30 @@ inline const char* quadsNote(const l3k_mesh* m)
 {
     return m->dim == 2 ? " (quads)" : "";
 }
+// ... and element ranges outside the mesh: -1
+inline int checkRange(const l3k_mesh* m, int64_t first, int64_t count)
+{
+    if (first < 0 || count < 0 || first + count > m->n_elems)
+    {
+        setError("element range [%lld, %lld) outside [0, %lld)", (long long)first, (long long)(first + count), (long long)m->n_elems);
+        return -1;
+    }
+    return 0;
+}
 struct l3k_bnd;
-// l3k_condense_local / l3k_condense_global / l3k_condensed_recover: two halves of element-system buffers (K_e, F_e, the factored
-// diagonal blocks and the pivot flags of a sub-batch), a second stream for the scatter and the events that order the reuse of the
-// halves; kept across calls, as l3k_mf::gasm
-struct CondenseBufs
+// The sub-batch pipeline of the assembled path (runSubBatches below): two halves of element-system buffers, a
+// second stream that consumes half i & 1 while the context's stream forms sub-batch i + 1 into the other, and the events that
+// order the reuse of the halves.  Kept across calls (allocating gigabytes per call cost more than the pipeline saved)
+struct SubBatchPipe
 {
     double*     buf[2]  = {nullptr, nullptr};
     size_t      doubles = 0; // per half
-    unsigned*   nfail   = nullptr; // device counter of elements with a non-positive pivot
     hipStream_t second  = nullptr;
     hipEvent_t  formed[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
-    ~CondenseBufs()
+    SubBatchPipe()                               = default;
+    SubBatchPipe(const SubBatchPipe&)            = delete;
+    SubBatchPipe& operator=(const SubBatchPipe&) = delete;
+    ~SubBatchPipe()
     {
         for (int k = 0; k < 2; ++k)
         {
@@ -198,10 +210,35 @@ struct CondenseBufs
             if (consumed[k])
                 (void)hipEventDestroy(consumed[k]);
         }
-        if (nfail)
-            (void)hipFree(nfail);
         if (second)
             (void)hipStreamDestroy(second);
+    }
+    // two halves of at least `need` doubles (both freed, then both allocated); the second stream and the events on first request
+    int ensure(size_t need, bool two_streams)
+    {
+        if (doubles < need)
+        {
+            for (int k = 0; k < 2; ++k)
+            {
+                if (buf[k])
+                    L3K_HIP(hipFree(buf[k]));
+                buf[k] = nullptr;
+            }
+            doubles = 0;
+            for (int k = 0; k < 2; ++k)
+                L3K_HIP(hipMalloc(reinterpret_cast< void** >(&buf[k]), need * sizeof(double)));
+            doubles = need;
+        }
+        if (two_streams && !second)
+        {
+            L3K_HIP(hipStreamCreateWithFlags(&second, hipStreamNonBlocking));
+            for (int k = 0; k < 2; ++k)
+            {
+                L3K_HIP(hipEventCreateWithFlags(&formed[k], hipEventDisableTiming));
+                L3K_HIP(hipEventCreateWithFlags(&consumed[k], hipEventDisableTiming));
+            }
+        }
+        return 0;
     }
 };
 struct l3k_mf
@@ -224,33 +261,60 @@ struct l3k_mf
     int                 energy_expected = 0;     // ... of how many non-empty ones: equal = fused, else the caller takes a dot product
     double*             ws = nullptr; // LocalAssembly workspace (grown on demand)
     size_t              ws_doubles = 0;
-    // l3k_assemble_global: two halves of element-system buffers, a second stream and the events that order their reuse; kept
-    // across calls (allocating gigabytes per call cost more than the pipeline saved)
-    struct GlobalAsm
-    {
-        double*     buf[2]      = {nullptr, nullptr};
-        size_t      doubles     = 0; // per half
-        hipStream_t second      = nullptr;
-        hipEvent_t  formed[2]   = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
-    } gasm;
-    CondenseBufs gcond;
+    // Two pipelines, not one, because they nest: l3k_condense_global forms its sub-batches through l3k_local_assemble, whose stored
+    // row-major route runs a whole pipeline on gasm (as l3k_assemble_global does) while the outer one is mid-flight on gcond
+    SubBatchPipe gasm, gcond;
+    unsigned*    cond_nfail = nullptr; // the condensation's device counter of elements with a non-positive pivot
     ~l3k_mf()
     {
         if (ws)
             (void)hipFree(ws);
-        for (int k = 0; k < 2; ++k)
-        {
-            if (gasm.buf[k])
-                (void)hipFree(gasm.buf[k]);
-            if (gasm.formed[k])
-                (void)hipEventDestroy(gasm.formed[k]);
-            if (gasm.consumed[k])
-                (void)hipEventDestroy(gasm.consumed[k]);
-        }
-        if (gasm.second)
-            (void)hipStreamDestroy(gasm.second);
+        if (cond_nfail)
+            (void)hipFree(cond_nfail);
     }
 };
+// Sub-batches of at most nb of the elements [first, first + count) through the pipe: form(k, at, n) enqueues on `main` (the
+// context's stream) what fills half k with the elements [at, at + n), consume(k, at, n) enqueues on p.second what reads it.  On
+// return `main` is ordered after everything consumed.  A non-zero return of either callable or a failing HIP call ends the loop;
+// the first error is the one returned, after both streams have drained: nothing queued can touch the halves or the caller's
+// arrays once this has returned, whatever the outcome.
+template < typename Form, typename Consume >
+int runSubBatches(SubBatchPipe& p, hipStream_t main, int64_t first, int64_t count, int64_t nb, Form&& form, Consume&& consume)
+{
+    const auto step = [&](int i, int64_t at, int64_t n) -> int {
+        const int k = i & 1;
+        if (i >= 2)
+            L3K_HIP(hipStreamWaitEvent(main, p.consumed[k], 0)); // the consumer of sub-batch i - 2 has read this half
+        if (int rc = form(k, at, n))
+            return rc;
+        L3K_HIP(hipEventRecord(p.formed[k], main));
+        L3K_HIP(hipStreamWaitEvent(p.second, p.formed[k], 0));
+        if (int rc = consume(k, at, n))
+            return rc;
+        L3K_HIP(hipEventRecord(p.consumed[k], p.second));
+        return 0;
+    };
+    const auto join = [&](int n_sub) -> int { // later work on the context's stream sees what the consumers wrote
+        for (int k = 0; k < 2 && k < n_sub; ++k)
+            L3K_HIP(hipStreamWaitEvent(main, p.consumed[k], 0));
+        return 0;
+    };
+    int rc = 0, i = 0;
+    for (int64_t done = 0; done < count && !rc; ++i)
+    {
+        const int64_t n = count - done < nb ? count - done : nb;
+        rc              = step(i, first + done, n);
+        done += n;
+    }
+    if (!rc)
+        rc = join(i);
+    if (rc)
+    {
+        (void)hipStreamSynchronize(p.second);
+        (void)hipStreamSynchronize(main);
+    }
+    return rc;
+}
 
 // a square CSR matrix on the device (api_csr.hip): the caller's three arrays, validated once at creation, nothing copied
 struct l3k_csr
@@ -301,6 +365,8 @@ struct KernelMeta
 const KernelMeta* findKernel(int id);
 const KernelMeta* findResidual(int id);
 } // namespace l3k::api
+// api.hip: the system's device instantiation for `ncols` columns, or nullptr with the error set (callers return -4)
+const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols);
 // api.hip: the refusals of an apply that its operands alone decide (fields set, number of columns, leading dimensions, alignment
 // of x, y and, where given, the ghost buffers): 0, or -1 with the error set.  The apply entry points call it before their first launch
 int checkApplyOperands(const l3k_mf* mf, int ncols, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, const double* d_y,

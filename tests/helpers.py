@@ -22,6 +22,17 @@ class SingleElementMesh:
         return self.n_owned_nodes
 
 
+def cube_with_inverted_element(ne=3, order=2, elem=20, perturb=0.15):
+    """A CubePartition whose element `elem` has its vertices 0 and 1 swapped: |J| <= 0 there, the degenerate-element error of
+    the assembly kernels, in the middle of an otherwise sound mesh."""
+    from l3ster_amd import system
+    part = system.CubePartition(ne, order, perturb=perturb)
+    verts = part.elem_verts.copy()
+    verts[elem, [0, 1]] = verts[elem, [1, 0]]
+    part.elem_verts = verts
+    return part
+
+
 def oracle_mesh(part, nq, dofs_per_node, field_inds, dirichlet=None, fields=None):
     return O.MeshView(3, part.order, nq, part.elem_nodes, part.elem_verts, part.n_local_nodes, dofs_per_node, field_inds,
                       dirichlet, fields)

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from helpers import HEX, SingleElementMesh, csr_graph
+from helpers import HEX, SingleElementMesh, csr_graph, cube_with_inverted_element
 from l3ster_amd import system
 
 torch = pytest.importorskip("torch")
@@ -401,3 +401,46 @@ def test_stored_row_major_routes_agree(ctx, kid, ne, p, vo, kpar):
     _, _, cs_stream = mf.local_assemble(1, part.n_elems - 1, want_K=False, want_F=False, want_checksum=True)
     assert torch.equal(Ks, K1[1:])
     np.testing.assert_allclose(cs.cpu().numpy(), cs_stream.cpu().numpy(), rtol=1e-12)  # (one atomic add per workgroup: order varies)
+
+
+def test_stored_row_major_after_a_degenerate_sub_batch(ctx):
+    """The sub-batch pipeline under l3k_local_assemble's stored route leaves nothing behind when a call fails: 27 elements in
+    sub-batches of 3 (which also selects the tiled route at order 2), element 20 -- sub-batch 6 -- degenerate.  The clean range
+    [0, 18) before and after the failing call, through the same two halves, gives the same bits."""
+    part = cube_with_inverted_element()
+    mf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, 4), system.KERNEL_DIFFUSION3D)
+    with ctx.tuning(assemble_sub_batch=3):
+        K0, _, _ = mf.local_assemble(0, 18, want_F=False)
+        with pytest.raises(system.L3KError, match="degenerate"):
+            mf.local_assemble(want_F=False)
+        K1, _, _ = mf.local_assemble(0, 18, want_F=False)
+    torch.cuda.synchronize()
+    assert torch.equal(K0, K1)
+
+
+def test_assemble_global_after_a_degenerate_sub_batch(ctx):
+    """The same for l3k_assemble_global, about three elements per half: the sums of [0, 18) before and after the failing call agree
+    to the rounding of the atomic adds (1e-12 of the largest value, as above), and no entry misses the graph."""
+    U, p, R = 4, 2, 1
+    part = cube_with_inverted_element()
+    mf = system.MatrixFreeSystem(system.DeviceMesh(ctx, part, U), system.KERNEL_DIFFUSION3D)
+    row_ptr, col_ind, n = csr_graph(part, U, np.arange(U))
+    RP, CI = torch.as_tensor(row_ptr, device="cuda"), torch.as_tensor(col_ind, device="cuda")
+    Nd = (p + 1) ** 3 * U
+    ws = 2 * 3 * 8 * (Nd * Nd + Nd * R + 8 * (p + 2) ** 3 * 128)
+
+    def run(count):
+        vals = torch.zeros(len(col_ind), dtype=torch.float64, device="cuda")
+        rhs = torch.zeros((R, n), dtype=torch.float64, device="cuda")
+        missing = mf.assemble_global(RP, CI, vals, rhs, first=0, count=count, workspace_bytes=ws)
+        torch.cuda.synchronize()
+        return vals, rhs, missing
+
+    v0, r0, m0 = run(18)
+    with pytest.raises(system.L3KError, match="degenerate"):
+        run(part.n_elems)
+    v1, r1, m1 = run(18)
+    assert m0 == 0 and m1 == 0
+    assert float(v0.abs().amax()) > 0
+    assert float((v1 - v0).abs().amax()) <= 1e-12 * float(v0.abs().amax())
+    assert float((r1 - r0).abs().amax()) <= 1e-12 * max(1.0, float(r0.abs().amax()))
