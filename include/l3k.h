@@ -65,6 +65,11 @@ int l3k_basis_1d(int p, int nq, double* I, double* D);
  * table; D = I * C for nq >= p+1) */
 int l3k_colloc_deriv(int nq, double* C);
 
+/* out[i][j] = l_j(x_i), row-major [p_to+1][p_from+1]: the order-p_from GLL Lagrange basis at the GLL nodes of order p_to, the 1-D
+ * factor of the tensor-product transfer between two orders on one element (l3k_pmg_* below).  The rows of the end nodes are exact
+ * unit vectors and p_from == p_to gives the exact identity.  Orders 1 .. 8. */
+int l3k_interp_1d(int p_from, int p_to, double* out);
+
 /* ---- kernel registry ------------------------------------------------------------------------------------------------
  * The reference takes the operator definition as a C++ callable wrapped by wrapDomainEquationKernel<params>
  * (common/KernelInterface.hpp:178-183) and instantiates the element loops on its type.  Here kernels are
@@ -434,6 +439,71 @@ int l3k_cheb_step(l3k_ctx* ctx, const double* d_r, const double* d_az, const dou
 int l3k_cg_update_rx(l3k_ctx* ctx, double* d_x, double* d_r, const double* d_p, const double* d_ap, const double* d_minv, int64_t n,
                      double* d_s);
 int l3k_cg_update_p(l3k_ctx* ctx, double* d_p, const double* d_z, int64_t n, double* d_s);
+
+/* ---- p-multigrid preconditioner, matrix-free -----------------------------------------------------------------------------
+ * The same elements rediscretised at strictly decreasing orders p_0 > p_1 > ... (level 0 = finest), the Chebyshev-Jacobi
+ * polynomial of l3k_cheb_create as the smoother of every level (Ifpack2ChebyshevPreconditioner, solve/Ifpack2Preconditioners.hpp:
+ * 26-36,107-131, stands next to it) and the tensor-product interpolation between the GLL node sets (l3k_interp_1d) as the
+ * transfer.  The reference has no multigrid of its own (it hands an assembled matrix to Ifpack2): like the matrix-free Chebyshev
+ * this exists because a matrix-free path has no matrix to hand to someone else's preconditioner.  Single rank.
+ *
+ * A level pair is a fine and a coarse mesh with the same elements: the same dim, n_elems, dofs_per_node and -- element by element --
+ * bitwise equal elem_verts; their own order, elem_nodes, node count and Dirichlet mask.  d_elem_map[e_fine] = e_coarse (device,
+ * kept by the object, the caller keeps it alive) pairs the elements, NULL = the same index.  Creation validates every pair on the
+ * device with one readback per pair (element map in range and a permutation, equal vertices) and refuses with -1 and a message
+ * naming the first offending fine element, so that no later call can transfer between two different elements.
+ *
+ * Ownership: owner[fine node] = the lowest fine element index that contains it (an integer atomicMin at creation).  The global
+ * prolongation P has one row per fine dof: the values of the coarse basis functions of the OWNING element at the node; all
+ * dofs_per_node components of a node move alike.  Rows of fine Dirichlet dofs and columns of coarse Dirichlet dofs are zero.
+ *   l3k_pmg_prolong:  x_f <- P x_c (add = 0) or x_f += P x_c (add != 0); coarse Dirichlet dofs are read as 0 (not loaded), fine
+ *                     Dirichlet dofs are written as 0 (add: left alone).  One writer per dof, plain stores, no floating-point
+ *                     atomics: bitwise reproducible on any context.
+ *   l3k_pmg_restrict: r_c <- P^T r_f, the exact transpose; r_c is zeroed by the call, fine Dirichlet dofs and the nodes an element
+ *                     does not own are not loaded, coarse Dirichlet dofs stay 0.  Accumulates with double atomics; on a context
+ *                     in deterministic mode (hierarchy and meshes created with the mode on) it launches colour by colour on the
+ *                     coarse mesh's colouring and is bitwise reproducible.
+ * coarse_level in [1, n_levels) names the pair (coarse_level - 1, coarse_level); vectors are the owned dofs of their level.
+ *
+ * l3k_pmg_apply: z <- M^-1 r, one symmetric V-cycle.  With S_l the level's smoother (z = S r is l3k_cheb_apply: zero initial guess):
+ *     cycle(l, r): z = S_l r;  last level: return z
+ *                  d = r - A_l z;  r_{l+1} = P^T d;  z += P cycle(l + 1, r_{l+1});  d = r - A_l z;  z += S_l d
+ * (the post-smoothing is the same polynomial, so M^-1 is symmetric).  On the last level the smoother is the coarse solve: a fixed
+ * polynomial, e.g. of a higher degree and cond_est.  Rows frozen by a level's smoother (minv == 0) behave as in
+ * l3k_pcg_solve_cheb: z = 0 there -- d is stored as 0 on them and the prolongation leaves them alone.  Dirichlet rows are identity
+ * rows of every A_l with diag = 1; the transfers do not touch them, so there M^-1 is the smoother's polynomial alone (pre- and
+ * post-smoothing of the row's own residual).  All vectors of all levels are allocated at creation.  Cost of a cycle on a level
+ * that is not the last: 2 (degree - 1) + 2 applies, the smoother's passes twice, and 4 + 4 + 3 vector passes of its own (d = r - Az
+ * with the mask twice, z += e once); on the last level degree - 1 applies.
+ *
+ * l3k_pcg_solve_pmg: the loop of l3k_pcg_solve_cheb with this cycle as the preconditioner (mf must be level 0's operator); options,
+ * result, frozen rows (level 0's smoother's minv), check_every and max_iters as there.  <r, z> takes a pass of its own behind the
+ * cycle (2 reads).
+ *
+ * Errors (-1): null arguments, n_levels outside 2 .. 8, levels on different contexts, a level with ghost nodes, a smoother created
+ * for another system than its level's mf, orders not strictly decreasing, a failed pair validation, r and z overlapping, a level
+ * index out of range, l3k_pcg_solve_pmg with an mf that is not level 0's. */
+typedef struct l3k_pmg l3k_pmg;
+typedef struct
+{
+    l3k_mf*        mf;         /* the operator of this level (level 0 = finest)                                              */
+    l3k_cheb*      smoother;   /* created by the caller on mf with l3k_cheb_create: degree, cond_est, lambda_max per level   */
+    const int64_t* d_elem_map; /* element of this level for each element of level - 1; NULL = identity; ignored on level 0   */
+} l3k_pmg_level;
+typedef struct
+{
+    int     n_levels;
+    int     order[8];             /* per level                                     */
+    int64_t n_dofs[8];
+    int     applies_per_cycle[8]; /* applies of A_l in one l3k_pmg_apply           */
+} l3k_pmg_info;
+int l3k_pmg_create(l3k_ctx* ctx, int n_levels, const l3k_pmg_level* levels, l3k_pmg** out);
+int l3k_pmg_info_get(const l3k_pmg* M, l3k_pmg_info* out);
+int l3k_pmg_prolong(l3k_pmg* M, int coarse_level, const double* d_xc, double* d_xf, int add);
+int l3k_pmg_restrict(l3k_pmg* M, int coarse_level, const double* d_rf, double* d_rc);
+int l3k_pmg_apply(l3k_pmg* M, const double* d_r, double* d_z); /* r and z must not overlap */
+int l3k_pmg_destroy(l3k_pmg* M);
+int l3k_pcg_solve_pmg(l3k_mf* mf, const double* d_b, double* d_x, l3k_pmg* M, const l3k_cg_opts* opts, l3k_cg_result* result);
 
 /* ---- device CSR operator: the assembled and the condensed system in front of the solver -----------------------------------
  * A square CSR matrix in the format l3k_assembled_scatter, l3k_assemble_global and l3k_condense_global fill: d_row_ptr int64

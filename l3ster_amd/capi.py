@@ -45,6 +45,15 @@ class ChebInfo(C.Structure):
                 ("power_iters", C.c_int), ("applies_per_call", C.c_int)]
 
 
+class PmgLevel(C.Structure):
+    """l3k_pmg_level: operator, smoother and element map (device int64, or NULL) of one p-multigrid level"""
+    _fields_ = [("mf", C.c_void_p), ("smoother", C.c_void_p), ("d_elem_map", C.c_void_p)]
+
+
+class PmgInfo(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("order", C.c_int * 8), ("n_dofs", C.c_int64 * 8), ("applies_per_cycle", C.c_int * 8)]
+
+
 class CsrInfo(C.Structure):
     """l3k_csr_info: what the validation pass of l3k_csr_create gathered"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
@@ -112,6 +121,7 @@ SIGNATURES = {
     "l3k_n_qps1d": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "l3k_basis_1d": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p]),
     "l3k_colloc_deriv": (C.c_int, [C.c_int, c_double_p]),
+    "l3k_interp_1d": (C.c_int, [C.c_int, C.c_int, c_double_p]),
     "l3k_kernel_info": (C.c_int, [C.c_int, C.POINTER(KParams), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]),
     "l3k_plugin_load": (C.c_int, [C.c_char_p]),
     "l3k_instance_count": (C.c_int, []),
@@ -201,6 +211,13 @@ SIGNATURES = {
     "l3k_cheb_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_rx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "l3k_cg_update_p": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "l3k_pmg_create": (C.c_int, [_vp, C.c_int, C.POINTER(PmgLevel), C.POINTER(_vp)]),
+    "l3k_pmg_info_get": (C.c_int, [_vp, C.POINTER(PmgInfo)]),
+    "l3k_pmg_prolong": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
+    "l3k_pmg_restrict": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "l3k_pmg_apply": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_pmg_destroy": (C.c_int, [_vp]),
+    "l3k_pcg_solve_pmg": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
     "l3k_csr_create": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "l3k_csr_info_get": (C.c_int, [_vp, C.POINTER(CsrInfo)]),
     "l3k_csr_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),

@@ -575,7 +575,8 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
         if (int rc = m.det_elem_flags.upload(fl.data(), fl.size(), s))
             return rc;
     L3K_HIP(hipStreamSynchronize(s)); // (the staging vectors are locals)
-    m.det_built = true;
+    m.det_colour = std::move(colour);
+    m.det_built  = true;
     return 0;
 }
 // the launch ranges of an element call: the caller's range as it is, or in deterministic mode the colours of the classes
@@ -660,6 +661,17 @@ int l3k_basis_1d(int p, int nq, double* I, double* D)
     l3k::host::basis1d(p, nq, Iv, Dv);
     std::copy(Iv.begin(), Iv.end(), I);
     std::copy(Dv.begin(), Dv.end(), D);
+    return 0;
+}
+int l3k_interp_1d(int p_from, int p_to, double* out)
+{
+    if (p_from < 1 || p_from > 8 || p_to < 1 || p_to > 8 || !out)
+    {
+        setError("l3k_interp_1d: orders must lie in 1 .. 8 and out must not be null");
+        return -1;
+    }
+    const auto v = l3k::host::interp1d(p_from, p_to);
+    std::copy(v.begin(), v.end(), out);
     return 0;
 }
 int l3k_colloc_deriv(int nq, double* C)

@@ -1,8 +1,7 @@
 // api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the single-rank drivers, written
 // once over the matrix-free operator and the device CSR operator (LinOp below).
 #include "reduce.hpp"
-
-#include "host/chebyshev.hpp"
+#include "solver.hpp"
 
 namespace
 {
@@ -333,24 +332,8 @@ struct CgDriver
         result->converged    = res <= o.tol;
     }
 };
-// The operator of a single-rank solve: n rows, y <- A x, and y <- A x with s[1] <- <x, A x>, on the context's stream.  The PCG
-// loops, the power method and the Chebyshev recurrence below are written ONCE over this value; mfOp and csrOp make it
-struct LinOp
-{
-    l3k_ctx* ctx;
-    int64_t  n;
-    void*    object; // the l3k_mf or l3k_csr behind it
-    int (*apply_fn)(void*, const double*, double*, size_t);
-    int (*energy_fn)(void*, const double*, double*, double*);
-    int apply(const double* d_x, double* d_y) const { return apply_fn(object, d_x, d_y, size_t(n)); }
-    int applyEnergy(const double* d_x, double* d_y, double* d_s) const { return energy_fn(object, d_x, d_y, d_s); }
-};
-LinOp mfOp(l3k_mf* mf)
-{
-    return {mf->ctx, mf->mesh->nOwnedDofs(), mf,
-            [](void* o, const double* x, double* y, size_t n) { return l3k_mf_apply(static_cast< l3k_mf* >(o), x, n, y, n, 1, 1., 0.); },
-            [](void* o, const double* x, double* y, double* s) { return l3k_mf_apply_energy(static_cast< l3k_mf* >(o), x, y, s); }};
-}
+using l3k::solver::LinOp;
+using l3k::solver::Precond;
 LinOp csrOp(l3k_csr* A)
 {
     return {A->ctx, A->n, A,
@@ -358,6 +341,17 @@ LinOp csrOp(l3k_csr* A)
             [](void* o, const double* x, double* y, double* s) { return l3k_csr_apply_energy(static_cast< l3k_csr* >(o), x, y, s); }};
 }
 } // namespace
+LinOp l3k::solver::mfOp(l3k_mf* mf)
+{
+    return {mf->ctx, mf->mesh->nOwnedDofs(), mf,
+            [](void* o, const double* x, double* y, size_t n) { return l3k_mf_apply(static_cast< l3k_mf* >(o), x, n, y, n, 1, 1., 0.); },
+            [](void* o, const double* x, double* y, double* s) { return l3k_mf_apply_energy(static_cast< l3k_mf* >(o), x, y, s); }};
+}
+using l3k::solver::mfOp;
+int l3k::solver::dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, double* d_s, int slot)
+{
+    return launchReduce(ctx, cgDotKernel, n, d_s, {slot}, d_u, d_v);
+}
 
 extern "C" {
 
@@ -514,21 +508,7 @@ int l3k_csr_pcg_solve_cols(l3k_csr* A, const double* d_b, size_t ldb, double* d_
 }
 // ------------------------------------------------------------------------------------------------ Chebyshev-Jacobi
 } // extern "C"
-// the object behind l3k_cheb (include/l3k.h): the operator it was created on, coefficients, the caller's minv, and two vectors of its own -- x and y of the power
-// method during creation, w and A z of l3k_cheb_apply afterwards
-struct l3k_cheb
-{
-    LinOp                 op; // the operator it was created on (mfOp or csrOp)
-    const double*         minv;
-    l3k_cheb_info         info;
-    l3k::host::ChebCoeffs coef;
-    DevBuf< double >      work; // w | az | s[8]
-    int64_t               n, ld; // owned dofs; distance between the vectors (a multiple of 4: the applies want aligned columns)
-};
-namespace
-{
-// z <- p(D^-1 A) D^-1 r with the caller's w and az (n doubles each); d_s != nullptr: s[2] = <r, z> from the last kernel
-int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, double* d_s)
+int l3k::solver::chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, double* d_s)
 {
     l3k_ctx*  ctx = c->op.ctx;
     const int d   = c->info.degree;
@@ -543,7 +523,7 @@ int chebApply(l3k_cheb* c, const double* r, double* z, double* w, double* az, do
     }
     return 0;
 }
-} // namespace
+using l3k::solver::chebApply;
 extern "C" {
 int l3k_cheb_first(l3k_ctx* ctx, const double* d_r, const double* d_minv, double c0, double* d_w, double* d_z, int64_t n, double* d_s)
 {
@@ -697,19 +677,17 @@ int l3k_cheb_destroy(l3k_cheb* c)
     return 0;
 }
 } // extern "C"
-namespace
+// the iteration of l3k_pcg_solve_cheb / l3k_csr_pcg_solve_cheb / l3k_pcg_solve_pmg (include/l3k.h)
+int l3k::solver::pcgSolvePrecond(const LinOp& A, const char* who, const double* d_b, double* d_x, const Precond& M,
+                                 const l3k_cg_opts* opts, l3k_cg_result* result)
 {
-// the iteration of l3k_pcg_solve_cheb / l3k_csr_pcg_solve_cheb (include/l3k.h)
-int pcgSolveCheb(const LinOp& A, const char* who, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts,
-                 l3k_cg_result* result)
-{
-    if (c->op.object != A.object)
+    if (M.system != A.object)
     {
         setError("%s: the preconditioner was created for another system", who);
         return -1;
     }
     l3k_ctx*         ctx = A.ctx;
-    const int64_t    n = c->n, ld = c->ld;
+    const int64_t    n = M.n, ld = M.ld;
     DevBuf< double > work; // r | z | p | ap (A z inside the preconditioner) | w | s[8]
     if (int rc = work.alloc(size_t(5 * ld + 8)))
         return rc;
@@ -718,14 +696,14 @@ int pcgSolveCheb(const LinOp& A, const char* who, const double* d_b, double* d_x
     // r = b - A x0 (0 on the frozen rows), s[3] = <r, r>
     if (int rc = A.apply(d_x, r))
         return rc;
-    if (int rc = launchReduce(ctx, cgInitRKernel, n, s, {3}, r, d_b, c->minv))
+    if (int rc = launchReduce(ctx, cgInitRKernel, n, s, {3}, r, d_b, M.mask))
         return rc;
     if (int rc = cg.start(d_b, n))
         return rc;
     if (cg.running())
     {
         // z = M^-1 r, s[2] = <r, z>; p = z; s[0] <- s[2]
-        if (int rc = chebApply(c, r, z, w, ap, s))
+        if (int rc = M.apply(r, z, w, ap, s))
             return rc;
         L3K_HIP(hipMemcpyAsync(p, z, size_t(n) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         if (int rc = launchShift(ctx, s))
@@ -735,19 +713,27 @@ int pcgSolveCheb(const LinOp& A, const char* who, const double* d_b, double* d_x
     {
         if (int rc = A.applyEnergy(p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
-        if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, c->minv, n, s))
+        if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, M.mask, n, s))
             return rc;
         if (int rc = cg.afterIteration())
             return rc;
         if (cg.res <= cg.o.tol || cg.it >= cg.o.max_iters) // (x is final: no preconditioner application for a direction nobody takes)
             break;
-        if (int rc = chebApply(c, r, z, w, ap, s)) // (ap is free until the next apply: it holds A z in here)
+        if (int rc = M.apply(r, z, w, ap, s)) // (ap is free until the next apply: it holds A z in here)
             return rc;
         if (int rc = l3k_cg_update_p(ctx, p, z, n, s))
             return rc;
     }
     cg.report(result);
     return 0;
+}
+namespace
+{
+// the Chebyshev object as the preconditioner of that loop
+Precond chebPrecond(l3k_cheb* c)
+{
+    return {c, c->op.object, c->minv, c->n, c->ld,
+            [](void* o, const double* r, double* z, double* w, double* az, double* s) { return chebApply(static_cast< l3k_cheb* >(o), r, z, w, az, s); }};
 }
 } // namespace
 extern "C" {
@@ -760,7 +746,7 @@ int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, 
     }
     if (int rc = singleRankOnly(mf, cheb_single_rank, "l3k_pcg_solve_cheb"))
         return rc;
-    return pcgSolveCheb(mfOp(mf), "l3k_pcg_solve_cheb", d_b, d_x, c, opts, result);
+    return l3k::solver::pcgSolvePrecond(mfOp(mf), "l3k_pcg_solve_cheb", d_b, d_x, chebPrecond(c), opts, result);
 }
 int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
 {
@@ -769,6 +755,6 @@ int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb*
         setError("l3k_csr_pcg_solve_cheb: null argument");
         return -1;
     }
-    return pcgSolveCheb(csrOp(A), "l3k_csr_pcg_solve_cheb", d_b, d_x, c, opts, result);
+    return l3k::solver::pcgSolvePrecond(csrOp(A), "l3k_csr_pcg_solve_cheb", d_b, d_x, chebPrecond(c), opts, result);
 }
 } // extern "C"

@@ -132,6 +132,23 @@ void basis1d(int p, int nq, std::vector< double >& I, std::vector< double >& D)
     }
 }
 
+std::vector< double > interp1d(int p_from, int p_to)
+{
+    const int             nf = p_from + 1, nt = p_to + 1;
+    const auto            from = gllNodes(nf), to = gllNodes(nt);
+    std::vector< double > out(size_t(nt) * nf, 0.);
+    if (p_from == p_to)
+    {
+        for (int i = 0; i < nt; ++i)
+            out[size_t(i) * nf + i] = 1.;
+        return out;
+    }
+    for (int i = 1; i + 1 < nt; ++i)
+        lagrange(from, to[i], out.data() + size_t(i) * nf, nullptr);
+    out[0] = out[size_t(nt) * nf - 1] = 1.; // xi = -1 and xi = +1 are nodes of every order: exact unit rows
+    return out;
+}
+
 std::vector< double > collocDeriv(int nq)
 {
     std::vector< double > qx, qw, v(nq), d(nq), C(size_t(nq) * nq);

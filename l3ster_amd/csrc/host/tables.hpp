@@ -13,6 +13,9 @@ void glRule(int nq, std::vector< double >& x, std::vector< double >& w);
 void lagrange(const std::vector< double >& nodes, double x, double* vals, double* ders);
 // I[b][q] = phi_b(x_q), D[b][q] = phi_b'(x_q), row-major (p+1) x nq (algsys/SumFactorization.hpp:25-65)
 void basis1d(int p, int nq, std::vector< double >& I, std::vector< double >& D);
+// out[i][j] = l_j(x_i): the order-p_from GLL Lagrange basis at the GLL nodes of order p_to, row-major (p_to+1) x (p_from+1); the
+// two end rows are exact unit vectors, equal orders give the exact identity (the transfer of the p-multigrid levels)
+std::vector< double > interp1d(int p_from, int p_to);
 // collocation derivative on the Gauss points: C[q'][q] = l_q''(x_q) for the Lagrange basis l on the nq Gauss points
 std::vector< double > collocDeriv(int nq);
 void evenOddTables(const std::vector< double >& W, int nin, int nout, bool anti, std::vector< double >& We,

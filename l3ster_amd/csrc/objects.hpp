@@ -155,6 +155,7 @@ struct l3k_mesh
     DevBuf< double >       det_elem_verts;
     DevBuf< uint8_t >      det_elem_flags;
     std::vector< int64_t > det_ptr[2];
+    std::vector< uint8_t >  det_colour; // host, [n_elems] in the ORIGINAL element order: the colour of each element
     std::vector< uint32_t > det_corner_nodes; // host, [n_elems][2^dim] in the ORIGINAL element order: colouring of boundary sides
     int64_t nOwnedDofs() const { return n_owned_nodes * dofs_per_node; }
     int64_t nLocalDofs() const { return (n_owned_nodes + n_ghost_nodes) * dofs_per_node; }

@@ -524,6 +524,7 @@ struct Diffusion2DVar
     X(::l3k::kernels::Diffusion3DVar, 3, 7, 1)                                                                         \
     X(::l3k::kernels::Diffusion3DVar, 3, 7, 2)                                                                         \
     X(::l3k::kernels::Diffusion3DVar, 4, 5, 1)                                                                         \
+    X(::l3k::kernels::AdvDiff3D, 1, 2, 1)                                                                              \
     X(::l3k::kernels::AdvDiff3D, 2, 3, 1)                                                                              \
     X(::l3k::kernels::AdvDiff3D, 2, 3, 2)                                                                              \
     X(::l3k::kernels::AdvDiff3D, 4, 5, 1)                                                                              \

@@ -185,6 +185,88 @@ class ChebyshevPreconditioner:
             pass
 
 
+class PMultigrid:
+    """Handle of l3k_pmg_create: the p-multigrid preconditioner of a single-rank MatrixFreeSystem (include/l3k.h).  `levels`, finest
+    first: (MatrixFreeSystem, ChebyshevPreconditioner created on it, elem_map or None) -- the same elements at strictly decreasing
+    orders; elem_map (int64, host or device; system.match_elements makes it) names the element of this level for each element of
+    the level before and is ignored on the first level.  The systems, smoothers and maps are kept alive here."""
+
+    def __init__(self, levels):
+        from . import capi
+        levels = [tuple(l) + (None,) * (3 - len(l)) for l in levels]
+        if len(levels) < 2:
+            raise capi.L3KError(f"PMultigrid needs at least two levels, got {len(levels)}")
+        self.levels = levels
+        self.system = levels[0][0]
+        dev = levels[0][1].minv.device
+        self._maps = [None if m is None or i == 0 else torch.as_tensor(m, dtype=torch.int64).to(dev).contiguous()
+                      for i, (_, _, m) in enumerate(levels)]
+        arr = (capi.PmgLevel * len(levels))()
+        for a, (sys_l, cheb, _), m in zip(arr, levels, self._maps):
+            a.mf, a.smoother, a.d_elem_map = sys_l._h, cheb._h, None if m is None else m.data_ptr()
+        self._h = C.c_void_p()
+        capi.check(capi.load().l3k_pmg_create(self.system.mesh.ctx._h, len(levels), arr, C.byref(self._h)))
+
+    def info(self):
+        """n_levels and per level order, n_dofs, applies_per_cycle (l3k_pmg_info)"""
+        import types
+        from . import capi
+        i = capi.PmgInfo()
+        capi.check(capi.load().l3k_pmg_info_get(self._h, C.byref(i)))
+        n = i.n_levels
+        return types.SimpleNamespace(n_levels=n, order=list(i.order[:n]), n_dofs=list(i.n_dofs[:n]),
+                                     applies_per_cycle=list(i.applies_per_cycle[:n]))
+
+    def _vec(self, t, level, name):
+        from . import capi
+        n = self.levels[level][0].mesh.n_owned_dofs
+        if t.numel() != n or not t.is_contiguous():
+            raise capi.L3KError(f"{name} must be a contiguous tensor over the {n} owned dofs of level {level}")
+        return C.c_void_p(t.data_ptr())
+
+    def _level(self, coarse_level):
+        from . import capi
+        if not 1 <= coarse_level < len(self.levels):
+            raise capi.L3KError(f"coarse_level {coarse_level} outside [1, {len(self.levels)})")
+
+    def prolong(self, coarse_level, xc, xf, add=False):
+        """xf <- P xc, or xf += P xc, between the levels coarse_level and coarse_level - 1 (l3k_pmg_prolong)"""
+        from . import capi
+        self._level(coarse_level)
+        capi.check(capi.load().l3k_pmg_prolong(self._h, coarse_level, self._vec(xc, coarse_level, "xc"),
+                                               self._vec(xf, coarse_level - 1, "xf"), int(bool(add))))
+        return xf
+
+    def restrict(self, coarse_level, rf, rc):
+        """rc <- P^T rf (l3k_pmg_restrict)"""
+        from . import capi
+        self._level(coarse_level)
+        capi.check(capi.load().l3k_pmg_restrict(self._h, coarse_level, self._vec(rf, coarse_level - 1, "rf"),
+                                                self._vec(rc, coarse_level, "rc")))
+        return rc
+
+    def apply(self, r, z):
+        """z <- M^-1 r, one symmetric V-cycle (l3k_pmg_apply); r, z: distinct vectors of level 0"""
+        from . import capi
+        pr, pz = self._vec(r, 0, "r"), self._vec(z, 0, "z")
+        if _overlap(r, z, r.numel()):
+            raise capi.L3KError("r and z must be distinct vectors that do not overlap")
+        capi.check(capi.load().l3k_pmg_apply(self._h, pr, pz))
+        return z
+
+    def close(self):
+        if getattr(self, "_h", None):
+            from . import capi
+            capi.load().l3k_pmg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+
 def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
     """NativeJacobiImpl::init through the C ABI (l3k_jacobi_inverse)."""
     from . import capi
@@ -218,8 +300,9 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
     context's stream, the host only reads 32 bytes per convergence check.  Single rank; `system` is a
     l3ster_amd.system.MatrixFreeSystem or a system.CsrOperator (an assembled or condensed matrix: l3k_csr_pcg_solve, the
     same iteration on the CSR apply), b / x / minv 1-D device tensors over its owned dofs (the operator's rows).  `precond`: a
-    ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb; a multivector b then solves
-    its columns one after the other, as l3k_pcg_solve_cols does."""
+    ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb, or a PMultigrid whose finest
+    level is this MatrixFreeSystem (one V-cycle per iteration; rows frozen by its finest smoother keep x) -> l3k_pcg_solve_pmg;
+    a multivector b then solves its columns one after the other, as l3k_pcg_solve_cols does."""
     from . import capi
     opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
     if precond is not None:
@@ -227,7 +310,7 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
             raise capi.L3KError("give minv or precond (which carries its own minv), not both")
         if precond.system is not system:
             raise capi.L3KError("the preconditioner was created for another system")
-        solve_cheb, n = _entry(system, "pcg_solve_cheb")
+        solve_cheb, n = _entry(system, "pcg_solve_pmg" if isinstance(precond, PMultigrid) else "pcg_solve_cheb")
         cols = [(b, x)] if b.dim() == 1 else list(zip(b, x))
         if x.shape != b.shape or any(bc.stride(0) != 1 or xc.stride(0) != 1 or bc.numel() != n for bc, xc in cols):
             raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")

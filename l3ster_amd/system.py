@@ -70,6 +70,38 @@ def colloc_deriv(nq):
     return Cm
 
 
+def interp_1d(p_from, p_to):
+    """[p_to + 1][p_from + 1]: the order-p_from GLL Lagrange basis at the GLL nodes of order p_to (l3k_interp_1d), the 1-D factor
+    of the transfer between two orders of one element."""
+    T = np.zeros((p_to + 1, p_from + 1))
+    check(capi.load().l3k_interp_1d(int(p_from), int(p_to), T.ctypes.data_as(capi.c_double_p)))
+    return T
+
+
+def match_elements(fine_part, coarse_part):
+    """elem_map[e_fine] = e_coarse (int64) for two partitions of ONE mesh at two orders, paired by their elem_verts rows (bitwise),
+    or None when the pairing is the identity: what l3k_pmg_level.d_elem_map takes.  CubePartition traverses its elements in bricks
+    whose edge depends on the order, so CubePartition(ne, p, perturb=...) at two orders lists the same elements in different
+    sequences once the mesh is larger than a brick; the perturbation itself depends on the mesh spacing only, not on the order,
+    so the vertices agree bit for bit.  Raises L3KError if some element has no partner (two different meshes); levels can then
+    be built from one order-1 connectivity with elevate_order / ElevatedHexMesh instead, which keeps the element order."""
+    vf = np.ascontiguousarray(fine_part.elem_verts, dtype=np.float64)
+    vc = np.ascontiguousarray(coarse_part.elem_verts, dtype=np.float64)
+    if vf.shape != vc.shape:
+        raise L3KError(f"match_elements: the partitions hold {vf.shape[0]} and {vc.shape[0]} elements of {vf.shape[1:]} / {vc.shape[1:]} vertices")
+    where = {}
+    for e in range(vc.shape[0]):
+        if where.setdefault(vc[e].tobytes(), e) != e:
+            raise L3KError(f"match_elements: coarse elements {where[vc[e].tobytes()]} and {e} have the same vertices")
+    out = np.empty(vf.shape[0], dtype=np.int64)
+    for e in range(vf.shape[0]):
+        ec = where.get(vf[e].tobytes())
+        if ec is None:
+            raise L3KError(f"match_elements: fine element {e} has no coarse element with the same vertices")
+        out[e] = ec
+    return None if np.array_equal(out, np.arange(out.size)) else out
+
+
 def kernel_info(kernel_id):
     kp, name, nbytes = capi.KParams(), C.c_char_p(), C.c_size_t()
     check(capi.load().l3k_kernel_info(kernel_id, C.byref(kp), C.byref(name), C.byref(nbytes)))
