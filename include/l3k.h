@@ -567,6 +567,50 @@ int l3k_csr_pcg_solve_cols(l3k_csr* A, const double* d_b, size_t ldb, double* d_
 int l3k_csr_cheb_create(l3k_csr* A, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
 int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result);
 
+/* ---- CSR sparsity graph of a mesh, built on the device -------------------------------------------------------------------
+ * computeLocalGraph of the reference (algsys/SparsityGraph.hpp:26-81: rows over-allocated, filled with duplicates, then sorted
+ * and de-duplicated) in front of makeSparsityGraph (:299), for one rank: the d_row_ptr / d_col_ind that l3k_assembled_scatter,
+ * l3k_assemble_global, l3k_condense_global and l3k_csr_create take.  Rows and columns are the rank-local dofs of
+ * l3k_assembled_scatter: n = (n_owned_nodes + n_ghost_nodes) * dofs_per_node, dof = node * dofs_per_node + field_inds[u].  The
+ * rows a rank receives from its neighbours (serializeSharedGraph, computeInNbrData, :83-212) are not part of it.
+ *
+ * L3K_GRAPH_FULL: dof (a, f) is coupled with dof (b, f') iff f and f' are in field_inds and some element of the mesh contains
+ *   both node a and node b; the rows of the dofs outside field_inds are empty.  Hexes and quads.
+ * L3K_GRAPH_CONDENSED: the same rule over the primary nodes of each element only (any of ix, iy, iz equal to 0 or p,
+ *   mesh/ElementTraits.hpp:37-59): the graph of the condensed system; the rows of element-internal dofs are empty.  Hexes only
+ *   (a quad mesh: -1).
+ * Several domain kernels with different dof sets: pass the union of their field_inds (a superset graph serves every consumer).
+ *
+ * Output: d_row_ptr int64 [n + 1], d_col_ind int32 [nnz], columns strictly ascending within a row -- what l3k_csr_create
+ * validates and the scatter kernels search.  The result is a sorted set: the same bit for bit on every run and on any context,
+ * whatever order the integer atomics of the builder land in.
+ *
+ * field_inds: n_fields indices, strictly ascending and inside [0, dofs_per_node), else -1; NULL with n_fields = 0: all dofs of
+ *   the node.  Also -1: a null mesh or out, any other kind, n >= 2^31 (as l3k_csr_create).  A mesh without elements gives nnz = 0.
+ * l3k_graph_create: everything except the caller's arrays -- the node -> element table, the number of coupled nodes of every
+ *   node (one workgroup per node sorts and de-duplicates the node ids of its elements, in the LDS where they fit), the row
+ *   offsets.  One readback (nnz, max_row_len, n_rows_scratch, max_elems_per_node), which synchronises the context's stream; a
+ *   mesh with a node whose key list (elements at the node times selected nodes per element) exceeds lds_key_capacity takes a
+ *   second one, after those nodes have been counted on slices of a global buffer sized by the largest list.
+ *   The object holds memory that grows with the nodes and with n_elems * (selected nodes per element), never with the node
+ *   pairs or with nnz; the mesh must outlive it.
+ * l3k_graph_info_get: the statistics of the readback.
+ * l3k_graph_fill: writes both arrays on the context's stream (no synchronisation); may be called more than once.  d_col_ind may
+ *   be NULL iff nnz == 0; a null d_row_ptr: -1.                                                                               */
+typedef struct l3k_graph l3k_graph;
+enum { L3K_GRAPH_FULL = 0, L3K_GRAPH_CONDENSED = 1 };
+typedef struct
+{
+    int64_t n, nnz, n_empty_rows, max_row_len; /* dof level, as l3k_csr_info counts them            */
+    int64_t n_rows_scratch;                    /* row NODES whose key list did not fit the LDS      */
+    int64_t workspace_bytes;                   /* device memory the object itself holds             */
+    int     max_elems_per_node, lds_key_capacity;
+} l3k_graph_info;
+int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int kind, l3k_graph** out);
+int l3k_graph_info_get(const l3k_graph* g, l3k_graph_info* out);
+int l3k_graph_fill(l3k_graph* g, int64_t* d_row_ptr, int32_t* d_col_ind);
+int l3k_graph_destroy(l3k_graph* g);
+
 /* ---- LocalAssembly --------------------------------------------------------------------------------------------------
  * assembleLocalSystem for a batch of elements, algsys/AssembleLocalSystem.hpp:234-256: K_e row-major [Nd][Nd],
  * F_e column-major [Nd][n_rhs] per element, elements [first, first+count).  d_K may be NULL (then only the checksum

@@ -485,6 +485,35 @@ private:
     double*  m_values{};
 };
 
+// The CSR sparsity graph of a mesh over its local dofs, built on the device: computeLocalGraph in front of makeSparsityGraph
+// (algsys/SparsityGraph.hpp:26-81, :299) for one rank.  field_inds strictly ascending, empty = all dofs of the node; kind
+// L3K_GRAPH_FULL or L3K_GRAPH_CONDENSED (primary nodes only, hexes).  The mesh must outlive the object.
+//   info   ~ n, nnz, n_empty_rows, max_row_len, n_rows_scratch, workspace_bytes, max_elems_per_node, lds_key_capacity
+//   fill   ~ d_row_ptr int64 [n + 1], d_col_ind int32 [nnz] (columns ascending): what assembleGlobal / condenseGlobal and
+//            CsrOperator take; may be called more than once
+class Graph
+{
+public:
+    Graph(const DeviceMesh& mesh, std::span< const int > field_inds = {}, int kind = L3K_GRAPH_FULL)
+    {
+        check(l3k_graph_create(mesh.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), kind, &m_graph));
+    }
+    Graph(const Graph&)            = delete;
+    Graph& operator=(const Graph&) = delete;
+    ~Graph() { l3k_graph_destroy(m_graph); }
+    l3k_graph_info info() const
+    {
+        l3k_graph_info i{};
+        check(l3k_graph_info_get(m_graph, &i));
+        return i;
+    }
+    void       fill(int64_t* d_row_ptr, int32_t* d_col_ind) const { check(l3k_graph_fill(m_graph, d_row_ptr, d_col_ind)); }
+    l3k_graph* get() const { return m_graph; }
+
+private:
+    l3k_graph* m_graph{};
+};
+
 // convertMeshToOrder< order >(mesh_o1) for one rank's hexahedra (mesh/ConvertMeshToOrder.hpp:51-104), on the device:
 // conn = [n_elems][8] vertex ids, local vertex i + 2j + 4k.  Returns the element-node table [n_elems][(order+1)^3] in the
 // numbering [vertices | edge nodes | face nodes | element-internal nodes]; n_nodes receives the node count.

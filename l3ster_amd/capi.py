@@ -60,6 +60,13 @@ class CsrInfo(C.Structure):
                 ("mean_row_len", C.c_double), ("lanes_per_row", C.c_int)]
 
 
+class GraphInfo(C.Structure):
+    """l3k_graph_info: the statistics of the one readback of l3k_graph_create"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
+                ("n_rows_scratch", C.c_int64), ("workspace_bytes", C.c_int64), ("max_elems_per_node", C.c_int),
+                ("lds_key_capacity", C.c_int)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -230,6 +237,10 @@ SIGNATURES = {
                                          C.POINTER(CgResult)]),
     "l3k_csr_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
     "l3k_csr_pcg_solve_cheb": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_graph_create": (C.c_int, [_vp, C.c_int, c_int_p, C.c_int, C.POINTER(_vp)]),
+    "l3k_graph_info_get": (C.c_int, [_vp, C.POINTER(GraphInfo)]),
+    "l3k_graph_fill": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_graph_destroy": (C.c_int, [_vp]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

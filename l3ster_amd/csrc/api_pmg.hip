@@ -68,14 +68,10 @@ struct l3k_pmg
 
 namespace
 {
-// workgroups of a transfer launch over `count` elements: the tuning's waves per CU where set (4 waves per workgroup), else the cap
-// of the solver's vector kernels
+// workgroups of a transfer launch over `count` elements
 unsigned transferGrid(const l3k_ctx* ctx, int64_t count)
 {
-    int64_t cap = l3k_cg_blocks;
-    if (ctx->tune.waves_per_cu > 0)
-        cap = std::max< int64_t >(1, int64_t(ctx->tune.waves_per_cu) * l3k::dev::deviceComputeUnits() / 4);
-    return unsigned(std::max< int64_t >(1, std::min(count, cap)));
+    return stridedGrid(ctx, count);
 }
 l3k::dev::TransferArgs pairArgs(const PmgLevel& fine, const PmgLevel& coarse)
 {

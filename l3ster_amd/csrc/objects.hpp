@@ -130,6 +130,16 @@ struct l3k_ctx
             (void)hipFree(scratch);
     }
 };
+// workgroups of a launch whose workgroups stride over `count` items (the p-multigrid transfers, the rows of l3k_graph): the
+// tuning's waves per CU where set (4 waves per workgroup), else the cap of the solver's vector kernels
+inline unsigned stridedGrid(const l3k_ctx* ctx, int64_t count)
+{
+    int64_t cap = l3k_cg_blocks;
+    if (ctx->tune.waves_per_cu > 0)
+        cap = int64_t(ctx->tune.waves_per_cu) * l3k::dev::deviceComputeUnits() / 4;
+    cap = cap < 1 ? 1 : cap;
+    return unsigned(count < 1 ? 1 : (count < cap ? count : cap));
+}
 struct l3k_mesh
 {
     l3k_ctx*            ctx;

@@ -620,6 +620,7 @@ class MatrixFreeSystem:
         fi = None
         if field_inds is not None:
             fi = (C.c_int * len(field_inds))(*field_inds)
+        self.field_inds = list(range(self.info["n_unknowns"])) if field_inds is None else [int(f) for f in field_inds]
         self._h = C.c_void_p()
         check(capi.load().l3k_mf_create(self.ctx._h, mesh._h, kernel_id, blob, nbytes, C.byref(opts), fi, n_rhs,
                                         C.byref(self._h)))
@@ -832,6 +833,53 @@ class MatrixFreeSystem:
     def new_ghost_buffer(self, ncols, like):
         import torch
         return torch.zeros((ncols, max(self.mesh.n_ghost_dofs, 1)), dtype=torch.float64, device=like.device)
+
+    def sparsity_graph(self, kind="full"):
+        """The CSR graph of this system's dofs on its mesh, built on the device (SparsityGraph): kind "full" is what
+        assemble_global writes into, "condensed" what condense_global does; CsrOperator takes its tensors as they are."""
+        return SparsityGraph(self.mesh, self.field_inds, kind)
+
+
+class SparsityGraph:
+    """The CSR sparsity graph of a DeviceMesh over its local dofs, built on the device (l3k_graph_create / l3k_graph_fill;
+    computeLocalGraph, algsys/SparsityGraph.hpp:26-81): the dofs node * dofs_per_node + field_inds[u] of every element coupled
+    with each other (kind "full"), or those of the element's primary nodes only (kind "condensed", hexes).  field_inds: strictly
+    ascending, None = all dofs of the node.  row_ptr int64 [n + 1] and col_ind int32 [nnz] are torch tensors on the mesh's
+    device, columns ascending within a row; `info` holds n, nnz, n_empty_rows, max_row_len, n_rows_scratch, workspace_bytes,
+    max_elems_per_node and lds_key_capacity (l3k_graph_info)."""
+
+    KINDS = {"full": 0, "condensed": 1}
+
+    def __init__(self, mesh, field_inds=None, kind="full"):
+        import types
+        self.mesh, self.ctx = mesh, mesh.ctx
+        if kind not in self.KINDS:
+            raise L3KError(f"SparsityGraph: kind is 'full' or 'condensed', not {kind!r}")
+        fi = None if field_inds is None else (C.c_int * len(field_inds))(*[int(f) for f in field_inds])
+        self._h = C.c_void_p()
+        check(capi.load().l3k_graph_create(mesh._h, 0 if fi is None else len(fi), fi, self.KINDS[kind], C.byref(self._h)))
+        i = capi.GraphInfo()
+        check(capi.load().l3k_graph_info_get(self._h, C.byref(i)))
+        self.info = types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.GraphInfo._fields_})
+        self.n = self.info.n
+        self.row_ptr, self.col_ind = self.fill()
+
+    def fill(self, row_ptr=None, col_ind=None):
+        """Writes the graph into row_ptr int64 [n + 1] and col_ind int32 [nnz] (allocated here if not given); returns both."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        row_ptr = torch.empty(self.info.n + 1, dtype=torch.int64, device=dev) if row_ptr is None else row_ptr
+        col_ind = torch.empty(self.info.nnz, dtype=torch.int32, device=dev) if col_ind is None else col_ind
+        if row_ptr.dtype != torch.int64 or col_ind.dtype != torch.int32 or row_ptr.numel() < self.info.n + 1 or \
+                col_ind.numel() < self.info.nnz or not (row_ptr.is_contiguous() and col_ind.is_contiguous()):
+            raise L3KError("SparsityGraph.fill: row_ptr is a contiguous int64 tensor of n + 1 entries, col_ind an int32 one of nnz")
+        check(capi.load().l3k_graph_fill(self._h, _ptr(row_ptr), _ptr(col_ind) if col_ind.numel() else None))
+        return row_ptr, col_ind
+
+    def __del__(self):
+        if getattr(self, "_h", None) and capi is not None:
+            capi.load().l3k_graph_destroy(self._h)
+            self._h = None
 
 
 class CsrOperator:
