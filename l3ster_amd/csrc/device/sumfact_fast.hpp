@@ -14,8 +14,11 @@
 //    decomposition (the reference's own flop cut, algsys/SumFactorization.hpp:88-343: 34 instead of 49 instructions per
 //    7-point pencil); the LDS only carries the pencil re-orientations (two buffers per element), with the fields
 //    interleaved in pairs so that every LDS access is 16 bytes wide;
-//  * the global gather goes straight to registers one element ahead (node ids two ahead) and stays in flight behind the
-//    whole compute phase of the current element; waves are persistent and walk the element batches;
+//  * waves are persistent and walk the element batches.  The global gather goes straight to registers: at the top of the element,
+//    with only the node ids requested ahead (behind the previous element's scatter) -- or, where one element per wave leaves the
+//    registers (FastCfg::gather_ahead: the order-6 shapes), one element ahead: ids behind the x-pencil stage, x rows and vertices
+//    behind the I^T-y stage of the previous element, waited for in front of its scatter, so that the first stage of an element
+//    starts without a memory wait and the drain of the scatter's atomics no longer stands in front of its gather;
 //  * the result is staged once through LDS into dof order so that the scatter's wave-instructions cover contiguous
 //    bytes; nodes touched by exactly one element (the element-internal nodes of the reference's numbering,
 //    mesh/LocalMeshView.hpp:425-458) use plain read-modify-write, only shared nodes use f64 atomics.
@@ -141,6 +144,11 @@ __device__ __forceinline__ double opaqueCopy(double x)
     asm volatile("v_mov_b64 %0, %1" : "=v"(y) : "v"(x));
     return y;
 }
+// Gives a register variable a value without an instruction: "whatever the register holds".  For pipeline state that a path does
+// not request (lanes without a pencil, the wave's last element): left alone, the variable would carry its previous value along
+// that path, i.e. stay live -- and occupy its registers -- across all stages of the element.
+__device__ __forceinline__ void anyValue(uint32_t& x) { asm("" : "=v"(x)); }
+__device__ __forceinline__ void anyValue(double& x) { asm("" : "=v"(x)); }
 // Copies a 1-D table out of the kernel-argument segment (scalar loads) and pins the loads in front of everything that
 // follows in program order, so that their latency overlaps with the stage's LDS reads instead of following it.
 template < int N >
@@ -231,6 +239,17 @@ constexpr int kernelWavesPerSimd()
         return K::params.n_unknowns == 1 && NQ_ * NFD <= 36 ? 3 : L3K_FAST_MIN_WAVES;
 }
 
+// A functor whose quadrature-point code already exceeds the register budget of its shape may keep the gather at the top of the
+// element (static constexpr bool gather_ahead = false): the next element's x rows would only add to its spills
+template < typename K >
+constexpr bool kernelGathersAhead()
+{
+    if constexpr (requires { K::gather_ahead; })
+        return K::gather_ahead;
+    else
+        return true;
+}
+
 template < typename K, int P, int NQ >
 struct FastCfg
 {
@@ -296,6 +315,17 @@ struct FastCfg
     // per wave the variant spills (order 6: 45 registers) and loses 12-17 % against column-by-column launches of the
     // single-column kernel (tools/bench_multicol.py), which those shapes therefore keep.
     static constexpr bool multi_column = EW > 1;
+    // the gather runs one element ahead of the sweeps: the next element's node ids are requested behind the x-pencil stage, where the
+    // 2 * NQ * 2 * NG registers of the pencil values and xi-derivatives die, its x rows and vertex coordinate behind the I^T-y stage;
+    // they stay in registers (N1 * (U + F) doubles + one coordinate) across I^T z, the staging and the scatter.  (Requested one stage
+    // earlier each -- ids behind the quadrature stage, x behind the x-pencil stage -- the order-6 Diffusion3D kernel spills 24 to 190
+    // bytes per lane, whatever else is trimmed; the mask bytes of flagged elements are fetched where they are used for the same reason.)
+    // One element per wave only (with several the freed registers hold the other elements' state), and where the shape was compiled
+    // and found free of scratch with it: the order-6 shapes (nq = 7) of functors that do not opt out.  Plain, SPLIT, ENERGY and AFFINE
+    // variants; not MULTI, STRIDED, RHS.
+    // (SG == 64: all 64 lanes scatter the element -- with 3 unknowns 63 do, and the kernel's straight path into the scatter, which
+    // takes every lane along, would let the 64th add a dof twice)
+    static constexpr bool gather_ahead = EW == 1 && N1 == 7 && NQ == 7 && SG == 64 && kernelGathersAhead< K >();
 };
 
 // SPLIT: ghost rows live in buffers of their own (a.xg / a.yg, the reference's import / export buffers): every node needs
@@ -326,6 +356,12 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
     constexpr int DG = Cfg::DG, DF = Cfg::DF; // groups / fields whose derivatives are formed
     static_assert(!STRIDED || (!ENERGY && !AFFINE && !MULTI));
     static_assert(!RHS || (!ENERGY && !AFFINE && !MULTI && !STRIDED));
+    // GA: the gather of element i + 1 is in flight behind the tail stages and the scatter of element i (FastCfg::gather_ahead)
+#if defined(L3K_FLAGGED_SCATTER) || defined(L3K_ABLATION) // (A/B and ablation builds keep the gather at the top of the element)
+    constexpr bool GA = false;
+#else
+    constexpr bool GA = Cfg::gather_ahead && !MULTI && !STRIDED && !RHS;
+#endif
     [[maybe_unused]] const int dpn = a.dofs_per_node; // (STRIDED)
     // bit u: dof u of the kernel at `node` is a Dirichlet dof
     auto dirBits = [&](int64_t node) -> uint32_t {
@@ -414,8 +450,10 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
     const int  dyn_step = by_xcd || !sharded ? 1 : 8;
     auto       drawTicket = [&]() -> uint32_t {
         uint32_t t = 0;
+        // (GA: the address through a per-lane register.  On a wave-uniform address the compiler rewrites the add into one of the
+        // active-lane count followed by s_waitcnt vmcnt(0) at once, which would drain the previous element's scatter in front of S1)
         if (dyn && lane == 0)
-            t = __hip_atomic_fetch_add(a.work_counters + 32 * victim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // 128 B apart
+            t = __hip_atomic_fetch_add(a.work_counters + 32 * victim + (GA ? opaqueCopy(0) : 0), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // 128 B apart
         return t;
     };
     // batch of a ticket drawn from the current victim, or the end marker nb when every counter is exhausted
@@ -432,11 +470,13 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
     };
     const int lim   = dyn ? nb : last; // loop bound: dynamic batches are valid below nb
     int       batch = dyn ? ticketBatch(drawTicket()) : first + (by_xcd ? int(blockIdx.x >> 3) : int(blockIdx.x));
-    // ---- software pipeline state: node ids two batches ahead, x values one batch ahead
+    // ---- software pipeline state: node ids of the next batch; GA: also its x rows, mask words and vertex coordinate (else these
+    // hold the current batch's, requested at the top of the element)
     uint32_t      ids_cur[N1], ids_nxt[N1];
     double        xn[N1][U];
     double        fn[N1][F > 0 ? F : 1];
     uint32_t      dm_nxt[N1];
+    [[maybe_unused]] double vreg_nxt = 0.;
     const int64_t n_owned_nodes = a.n_owned_dofs / (STRIDED ? a.dofs_per_node : U);
     auto          elemOf = [&](int b) { return a.elem_begin + int64_t(b) * EW + team; };
     auto          valid  = [&](int b) { return (b < lim) & on_nn & ((int64_t(b) * EW + team) < a.elem_count); };
@@ -459,7 +499,26 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         // bit 0 / 1: the gathered / the scattered element touches a Dirichlet dof (bit 1 of the mesh's flags marks affine
         // elements: used at launch time to select the AFFINE kernel variant for all-affine meshes)
         flag = ((fg & 1u) ? 1u : 0u) | ((fs & 1u) ? 2u : 0u);
-        if (valid(batch))
+        if constexpr (GA)
+        {
+            // every lane requests ids, the lanes without a pencil those of the last pencil, so that the only branch is the wave-uniform
+            // "there is a next batch".  (A per-lane branch has the other lanes redefine registers with loads in flight, which
+            // waits for the loads at once.)  Beyond the last batch: no value carried along beside the current ids
+            if (batch < lim)
+            {
+                const uint32_t* en = a.elem_nodes + (a.elem_begin + int64_t(batch)) * NN + (lane_o < N1 * N1 ? lane_o : N1 * N1 - 1);
+#pragma unroll
+                for (int k = 0; k < N1; ++k)
+                    ids[k] = en[k * N1 * N1];
+            }
+            else
+            {
+#pragma unroll
+                for (int k = 0; k < N1; ++k)
+                    anyValue(ids[k]);
+            }
+        }
+        else if (valid(batch))
         {
             const uint32_t* en = a.elem_nodes + elemOf(batch) * NN + (lane_o - team * TEAM); // + i1 + N1 * j1
 #pragma unroll
@@ -512,10 +571,36 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
                 for (int u = 0; u < U; ++u)
                     xn[k][u] = (L3K_DBG(a) & 2) ? 1e-9 * double(node) : p[u];
             }
-            dm_nxt[k] = !RHS && flagged ? dirBits(node) : 0u;
+            if constexpr (!GA)
+                dm_nxt[k] = !RHS && flagged ? dirBits(node) : 0u;
 #pragma unroll
             for (int f = 0; f < F; ++f)
                 fn[k][f] = a.fields[node + f * a.ldf];
+        }
+    };
+    // GA: the gather of batch b (ids already there), vertex coordinate included, by every lane (as the ids: the lanes without a
+    // pencil repeat the last pencil's requests, the lanes beyond the 24 coordinates the last coordinate's); nothing beyond the last
+    // batch (one element per wave: every batch below lim has its element)
+    [[maybe_unused]] auto gatherAhead = [&](int b, const uint32_t (&ids)[N1]) {
+        if (b < lim)
+        {
+            loadX(true, ids, false); // (the mask bytes of a flagged element are fetched where they are used)
+            const int lane_o = opaqueCopy(lane);
+            vreg_nxt         = a.elem_verts[(a.elem_begin + int64_t(b)) * 24 + (lane_o < 24 ? lane_o : 23)];
+        }
+        else // (nothing requested: the state is not read either)
+        {
+#pragma unroll
+            for (int k = 0; k < N1; ++k)
+            {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    anyValue(xn[k][u]);
+#pragma unroll
+                for (int f = 0; f < F; ++f)
+                    anyValue(fn[k][f]);
+            }
+            anyValue(vreg_nxt);
         }
     };
 
@@ -533,6 +618,8 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
     stageFence();
     uint32_t flag_cur, flag_nxt = 0;
     loadIds(batch, ids_cur, flag_cur);
+    if constexpr (GA) // prologue: the first element of the wave gathers here
+        gatherAhead(batch, ids_cur);
 
     [[maybe_unused]] int stamp_it = 0;
 #ifdef L3K_ABLATION
@@ -555,11 +642,16 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         {
         // all gather loads of this element are issued back to back (one exposed latency, hidden by the other resident
         // waves); only the next element's node ids are prefetched: holding the next x values in registers across the
-        // compute phase made the compiler spill them and wait on every load (profiles/r01 notes in DESIGN.md)
+        // compute phase made the compiler spill them and wait on every load (profiles/r01 notes in DESIGN.md).
+        // GA: nothing is loaded here -- the x rows were requested behind the I^T-y stage of the previous element (or in the
+        // prologue) and waited for in front of its scatter: S1 starts without a memory wait, the scatter's atomics drain behind it
         // one masked region for everything up to the scatter: the lanes without a pencil (helpers of the scatter) skip it
+        // (GA: two regions, with the wave-uniform batch bookkeeping between them)
+        double v[NQ][2 * NG], dxi[NQ][2 * NG]; // (S3/S4 to the x-pencil stage)
         if (w_all)
         {
-        loadX(w_nn, ids_cur, RHS ? (a.dirichlet_vals != nullptr && ((flag_cur & 1u) != 0 || !have_flags)) : (flag_cur & 1u) != 0);
+        if constexpr (!GA)
+            loadX(w_nn, ids_cur, RHS ? (a.dirichlet_vals != nullptr && ((flag_cur & 1u) != 0 || !have_flags)) : (flag_cur & 1u) != 0);
         // ---- take over the prefetched data (gatherSumFact: Dirichlet dofs read as 0, MatrixFreeSystem.hpp:441-466)
         double u0[N1][2 * NG];
         if (w_nn)
@@ -572,6 +664,8 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
                     u0[k][u] = xn[k][u];
                 if (!RHS && (flag_cur & 1u) != 0) // only elements touching a Dirichlet dof pay for the masking
                 {
+                    if constexpr (GA) // (the mask bytes of a flagged element are fetched here: full waits, on these elements only)
+                        dm_nxt[k] = dirBits(ids_cur[k]);
 #pragma unroll
                     for (int u = 0; u < U; ++u)
                         u0[k][u] = (dm_nxt[k] >> u) & 1u ? 0. : u0[k][u];
@@ -587,7 +681,9 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         // waited for.  Teams of fewer than 24 lanes (orders <= 3) store them to the team's LDS block right away
         constexpr bool VREG = TEAM >= 24;
         double         vreg = 0.;
-        if constexpr (VREG)
+        if constexpr (VREG && GA)
+            vreg = vreg_nxt;
+        else if constexpr (VREG)
         {
             if (l < 24)
                 vreg = a.elem_verts[elemOf(batch) * 24 + opaqueCopy(l)];
@@ -658,7 +754,6 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         stageFence();
         L3K_STAMP(2);
         // ---- S3/S4: x interpolation + xi-derivative, lane (qy, qz) = (qa, qb); values to bufA (c=qx, b=qy, a=qz)
-        double v[NQ][2 * NG], dxi[NQ][2 * NG];
         if (w_qq)
         {
             double tI[2 * HN * HQ];
@@ -970,6 +1065,18 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         }
         stageFence();
         L3K_STAMP(8);
+        } // if (w_all)
+        // GA: v and dxi are dead.  The ticket drawn at the top of the element has arrived long ago: the next batch is resolved here
+        // (the switch to another XCD's counter included, so that ids and x both come from the batch that is processed) and its
+        // node ids are requested, in flight behind the I^T-y stage.  (Outside the masked region: the batch bookkeeping is
+        // wave-uniform, and every lane defines its pipeline state, see anyValue)
+        if constexpr (GA)
+        {
+            batch_next = dyn ? ticketBatch(ticket) : batch + stride;
+            loadIds(batch_next, ids_nxt, flag_nxt);
+        }
+        if (w_all)
+        {
         // ---- I^T along y, lane (ix, qz) = (iq, kq): bufB (c=ix, b=qy, a=qz) -> bufA (c=ix, b=iy, a=qz)
         if (w_nq)
         {
@@ -1003,6 +1110,12 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         }
         stageFence();
         L3K_STAMP(9);
+        } // if (w_all)
+        // GA: the next element's x rows and vertex coordinate, in flight behind the I^T-z stage, the staging and the ids' way to LDS
+        if constexpr (GA)
+            gatherAhead(batch_next, ids_nxt);
+        if (w_all)
+        {
         // ---- I^T along z in registers, lane (ix, iy) = (i1, j1); stage the result in bufB as [node][unknown]
         if (w_nn)
         {
@@ -1116,7 +1229,14 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         } // if (w_all)
         stageFence(); // (every lane: the scatter below reads what the pencil lanes staged)
         L3K_STAMP(11);
-        if (!MULTI || col == (a.n_cols > 1 ? a.n_cols : 1) - 1)
+        // GA: the x rows requested behind the I^T-y stage have had two stages to arrive; they are waited for HERE, in front of the
+        // scatter's first memory instruction and outside every branch (s_waitcnt vmcnt(0), nothing else pending), so that nothing
+        // with a register result is in flight across the scatter: the compiler's wait-count merge over the scatter's paths then has
+        // nothing to turn into a full wait -- neither in front of S1 nor at the copy of the next ids at the end of the pass, where
+        // a full wait would drain this scatter's atomics
+        if constexpr (GA)
+            __builtin_amdgcn_s_waitcnt(0x0f70);
+        if (!GA && (!MULTI || col == (a.n_cols > 1 ? a.n_cols : 1) - 1))
         {
             batch_next = dyn ? ticketBatch(ticket) : batch + stride;
             loadIds(batch_next, ids_nxt, flag_nxt); // next element's node ids: in flight behind the scatter
@@ -1131,8 +1251,9 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
         // (the scatter's per-lane constants are rebuilt here from an opaque copy of the lane id: as loop invariants they
         // would be kept in registers across the sweeps, which have none to spare)
         const int lane_s = opaqueCopy(lane);
-        const int steam_s = lane_s / SG, sl = lane_s - steam_s * SG;
-        if (steam_s < EW && (int64_t(batch) * EW + steam_s) < a.elem_count)
+        // (GA: one element per wave, batch < lim <= elem_count and SG = 64 -- every lane scatters: no branch around the scatter)
+        const int steam_s = GA ? 0 : lane_s / SG, sl = lane_s - steam_s * SG;
+        if (GA || (steam_s < EW && (int64_t(batch) * EW + steam_s) < a.elem_count))
         {
             const double* const   sb      = lds + size_t(steam_s) * Cfg::TEAM_D + Cfg::OFF_B;
             const uint32_t* const idsS    = reinterpret_cast< const uint32_t* >(lds + size_t(steam_s) * Cfg::TEAM_D);
@@ -1144,7 +1265,7 @@ __global__ __launch_bounds__(64, (FastCfg< K, P, NQ >::wavesPerSimd(MULTI))) voi
 #endif
             // (SG is a multiple of U: a lane keeps its unknown and moves SG / U slots per round -- every LDS address below is
             // one per-lane base plus a compile-time offset)
-            static_assert(SG % U == 0);
+            static_assert(SG % U == 0 && (!GA || SG == 64));
             // exclusive (element-internal) nodes: 16-byte stores, two unknowns per lane -- or, with an odd number of unknowns
             // (8-byte aligned rows), one unknown per lane like the shell slots: XW doubles per lane, UX = U / XW lanes per node
             constexpr int         XW = U % 2 == 0 ? 2 : 1, UX = U / XW;

@@ -132,6 +132,8 @@ struct AdvDiff3D
 struct Diffusion3DPoint
 {
     static constexpr KernelParams params{.dimension = 3, .n_equations = 7, .n_unknowns = 4};
+    // (order 6: the sin / cos of the quadrature stage already spill ~80 registers; no room to hold the next element's x rows)
+    static constexpr bool         gather_ahead = false;
     double                        k = 1., s = 1.;
 
     template < typename In, typename Out >
