@@ -258,7 +258,9 @@ int l3k_mf_dirichlet_finalize(l3k_mf* mf, const double* d_dirichlet_vals, size_t
  * l3k_mf_attach_boundary registers the term with a system: l3k_mf_apply / l3k_mf_apply_elems / l3k_mf_diag_rhs then
  * include it, like the reference evaluates every kernel passed to assembleProblem.  `which` as in l3k_mf_apply_elems:
  * sides of interior elements (0), of border elements (1), all (2).  The term does not own the system or the mesh and
- * must outlive the systems it is attached to. */
+ * must outlive the systems it is attached to.  The assembled and condensed entry points (l3k_local_assemble,
+ * l3k_assemble_global, l3k_condense_local, l3k_condense_global, l3k_condensed_recover) include the attached terms only after
+ * l3k_mf_assemble_boundary(mf, 1), below. */
 typedef struct l3k_bnd l3k_bnd;
 int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kparam_blob, size_t kparam_bytes,
                    const l3k_asmopts* opts, const int* field_inds, int n_rhs, int64_t n_faces, const int64_t* face_elem,
@@ -273,6 +275,28 @@ int l3k_bnd_apply(l3k_bnd* bnd, int which, const double* d_x, size_t ldx, const 
 int l3k_bnd_diag_rhs(l3k_bnd* bnd, int which, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs,
                      size_t ldr, double* d_diag_ghost, double* d_rhs_ghost, size_t ldrg);
 int l3k_mf_attach_boundary(l3k_mf* mf, l3k_bnd* bnd);
+/* ---- ... in the assembled and condensed paths (hexes; quads are refused) ------------------------------------------------
+ * assembleLocalSystem on a BoundaryElementView (algsys/AssembleLocalSystem.hpp:77-216): the local system of the WHOLE element
+ * from the side quadrature, K_s = sum_q w jac B_q^T B_q, F_s = sum_q w jac B_q^T f_q, for the sides [first, first + count) of the
+ * term's list in the order l3k_bnd_create was given.  Layouts of l3k_local_assemble: d_K [count][Nd][Nd] row-major, d_F
+ * [count][n_rhs][Nd], Nd = (p+1)^3 * n_unknowns; either may be NULL; no Dirichlet lifting, no mask.  Every entry is written
+ * (zeros included); K_s is bitwise symmetric and bitwise reproducible. */
+int l3k_bnd_local_assemble(l3k_bnd* bnd, int64_t first, int64_t count, double* d_K, double* d_F);
+/* The boundary overload of assembleGlobalSystem (algsys/AssembleGlobalSystem.hpp:55-96) for the sides [first, first + count) of one
+ * term: side systems formed in sub-batches (the library's own workspace, workspace_bytes in total, 0 = 1 GiB) and summed into
+ * d_values / d_rhs over the rows node * dofs_per_node + field_inds[u] of the term.  Graph, ldr, skip_dirichlet and n_missing as
+ * for l3k_assemble_global.  Additive: after l3k_assemble_global on the same arrays the result is A_domain + A_boundary. */
+int l3k_bnd_assemble_global(l3k_bnd* bnd, int64_t first, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind,
+                            double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes,
+                            int64_t* n_missing);
+/* on != 0: from now on l3k_local_assemble, l3k_assemble_global, l3k_condense_local, l3k_condense_global and
+ * l3k_condensed_recover work on K_e + sum K_s, F_e + sum F_s over the attached sides of each element, as the reference's assembled
+ * path does with CondensationPolicy::ElementBoundary (StaticCondensationManager.hpp:354-407: the side matrix joins the element's
+ * blocks before the internal dofs are eliminated).  The sides of an element are added in a fixed order (terms in attachment
+ * order, a term's sides in list order): results stay bitwise symmetric and reproducible.  Refused (-1) while it is on: a term
+ * whose n_unknowns, field_inds or n_rhs differ from the system's or whose shape has no assembly launcher, l3k_local_assemble
+ * with a checksum, and l3k_local_assemble_tiled.  Default 0: every call does exactly what it did without this switch. */
+int l3k_mf_assemble_boundary(l3k_mf* mf, int on);
 
 /* ---- integrals of residual kernels (post-processing) -----------------------------------------------------------------
  * evalLocalIntegral, post/Integral.hpp:54-111: h_out[n_equations] (HOST) = sum over all elements (n_faces < 0) or over

@@ -7,6 +7,7 @@
 //       .diagAndRhs(...)            ~ endAssembly() -> computeDiagAndRhs                   :877-941
 //       .assembleLocal(...)         ~ assembleLocalSystem                                  algsys/AssembleLocalSystem.hpp:234-256
 //       .assembleProblem(bnd)       ~ assembleProblem(boundary kernel, boundary_ids)      algsys/MatrixFreeSystem.hpp:58-68
+//       .assembleBoundary(on)       ~ the boundary overload of assembleGlobalSystem          algsys/AssembleGlobalSystem.hpp:55-96
 //       .apply(halo, X, Y, ...)     ~ applyImpl of a partitioned system, exchange included    :1020-1140
 //       .scatterLocalSystems(...)   ~ scatterLocalSystem / assembleGlobalSystem             algsys/ScatterLocalSystem.hpp:24-54
 //   l3k::Halo                    ~ comm::ImportExportContext + comm::Import / comm::Export  comm/ImportExport.hpp:29-72,130-215
@@ -238,6 +239,22 @@ public:
     ~BoundaryTerm() { l3k_bnd_destroy(m_bnd); }
     void     setFields(const double* d_soa, size_t ld) { check(l3k_bnd_set_fields(m_bnd, d_soa, ld)); }
     void     setTime(double t) { check(l3k_bnd_set_time(m_bnd, t)); } // in.point.time of the boundary kernel
+    // assembleLocalSystem on the sides [first, first+count) of the list (AssembleLocalSystem.hpp:77-216): K_s (row-major Nd x Nd),
+    // F_s (column-major Nd x n_rhs) of the whole element from the side quadrature; either may be nullptr (hexes)
+    void assembleLocal(int64_t first, int64_t count, double* d_K, double* d_F) const
+    {
+        check(l3k_bnd_local_assemble(m_bnd, first, count, d_K, d_F));
+    }
+    // the boundary overload of assembleGlobalSystem (AssembleGlobalSystem.hpp:55-96) for the sides [first, first+count): summed into
+    // the caller's CSR values / rhs, additive; returns the number of entries outside the graph
+    int64_t assembleGlobal(int64_t first, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind, double* d_values, double* d_rhs,
+                           size_t ldr, bool skip_dirichlet = false, size_t workspace_bytes = 0) const
+    {
+        int64_t missing = 0;
+        check(l3k_bnd_assemble_global(m_bnd, first, count, d_row_ptr, d_col_ind, d_values, d_rhs, ldr, skip_dirichlet ? 1 : 0, workspace_bytes,
+                                      &missing));
+        return missing;
+    }
     l3k_bnd* get() const { return m_bnd; }
 
 private:
@@ -335,6 +352,9 @@ public:
     // assembleProblem(boundary kernel, boundary ids): the term takes part in apply / diagAndRhs from now on and must
     // outlive this system
     void assembleProblem(const BoundaryTerm& term) { check(l3k_mf_attach_boundary(m_mf, term.get())); }
+    // ... and, once switched on, in assembleLocal, assembleGlobal and the condensation calls: K_e + sum K_s, F_e + sum F_s over the
+    // attached sides of each element, as the reference's assembled path forms them (AssembleGlobalSystem.hpp:55-96)
+    void assembleBoundary(bool on = true) { check(l3k_mf_assemble_boundary(m_mf, on ? 1 : 0)); }
     // Y <- alpha*A*X + beta*Y (Operator::apply; the operator is symmetric, `mode` is ignored by the reference too)
     void apply(const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols = 1, double alpha = 1., double beta = 0.) const
     {

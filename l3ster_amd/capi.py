@@ -191,6 +191,9 @@ SIGNATURES = {
                                 C.c_double]),
     "l3k_bnd_diag_rhs": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t]),
     "l3k_mf_attach_boundary": (C.c_int, [_vp, _vp]),
+    "l3k_bnd_local_assemble": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "l3k_bnd_assemble_global": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, c_int64_p]),
+    "l3k_mf_assemble_boundary": (C.c_int, [_vp, C.c_int]),
     "l3k_residual_info": (C.c_int, [C.c_int, C.POINTER(KParams), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]),
     "l3k_integrate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(AsmOpts), _vp, C.c_size_t, C.c_double,
                                 C.c_int, C.c_int64, c_int64_p, c_uint8_p, c_double_p]),

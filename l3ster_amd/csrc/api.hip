@@ -1606,6 +1606,18 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
         return rc;
     if (count == 0)
         return 0;
+    const bool sides = assemblesBoundary(mf);
+    if (sides)
+    {
+        if (int rc = checkAssembleBoundary(mf, "l3k_local_assemble"))
+            return rc;
+        if (d_checksum)
+        {
+            setError("l3k_local_assemble: no checksum with l3k_mf_assemble_boundary on (the streaming checksum has no stored matrix to "
+                     "add the side matrices to)");
+            return -1;
+        }
+    }
     const auto* inst = instanceFor(mf, mf->n_rhs);
     if (!inst)
         return -4;
@@ -1653,6 +1665,8 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
         if (int rc = inst->diag_rhs(a, blob, s))
             return rc;
     }
+    if (sides) // the finished row-major K_e, F_e take the side systems of their elements (on the tiled route: after the transposition)
+        return accumulateBoundarySides(mf, first, count, d_K, d_F);
     return 0;
 }
 // K_e of the elements [first, first + count) in the TILED layout (include/l3k.h): what l3k_assemble_global keeps between its two kernels
@@ -1666,6 +1680,12 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
     const l3k_mesh* m = mf->mesh;
     if (int rc = refuseQuads(m, "l3k_local_assemble_tiled"))
         return rc;
+    if (assemblesBoundary(mf))
+    {
+        setError("l3k_local_assemble_tiled: not with l3k_mf_assemble_boundary on (the side matrices are added to row-major element "
+                 "matrices: use l3k_local_assemble)");
+        return -1;
+    }
     if (int rc = checkRange(m, first, count))
         return rc;
     if (count == 0)
@@ -1722,6 +1742,10 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
         *n_missing = 0;
     if (count == 0)
         return 0;
+    const bool sides = assemblesBoundary(mf);
+    if (sides)
+        if (int rc = checkAssembleBoundary(mf, "l3k_assemble_global"))
+            return rc;
     const auto* inst = instanceFor(mf, mf->n_rhs);
     if (!inst)
         return -4;
@@ -1782,7 +1806,12 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
                                               skip_dirichlet, d_count, g.second, tiled);
             }))
         return rc;
-    return readDegenerateFlags(sa, flag[0], flag[1], d_count, n_missing);
+    if (int rc = readDegenerateFlags(sa, flag[0], flag[1], d_count, n_missing))
+        return rc;
+    if (sides) // the domain route above is the tiled one; the sides of the range's elements follow through the standalone side route
+        return assembleGlobalBoundarySides(mf, first, count, d_row_ptr, d_col_ind, d_values, d_rhs, ldr, skip_dirichlet, workspace_bytes,
+                                           n_missing);
+    return 0;
 }
 // ------------------------------------------------------------------------------------------------ boundary terms
 int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kparam_blob, size_t kparam_bytes,
@@ -1855,6 +1884,8 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
             b->n_interior_faces = int64_t(fe.size());
     }
     b->n_faces = n_faces;
+    b->list_elem.assign(face_elem, face_elem + n_faces); // (the caller's order: what the assembly entry points index)
+    b->list_side.assign(face_side, face_side + n_faces);
     if (ctx->deterministic)
     {
         // greedy colouring of the sides by ALL 2^dim corner nodes of their elements: the side kernel scatter-adds over every

@@ -486,7 +486,14 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
                            const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
                            unsigned long long* d_count, hipStream_t s, int tiled)
 {
-    const l3k_mesh* m  = mf->mesh;
+    return launchAssembledScatterRows(mf->ctx, mf->mesh, mf->mesh->elem_nodes.ptr, mf->kp.n_unknowns, mf->n_rhs, mf->field_inds, first, count, d_K,
+                                      d_F, d_row_ptr, d_col_ind, d_values, d_rhs, ldr, skip_dirichlet, d_count, s, tiled);
+}
+int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint32_t* d_nodes, int n_unknowns, int n_rhs, const int* field_inds,
+                               int64_t first, int64_t count, const double* d_K, const double* d_F, const int64_t* d_row_ptr,
+                               const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
+                               unsigned long long* d_count, hipStream_t s, int tiled)
+{
     const int       N1 = m->order + 1, NN = N1 * N1 * N1;
     const int64_t   blocks = count * NN;
     if (blocks > int64_t(0x7fffffff))
@@ -495,7 +502,7 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
         return -1;
     }
     ScatterArgs a{};
-    a.elem_nodes     = m->elem_nodes.ptr;
+    a.elem_nodes     = d_nodes;
     a.dirichlet      = m->dirichlet.ptr;
     a.K              = d_K;
     a.F              = d_F;
@@ -509,15 +516,15 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
     a.count          = count;
     a.NN             = NN;
     a.dpn            = m->dofs_per_node;
-    a.n_rhs          = mf->n_rhs;
+    a.n_rhs          = n_rhs;
     a.skip_dirichlet = skip_dirichlet;
     for (int u = 0; u < l3k::dev::max_unknowns; ++u)
-        a.field_inds[u] = mf->field_inds[u];
-    a.U_rt = mf->kp.n_unknowns;
+        a.field_inds[u] = field_inds[u];
+    a.U_rt = n_unknowns;
     if (tiled)
     {
         int rc = 1;
-        switch (mf->kp.n_unknowns)
+        switch (n_unknowns)
         {
         case 1: rc = launchScatterTiled< 1 >(a, N1, blocks, s); break;
         case 2: rc = launchScatterTiled< 2 >(a, N1, blocks, s); break;
@@ -527,13 +534,13 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
         }
         if (rc)
         {
-            setError("tiled scatter: shape (order %d, %d unknowns) not instantiated", m->order, mf->kp.n_unknowns);
+            setError("tiled scatter: shape (order %d, %d unknowns) not instantiated", m->order, n_unknowns);
             return -1;
         }
     }
-    else if (mf->ctx->tune.scatter_per_entry) // (the round-2 kernel, kept as the cross-check of the per-row-node one)
+    else if (ctx->tune.scatter_per_entry) // (the round-2 kernel, kept as the cross-check of the per-row-node one)
     {
-        const int64_t rows = count * NN * mf->kp.n_unknowns;
+        const int64_t rows = count * NN * n_unknowns;
         if (rows > int64_t(0x7fffffff))
         {
             setError("batch too large: %lld element rows in one launch", (long long)rows);
@@ -542,7 +549,7 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
         hipLaunchKernelGGL(assembledScatterPerEntryKernel, dim3(unsigned(rows)), dim3(64), 0, s, a);
     }
     else
-        switch (mf->kp.n_unknowns)
+        switch (n_unknowns)
         {
         case 1: hipLaunchKernelGGL(assembledScatterKernel< 1 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
         case 2: hipLaunchKernelGGL(assembledScatterKernel< 2 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
@@ -552,7 +559,7 @@ int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const doubl
         case 6: hipLaunchKernelGGL(assembledScatterKernel< 6 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
         case 7: hipLaunchKernelGGL(assembledScatterKernel< 7 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
         case 8: hipLaunchKernelGGL(assembledScatterKernel< 8 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        default: setError("l3k_assembled_scatter: %d unknowns not supported (1..8)", mf->kp.n_unknowns); return -1;
+        default: setError("l3k_assembled_scatter: %d unknowns not supported (1..8)", n_unknowns); return -1;
         }
     L3K_HIP(hipGetLastError());
     return 0;

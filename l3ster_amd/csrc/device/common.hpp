@@ -141,12 +141,35 @@ struct Instance
     CondenseFn condense = nullptr; // static condensation of element systems of this (order, unknowns) shape; nullptr on quads
 };
 
+// what the side assembly kernels need (device/boundary_assemble.hpp); passed by value as the kernel argument
+struct SideAsmArgs
+{
+    const uint32_t* elem_nodes; // [n_elems][N]
+    const double*   elem_verts; // [n_elems][8][3]
+    const double*   tables;     // TableLayout (device)
+    const double*   fields;     // SoA [F][ldf] or nullptr
+    size_t          ldf;
+    double          time;
+    const int64_t*  face_elem;  // the sides of the list this launch walks ...
+    const uint8_t*  face_side;
+    const uint8_t*  face_rank;  // ... accumulate mode: the position of each side among the sides of its element
+    int64_t         face_begin, face_count;
+    double*         coef;       // [face_count][nq^2][coefficient record]
+    double *        K, *F;      // [slots][Nd][Nd] row-major / [slots][R][Nd], either may be null
+    int64_t         elem_base;  // accumulate mode: slot = element - elem_base (write mode: slot = position in the launch)
+    int             accumulate;
+    int             round;      // accumulate mode: only sides with face_rank == round; the coefficients are formed in round 0
+};
+using SideAsmFn = int (*)(const SideAsmArgs&, const void* kparam_blob, hipStream_t stream);
+
 // boundary equation kernel on element sides (device/boundary.hpp)
 struct BoundaryInstance
 {
     int      kernel_id, order, nq, ncols;
     LaunchFn apply;    // y += alpha * A_b x
     LaunchFn diag_rhs; // diag += diag(A_b), rhs += B_b^T W (f_b - B_b g)
+    SideAsmFn assemble = nullptr;      // local systems K_s, F_s of the sides (hexes; nullptr on quads)
+    size_t    assemble_ws_doubles = 0; // coefficient doubles per side for `assemble`
 };
 // residual kernel integral (device/integral.hpp); `blocks` = number of partial sums the launch writes
 struct IntegralInstance

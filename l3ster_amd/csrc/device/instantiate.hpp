@@ -13,6 +13,7 @@
 #include "assemble.hpp"
 #include "condense.hpp"
 #include "boundary.hpp"
+#include "boundary_assemble.hpp"
 #include "integral.hpp"
 #include "quad.hpp"
 #include "quad_boundary.hpp"
@@ -118,14 +119,16 @@ Instance makeInstance()
                 assembleWorkspaceDoublesPerElem< T, P, NQ >(), selectApplyCols< T, P, NQ, R >(), SfAsmCfg< P, NQ >::feasible,
                 selectRoute< T, P, NQ, R >(), selectCondense< P, T::params.n_unknowns >()};
 }
-// ... of a boundary equation kernel: the side kernel of quad_boundary.hpp on quads, of boundary.hpp on hexes
+// ... of a boundary equation kernel: the side kernel of quad_boundary.hpp on quads, of boundary.hpp on hexes, which also have
+// the side assembly of boundary_assemble.hpp
 template < typename T, int P, int NQ, int R >
 BoundaryInstance makeBoundaryInstance()
 {
     if constexpr (T::params.dimension == 2)
         return {KernelId< T >::value, P, NQ, R, &launchQuadSide< T, P, NQ, R, false >, &launchQuadSide< T, P, NQ, R, true >};
     else
-        return {KernelId< T >::value, P, NQ, R, &launchFace< T, P, NQ, R, false >, &launchFace< T, P, NQ, R, true >};
+        return {KernelId< T >::value, P, NQ, R, &launchFace< T, P, NQ, R, false >, &launchFace< T, P, NQ, R, true >,
+                &launchSideAssemble< T, P, NQ, R >, sideAssembleWorkspaceDoubles< T, NQ, R >()};
 }
 // ... of a residual kernel (integrals over elements and sides, values at nodes), chosen the same way
 template < typename T, int P, int NQ >

@@ -275,6 +275,8 @@ struct l3k_mf
     // Two pipelines, not one, because they nest: l3k_condense_global forms its sub-batches through l3k_local_assemble, whose stored
     // row-major route runs a whole pipeline on gasm (as l3k_assemble_global does) while the outer one is mid-flight on gcond
     SubBatchPipe gasm, gcond;
+    // l3k_mf_assemble_boundary: the assembled and condensed entry points work on K_e + sum K_s, F_e + sum F_s over the attached sides
+    bool         assemble_boundary = false;
     unsigned*    cond_nfail = nullptr; // the condensation's device counter of elements with a non-positive pivot
     ~l3k_mf()
     {
@@ -359,6 +361,22 @@ struct l3k_bnd
     const double*         fields = nullptr;
     size_t                ldf    = 0;
     double                time   = 0.;
+    // ---- assembly of the side systems (api_bnd_assemble.hip): two more orders of the list, built on first use
+    struct SideList
+    {
+        DevBuf< int64_t >  elem;
+        DevBuf< uint8_t >  side, rank; // rank: position of the side among the sides of its element (sorted list only)
+        DevBuf< uint32_t > nodes;      // [n_faces][N]: the node rows of the sides' elements, what the scatter kernel indexes
+        bool               built = false;
+    };
+    std::vector< int64_t > list_elem; // host: the list in the order l3k_bnd_create was given
+    std::vector< uint8_t > list_side;
+    SideList               in_order;  // ... in that order on the device
+    SideList               by_elem;   // ... stably sorted by element
+    std::vector< int64_t > by_elem_host; // host: the elements of by_elem
+    std::vector< uint8_t > by_elem_rank; // host: the ranks of by_elem
+    SubBatchPipe           gasm;         // the sub-batch pipeline of l3k_bnd_assemble_global
+    DevBuf< double >       coef_ws;      // coefficient workspace of l3k_bnd_local_assemble and of the accumulating route
 };
 
 
@@ -390,4 +408,23 @@ int launchTiledXToRowMajorSym(int U, int N1, int64_t count, const double* d_Kt, 
 int launchAssembledScatter(l3k_mf* mf, int64_t first, int64_t count, const double* d_K, const double* d_F, const int64_t* d_row_ptr,
                            const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
                            unsigned long long* d_count, hipStream_t s, int tiled);
+// ... of systems whose node rows are d_nodes[first + e] (element systems: the mesh's elem_nodes; side systems: the node rows of the
+// sides' elements) with the unknowns, right-hand sides and dofs of the caller's term
+int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint32_t* d_nodes, int n_unknowns, int n_rhs, const int* field_inds,
+                               int64_t first, int64_t count, const double* d_K, const double* d_F, const int64_t* d_row_ptr,
+                               const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
+                               unsigned long long* d_count, hipStream_t s, int tiled);
+// api_bnd_assemble.hip: with l3k_mf_assemble_boundary on and terms attached, the refusals of `what` (0, or -1 with the error set) ...
+int checkAssembleBoundary(const l3k_mf* mf, const char* what);
+inline bool assemblesBoundary(const l3k_mf* mf)
+{
+    return mf->assemble_boundary && !mf->boundary_terms.empty();
+}
+// ... K_e += sum K_s, F_e += sum F_s over the attached sides of the elements [first, first + count) on the context's stream: d_K
+// [count][Nd][Nd] row-major, d_F [count][n_rhs][Nd], either may be null
+int accumulateBoundarySides(l3k_mf* mf, int64_t first, int64_t count, double* d_K, double* d_F);
+// ... the side systems of every attached term on the elements [first, first + count) summed into the CSR values / rhs (the
+// standalone route of l3k_bnd_assemble_global); entries outside the graph are added to *n_missing
+int assembleGlobalBoundarySides(l3k_mf* mf, int64_t first, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind, double* d_values,
+                                double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes, int64_t* n_missing);
 #endif

@@ -587,7 +587,10 @@ struct Diffusion2DVar
     X(::l3k::kernels::Adiabatic2D, 1, 2, 2)                                                                            \
     X(::l3k::kernels::Adiabatic2D, 2, 3, 2)                                                                            \
     X(::l3k::kernels::Adiabatic2D, 4, 5, 2)                                                                            \
-    X(::l3k::kernels::Adiabatic2D, 6, 7, 2)
+    X(::l3k::kernels::Adiabatic2D, 6, 7, 2)                                                                            \
+    X(::l3k::kernels::Robin3D, 1, 2, 1)                                                                                \
+    X(::l3k::kernels::Adiabatic3D, 1, 2, 1)                                                                            \
+    X(::l3k::kernels::Robin3D, 6, 7, 1)
 
 // (functor, order p, nq); computeNormL2 doubles the quadrature orders: nq = 2p+1 for the default options
 #define L3K_FOR_EACH_RESIDUAL_INSTANCE(X)                                                                              \

@@ -484,6 +484,30 @@ class BoundaryTerm:
                                            _ptr(diag_ghost), _ptr(rhs_ghost), ldrg))
         return diag, rhs
 
+    def local_assemble(self, first=0, count=None, want_K=True, want_F=True):
+        """assembleLocalSystem on the sides [first, first+count) of the list, in the order the term was given
+        (l3k_bnd_local_assemble; hexes): the local system of the whole element from the side quadrature.  Returns
+        (K [count, Nd, Nd] row-major, bitwise symmetric, F [count, n_rhs, Nd])."""
+        import torch
+        count = self.n_faces - first if count is None else count
+        Nd = (self.mesh.part.order + 1) ** 3 * self.info["n_unknowns"]
+        n = max(count, 0)
+        K = torch.empty((n, Nd, Nd), dtype=torch.float64, device="cuda") if want_K else None
+        F = torch.empty((n, self.n_rhs, Nd), dtype=torch.float64, device="cuda") if want_F else None
+        check(capi.load().l3k_bnd_local_assemble(self._h, first, count, _ptr(K), _ptr(F)))
+        return K, F
+
+    def assemble_global(self, row_ptr, col_ind, values, rhs=None, first=0, count=None, skip_dirichlet=False, workspace_bytes=0):
+        """The boundary overload of assembleGlobalSystem for the sides [first, first+count) of the list
+        (l3k_bnd_assemble_global; hexes): side systems formed and summed into `values` (over the CSR graph row_ptr int64 /
+        col_ind int32) and `rhs` [n_rhs, n_local_dofs]; additive.  Returns the number of entries outside the graph."""
+        count = self.n_faces - first if count is None else count
+        missing = C.c_int64(0)
+        check(capi.load().l3k_bnd_assemble_global(self._h, first, count, _ptr(row_ptr), _ptr(col_ind), _ptr(values), _ptr(rhs),
+                                                  0 if rhs is None else rhs.stride(0) if rhs.dim() == 2 else rhs.numel(),
+                                                  int(skip_dirichlet), workspace_bytes, C.byref(missing)))
+        return missing.value
+
 
 def integrate(mesh, residual_id, fields=None, kernel_params=None, asm_opts=(1, 0, 0), time=0.0, square=False,
               face_elem=None, face_side=None):
@@ -636,6 +660,12 @@ class MatrixFreeSystem:
         """Registers a BoundaryTerm: apply / apply_elems / diag_rhs include it from now on."""
         check(capi.load().l3k_mf_attach_boundary(self._h, term._h))
         self._boundary_terms.append(term)  # keeps the term alive as long as the system
+
+    def assemble_boundary(self, on=True):
+        """With on, local_assemble, assemble_global, condense_local, condense_global and recover_internal work on
+        K_e + sum K_s, F_e + sum F_s over the attached sides of each element (l3k_mf_assemble_boundary; hexes).  Off by
+        default: the assembled and condensed calls then ignore the attached terms."""
+        check(capi.load().l3k_mf_assemble_boundary(self._h, int(bool(on))))
 
     # post::FieldAccess: SoA (n_fields, n_local_nodes) device tensor, kept alive here
     def set_fields(self, fields):
