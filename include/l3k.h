@@ -529,6 +529,54 @@ int l3k_pmg_apply(l3k_pmg* M, const double* d_r, double* d_z); /* r and z must n
 int l3k_pmg_destroy(l3k_pmg* M);
 int l3k_pcg_solve_pmg(l3k_mf* mf, const double* d_b, double* d_x, l3k_pmg* M, const l3k_cg_opts* opts, l3k_cg_result* result);
 
+/* ---- p-multigrid on partitioned meshes: the transfer of one level pair, ghost rows included -------------------------------
+ * l3k_pmg_* above serves single-rank systems.  A partitioned host keeps its hierarchy itself, as it keeps the Chebyshev iteration
+ * (l3k_cheb_first / _step above): the smoothers are those pieces around l3k_mf_apply_dist, the exchanges are l3k_halo_import /
+ * _export_add, and what is left -- the transfer between two orders of this rank's elements and the masked residual -- is here.
+ *
+ * l3k_transfer_create stands beside the pair set-up of l3k_pmg_create and validates the pair as it does (same dim, element count
+ * and dofs_per_node, coarse order below the fine one, element map in range and a permutation, bitwise equal elem_verts; the same
+ * message texts, with this call's name).  The meshes may have ghost nodes; both must live on ctx, and d_elem_map (device, NULL =
+ * identity) and the meshes are kept, not copied: the caller keeps them alive.
+ *
+ * A vector of a level is two buffers, owned rows [n_owned_dofs] and ghost rows [n_ghost_dofs]; local dof < n_owned_dofs selects
+ * the buffer, as in l3k_mf_apply_elems.  Ownership: a fine node is handled by the rank that owns it, there by the lowest local fine
+ * element that contains it; ghost fine nodes have no handler on this rank.  The owned fine nodes of all ranks are the global fine
+ * nodes once each, so the ranks' rows together are one P with one row per global fine dof -- the P of l3k_pmg_prolong on the
+ * whole mesh up to the order of the sums (the interpolated value at a shared node does not depend on the element that computes
+ * it: the end rows of l3k_interp_1d are unit vectors).  Creation counts the owned fine nodes that no local element contains
+ * (one more word in the validation's readback) and refuses if there are any.
+ *   l3k_transfer_prolong:  (beside l3k_pmg_prolong) x_f <- P x_c (add = 0) or x_f += P x_c; reads coarse owned rows d_xc and coarse
+ *                          ghost rows d_xc_ghost -- the caller has run l3k_halo_import of d_xc on the coarse level -- and writes
+ *                          OWNED fine rows only, one writer per dof, plain stores.  Fine ghost rows do not exist here: the next
+ *                          apply imports them itself.  d_frozen (NULL: none): owned fine rows with d_frozen[row] == 0, tested on
+ *                          the bits, are left alone (the smoother's minv).  Dirichlet dofs as in l3k_pmg_prolong.
+ *   l3k_transfer_restrict: (beside l3k_pmg_restrict) r_c <- P^T r_f; reads OWNED fine rows only (no exchange on the fine level),
+ *                          zeroes d_rc and d_rc_ghost and accumulates into both; the caller then runs l3k_halo_export_add of
+ *                          d_rc_ghost into d_rc on the coarse level.  Deterministic mode as in l3k_pmg_restrict (colour by colour
+ *                          on the coarse mesh's colouring); reproducibility ACROSS ranks is not claimed -- it depends on the add
+ *                          order of the halo.
+ * On meshes without ghost nodes the ghost pointers may be NULL and the prolongation equals l3k_pmg_prolong bit for bit.  A rank
+ * with no elements creates the object and its calls return 0 (pointers to vectors of length 0 may be NULL).
+ *
+ * l3k_pmg_residual: d = r - az on the rows with minv != 0 (tested on the bits), 0 on the others: the masked residual of the cycle
+ * of l3k_pmg_apply (az holds A z) for hosts that run the cycle themselves; n rows, all four arrays required.
+ *
+ * Errors (-1, the message names the call): null arguments (owned pointers of a non-empty vector included), meshes on another
+ * context, a failed pair validation, owned fine nodes without a local element, NULL ghost pointers on a coarse mesh with ghosts. */
+typedef struct l3k_transfer l3k_transfer;
+typedef struct
+{
+    int     order_fine, order_coarse;
+    int64_t n_owned_dofs_fine, n_ghost_dofs_fine, n_owned_dofs_coarse, n_ghost_dofs_coarse;
+} l3k_transfer_info;
+int l3k_transfer_create(l3k_ctx* ctx, l3k_mesh* mesh_fine, l3k_mesh* mesh_coarse, const int64_t* d_elem_map, l3k_transfer** out);
+int l3k_transfer_info_get(const l3k_transfer* T, l3k_transfer_info* out);
+int l3k_transfer_prolong(l3k_transfer* T, const double* d_xc, const double* d_xc_ghost, double* d_xf, int add, const double* d_frozen);
+int l3k_transfer_restrict(l3k_transfer* T, const double* d_rf, double* d_rc, double* d_rc_ghost);
+int l3k_transfer_destroy(l3k_transfer* T);
+int l3k_pmg_residual(l3k_ctx* ctx, double* d_d, const double* d_r, const double* d_az, const double* d_minv, int64_t n);
+
 /* ---- device CSR operator: the assembled and the condensed system in front of the solver -----------------------------------
  * A square CSR matrix in the format l3k_assembled_scatter, l3k_assemble_global and l3k_condense_global fill: d_row_ptr int64
  * [n + 1], d_col_ind int32 strictly ascending within a row, d_values double; single rank, rows and columns in the local dofs.

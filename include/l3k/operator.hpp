@@ -11,6 +11,7 @@
 //       .apply(halo, X, Y, ...)     ~ applyImpl of a partitioned system, exchange included    :1020-1140
 //       .scatterLocalSystems(...)   ~ scatterLocalSystem / assembleGlobalSystem             algsys/ScatterLocalSystem.hpp:24-54
 //   l3k::Halo                    ~ comm::ImportExportContext + comm::Import / comm::Export  comm/ImportExport.hpp:29-72,130-215
+//   l3k::Transfer                ~ (no counterpart: the p-multigrid transfer of a partitioned mesh, next to l3k_pmg_*)
 //   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
 //   l3k::computeIntegral / computeNormL2 ~ post/Integral.hpp:113-128, post/NormL2.hpp:31-62 (one rank)
@@ -214,6 +215,47 @@ public:
 private:
     l3k_halo* m_halo{};
 };
+
+// The inter-order transfer of one level pair of a mesh that may be partitioned (l3k_transfer_*): the p-multigrid transfer for hosts
+// that keep the hierarchy of a partitioned run themselves.  d_elem_map: device, nullptr = identity; it and the meshes must outlive
+// the object.  A vector of a level is its owned rows plus its ghost rows (Halo::importGhosts before prolong on the coarse level,
+// Halo::exportAdd of the ghost rows after restrict); the ghost pointers may be null on meshes without ghosts.
+class Transfer
+{
+public:
+    Transfer(Context& ctx, const DeviceMesh& fine, const DeviceMesh& coarse, const int64_t* d_elem_map = nullptr)
+    {
+        check(l3k_transfer_create(ctx.get(), fine.get(), coarse.get(), d_elem_map, &m_transfer));
+    }
+    Transfer(const Transfer&)            = delete;
+    Transfer& operator=(const Transfer&) = delete;
+    ~Transfer() { l3k_transfer_destroy(m_transfer); }
+    l3k_transfer_info info() const
+    {
+        l3k_transfer_info i{};
+        check(l3k_transfer_info_get(m_transfer, &i));
+        return i;
+    }
+    // x_f <- P x_c (add: x_f += P x_c) on the owned fine rows; d_frozen: owned fine rows with 0 there are left alone
+    void prolong(const double* d_xc, const double* d_xc_ghost, double* d_xf, bool add = false, const double* d_frozen = nullptr) const
+    {
+        check(l3k_transfer_prolong(m_transfer, d_xc, d_xc_ghost, d_xf, add ? 1 : 0, d_frozen));
+    }
+    // r_c, r_c_ghost <- this rank's share of P^T r_f
+    void restrict(const double* d_rf, double* d_rc, double* d_rc_ghost) const
+    {
+        check(l3k_transfer_restrict(m_transfer, d_rf, d_rc, d_rc_ghost));
+    }
+    l3k_transfer* get() const { return m_transfer; }
+
+private:
+    l3k_transfer* m_transfer{};
+};
+// d = r - az on the rows with minv != 0, 0 on the others: the masked residual of the p-multigrid cycle (l3k_pmg_residual)
+inline void pmgResidual(Context& ctx, double* d_d, const double* d_r, const double* d_az, const double* d_minv, int64_t n)
+{
+    check(l3k_pmg_residual(ctx.get(), d_d, d_r, d_az, d_minv, n));
+}
 
 // A boundary equation kernel on a list of element sides (the reference's assembleProblem(kernel, boundary_ids))
 class BoundaryTerm

@@ -54,6 +54,12 @@ class PmgInfo(C.Structure):
     _fields_ = [("n_levels", C.c_int), ("order", C.c_int * 8), ("n_dofs", C.c_int64 * 8), ("applies_per_cycle", C.c_int * 8)]
 
 
+class TransferInfo(C.Structure):
+    """l3k_transfer_info: orders and owned / ghost dof counts of the two levels of a transfer"""
+    _fields_ = [("order_fine", C.c_int), ("order_coarse", C.c_int), ("n_owned_dofs_fine", C.c_int64),
+                ("n_ghost_dofs_fine", C.c_int64), ("n_owned_dofs_coarse", C.c_int64), ("n_ghost_dofs_coarse", C.c_int64)]
+
+
 class CsrInfo(C.Structure):
     """l3k_csr_info: what the validation pass of l3k_csr_create gathered"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
@@ -228,6 +234,12 @@ SIGNATURES = {
     "l3k_pmg_apply": (C.c_int, [_vp, _vp, _vp]),
     "l3k_pmg_destroy": (C.c_int, [_vp]),
     "l3k_pcg_solve_pmg": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_transfer_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "l3k_transfer_info_get": (C.c_int, [_vp, C.POINTER(TransferInfo)]),
+    "l3k_transfer_prolong": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "l3k_transfer_restrict": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "l3k_transfer_destroy": (C.c_int, [_vp]),
+    "l3k_pmg_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "l3k_csr_create": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "l3k_csr_info_get": (C.c_int, [_vp, C.POINTER(CsrInfo)]),
     "l3k_csr_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),

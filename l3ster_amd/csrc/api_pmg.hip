@@ -1,5 +1,6 @@
 // api_pmg.hip -- the p-multigrid preconditioner of libl3k.so (include/l3k.h: l3k_pmg_*): the level pairs with their ownership tables,
-// the inter-order transfer launches (device/transfer.hpp), the symmetric V-cycle on the Chebyshev smoothers and the PCG entry point.
+// the inter-order transfer launches (device/transfer.hpp), the symmetric V-cycle on the Chebyshev smoothers and the PCG entry point;
+// and the standalone transfer of one level pair of a partitioned mesh (l3k_transfer_*), whose hierarchy lives above the ABI.
 #include "reduce.hpp"
 #include "solver.hpp"
 
@@ -40,16 +41,9 @@ inline int vecGrid(int64_t n)
 }
 } // namespace
 
-// one level of the hierarchy and, from level 1 on, the pair it forms with the level above it (the finer one)
-struct PmgLevel
+// a level pair: what the transfers between a fine and a coarse mesh need beyond the meshes
+struct TransferPair
 {
-    l3k_mf*          mf;
-    l3k_cheb*        smoother;
-    LinOp            op;
-    int64_t          n, ld;
-    DevBuf< double > work; // r | z | d | e | w | az (ld apart); level 0 takes r and z from the caller and holds d | e | w | az only
-    double *         r, *z, *d, *e, *w, *az;
-    // the pair (this level = coarse, the previous one = fine)
     const int64_t*     elem_map = nullptr; // the caller's
     DevBuf< int32_t >  owner;              // [fine nodes]
     DevBuf< double >   tab_p, tab_r;       // sweep weights of the prolongation [nc][nf] and of the restriction [nf][nc]
@@ -59,11 +53,30 @@ struct PmgLevel
     DevBuf< int64_t >      det_elems;
     std::vector< int64_t > det_ptr;
 };
+// one level of the hierarchy and, from level 1 on, the pair it forms with the level above it (the finer one)
+struct PmgLevel
+{
+    l3k_mf*          mf;
+    l3k_cheb*        smoother;
+    LinOp            op;
+    int64_t          n, ld;
+    DevBuf< double > work; // r | z | d | e | w | az (ld apart); level 0 takes r and z from the caller and holds d | e | w | az only
+    double *         r, *z, *d, *e, *w, *az;
+    TransferPair     pair; // (this level = coarse, the previous one = fine)
+};
 struct l3k_pmg
 {
     l3k_ctx*                ctx;
     std::vector< PmgLevel > levels;
     l3k_pmg_info            info;
+};
+// l3k_transfer_*: one pair on its own, ghost rows included
+struct l3k_transfer
+{
+    l3k_ctx*          ctx;
+    l3k_mesh *        fine, *coarse;
+    TransferPair      pair;
+    l3k_transfer_info info;
 };
 
 namespace
@@ -73,17 +86,21 @@ unsigned transferGrid(const l3k_ctx* ctx, int64_t count)
 {
     return stridedGrid(ctx, count);
 }
-l3k::dev::TransferArgs pairArgs(const PmgLevel& fine, const PmgLevel& coarse)
+l3k::dev::TransferGhostArgs pairArgs(const l3k_mesh* mf, const l3k_mesh* mc, const TransferPair& pair)
 {
-    const l3k_mesh *       mf = fine.mf->mesh, *mc = coarse.mf->mesh;
-    l3k::dev::TransferArgs a{};
-    a.dim = mf->dim, a.nf = mf->order + 1, a.nc = mc->order + 1, a.U = mf->dofs_per_node, a.group = coarse.group;
+    l3k::dev::TransferGhostArgs a{};
+    a.dim = mf->dim, a.nf = mf->order + 1, a.nc = mc->order + 1, a.U = mf->dofs_per_node, a.group = pair.group;
     a.elem_begin = 0, a.elem_count = mf->n_elems;
-    a.elem_list = nullptr, a.elem_map = coarse.elem_map;
+    a.elem_list = nullptr, a.elem_map = pair.elem_map;
     a.nodes_f = mf->elem_nodes.ptr, a.nodes_c = mc->elem_nodes.ptr;
     a.dirichlet_f = mf->dirichlet.ptr, a.dirichlet_c = mc->dirichlet.ptr;
-    a.owner = coarse.owner.ptr;
+    a.owner = pair.owner.ptr;
+    a.n_owned_dofs_f = mf->nOwnedDofs(), a.n_owned_dofs_c = mc->nOwnedDofs();
     return a;
+}
+l3k::dev::TransferArgs pairArgs(const PmgLevel& fine, const PmgLevel& coarse)
+{
+    return pairArgs(fine.mf->mesh, coarse.mf->mesh, coarse.pair);
 }
 // x_f <- P x_c or x_f += P x_c; frozen: fine rows to leave alone (nullptr: none)
 int launchProlong(l3k_pmg* M, int coarse_level, const double* d_xc, double* d_xf, int add, const double* frozen)
@@ -92,11 +109,34 @@ int launchProlong(l3k_pmg* M, int coarse_level, const double* d_xc, double* d_xf
     auto            a = pairArgs(fine, coarse);
     if (a.elem_count == 0)
         return 0;
-    a.table = coarse.tab_p.ptr, a.frozen = frozen, a.src = d_xc, a.dst = d_xf, a.add = add;
+    a.table = coarse.pair.tab_p.ptr, a.frozen = frozen, a.src = d_xc, a.dst = d_xf, a.add = add;
     return l3k::dev::launchKernel("transferKernel<prolong>", l3k::dev::transferKernel< false >, dim3(transferGrid(M->ctx, a.elem_count)),
-                                  dim3(l3k::dev::transfer_threads), coarse.lds, M->ctx->stream, a);
+                                  dim3(l3k::dev::transfer_threads), coarse.pair.lds, M->ctx->stream, a);
 }
-// r_c <- P^T r_f (r_c zeroed here); deterministic mode: one launch per colour of the coarse mesh
+// The restriction's launches over the elements of `a` (the destination is zeroed by the caller); deterministic mode: one launch
+// per colour of the coarse mesh.  what: "p-multigrid hierarchy" / "transfer" for the message
+template < typename Args, typename Launch >
+int restrictLaunches(const l3k_ctx* ctx, const TransferPair& pair, Args a, const char* what, Launch&& launch)
+{
+    if (!ctx->deterministic)
+        return launch(a);
+    if (pair.det_ptr.empty())
+    {
+        setError("deterministic mode was enabled after this %s was created: create it with the mode on", what);
+        return -1;
+    }
+    a.elem_list = pair.det_elems.ptr;
+    for (size_t c = 0; c + 1 < pair.det_ptr.size(); ++c)
+    {
+        a.elem_begin = pair.det_ptr[c];
+        a.elem_count = pair.det_ptr[c + 1] - pair.det_ptr[c];
+        if (a.elem_count > 0)
+            if (int rc = launch(a))
+                return rc;
+    }
+    return 0;
+}
+// r_c <- P^T r_f (r_c zeroed here)
 int launchRestrict(l3k_pmg* M, int coarse_level, const double* d_rf, double* d_rc)
 {
     const PmgLevel &fine = M->levels[coarse_level - 1], &coarse = M->levels[coarse_level];
@@ -104,92 +144,107 @@ int launchRestrict(l3k_pmg* M, int coarse_level, const double* d_rf, double* d_r
     L3K_HIP(hipMemsetAsync(d_rc, 0, size_t(coarse.n) * sizeof(double), M->ctx->stream));
     if (a.elem_count == 0)
         return 0;
-    a.table = coarse.tab_r.ptr, a.frozen = nullptr, a.src = d_rf, a.dst = d_rc, a.add = 1;
-    const auto launch = [&](const l3k::dev::TransferArgs& r) {
+    a.table = coarse.pair.tab_r.ptr, a.frozen = nullptr, a.src = d_rf, a.dst = d_rc, a.add = 1;
+    return restrictLaunches(M->ctx, coarse.pair, a, "p-multigrid hierarchy", [&](const l3k::dev::TransferArgs& r) {
         return l3k::dev::launchKernel("transferKernel<restrict>", l3k::dev::transferKernel< true >, dim3(transferGrid(M->ctx, r.elem_count)),
-                                      dim3(l3k::dev::transfer_threads), coarse.lds, M->ctx->stream, r);
-    };
-    if (!M->ctx->deterministic)
-        return launch(a);
-    if (coarse.det_ptr.empty())
-    {
-        setError("deterministic mode was enabled after this p-multigrid hierarchy was created: create it with the mode on");
-        return -1;
-    }
-    a.elem_list = coarse.det_elems.ptr;
-    for (size_t c = 0; c + 1 < coarse.det_ptr.size(); ++c)
-    {
-        a.elem_begin = coarse.det_ptr[c];
-        a.elem_count = coarse.det_ptr[c + 1] - coarse.det_ptr[c];
-        if (a.elem_count > 0)
-            if (int rc = launch(a))
-                return rc;
-    }
-    return 0;
+                                      dim3(l3k::dev::transfer_threads), coarse.pair.lds, M->ctx->stream, r);
+    });
 }
-// The pair (levels[l - 1], levels[l]): validation (one kernel, one readback), ownership table, sweep tables, deterministic plan
-int buildPair(l3k_pmg* M, int l)
+// The names a pair's messages use: l3k_pmg_create speaks of its levels, l3k_transfer_create of its two meshes
+struct PairNames
 {
-    PmgLevel &      fine = M->levels[l - 1], &coarse = M->levels[l];
-    const l3k_mesh *mf = fine.mf->mesh, *mc = coarse.mf->mesh;
-    l3k_ctx*        ctx = M->ctx;
-    hipStream_t     st  = ctx->stream;
+    std::string call, both, fine, coarse; // "l3k_pmg_create", "levels 0 and 1", "level 0", "level 1"
+};
+// A level pair: validation (one kernel, one readback), ownership table, sweep tables, deterministic plan.  `partitioned` (the
+// standalone transfer): the ownership table covers owned and ghost fine nodes and only owned ones enter it; the readback of the
+// validation then carries a second word, the number of owned fine nodes that no local element contains, which must be 0
+int buildPair(l3k_ctx* ctx, const PairNames& nm, const l3k_mesh* mf, const l3k_mesh* mc, TransferPair& coarse, bool partitioned)
+{
+    hipStream_t st = ctx->stream;
     if (mf->dim != mc->dim || mf->n_elems != mc->n_elems || mf->dofs_per_node != mc->dofs_per_node)
     {
-        setError("l3k_pmg_create: levels %d and %d are not one mesh at two orders: dim %d / %d, %lld / %lld elements, %d / %d dofs per "
-                 "node", l - 1, l, mf->dim, mc->dim, (long long)mf->n_elems, (long long)mc->n_elems, mf->dofs_per_node, mc->dofs_per_node);
+        setError("%s: %s are not one mesh at two orders: dim %d / %d, %lld / %lld elements, %d / %d dofs per "
+                 "node", nm.call.c_str(), nm.both.c_str(), mf->dim, mc->dim, (long long)mf->n_elems, (long long)mc->n_elems,
+                 mf->dofs_per_node, mc->dofs_per_node);
         return -1;
     }
     if (!(mc->order < mf->order))
     {
-        setError("l3k_pmg_create: the orders must decrease strictly from level to level; level %d has order %d, level %d order %d", l - 1,
-                 mf->order, l, mc->order);
+        setError("%s: the orders must decrease strictly from level to level; %s has order %d, %s order %d", nm.call.c_str(),
+                 nm.fine.c_str(), mf->order, nm.coarse.c_str(), mc->order);
         return -1;
     }
     if (mf->order > 8 || mf->n_elems >= 0x7f7f7f7f) // (the ownership table holds element indices in 32 bits below its fill value)
     {
-        setError("l3k_pmg_create: orders up to 8 and fewer than 2^31 - 2^24 elements");
+        setError("%s: orders up to 8 and fewer than 2^31 - 2^24 elements", nm.call.c_str());
         return -1;
     }
     const int64_t n_elems = mf->n_elems;
     const int     words   = (1 << mf->dim) * 3;
+    const int     nf = mf->order + 1, nc = mc->order + 1;
+    const int     Nf = l3k::dev::transferPow(nf, mf->dim);
+    if (partitioned)
+    {
+        // ownership of the OWNED fine nodes, ahead of the validation (it reads the fine node table only, not the element map), so
+        // that its count of nodes without a handler travels in the validation's readback
+        const int64_t n_nodes_f = mf->n_owned_nodes + mf->n_ghost_nodes;
+        if (int rc = coarse.owner.alloc(size_t(std::max< int64_t >(n_nodes_f, 1))))
+            return rc;
+        L3K_HIP(hipMemsetAsync(coarse.owner.ptr, 0x7f, coarse.owner.n * sizeof(int32_t), st));
+        if (n_elems > 0)
+            hipLaunchKernelGGL(l3k::dev::transferOwnerOwnedKernel, dim3(gridFor(n_elems * Nf)), dim3(256), 0, st, mf->elem_nodes.ptr,
+                               n_elems * Nf, Nf, mf->n_owned_nodes, coarse.owner.ptr);
+        L3K_HIP(hipGetLastError());
+    }
     {
         DevBuf< unsigned >           hit;
-        DevBuf< unsigned long long > flag;
+        DevBuf< unsigned long long > flag; // [0] the validation's word, [1] (partitioned) owned fine nodes without a handler
         if (int rc = hit.alloc(size_t(std::max< int64_t >(n_elems, 1))))
             return rc;
-        if (int rc = flag.alloc(1))
+        if (int rc = flag.alloc(2))
             return rc;
         L3K_HIP(hipMemsetAsync(hit.ptr, 0xff, hit.n * sizeof(unsigned), st));
         L3K_HIP(hipMemsetAsync(flag.ptr, 0xff, sizeof(unsigned long long), st));
+        L3K_HIP(hipMemsetAsync(flag.ptr + 1, 0, sizeof(unsigned long long), st));
         if (n_elems > 0)
             hipLaunchKernelGGL(l3k::dev::transferCheckPairKernel, dim3(gridFor(n_elems)), dim3(256), 0, st, n_elems, coarse.elem_map,
                                reinterpret_cast< const unsigned long long* >(mf->elem_verts.ptr),
                                reinterpret_cast< const unsigned long long* >(mc->elem_verts.ptr), words, hit.ptr, flag.ptr);
         L3K_HIP(hipGetLastError());
-        unsigned long long f = 0;
-        L3K_HIP(hipMemcpyAsync(&f, flag.ptr, sizeof f, hipMemcpyDeviceToHost, st)); // (the one readback of the validation)
+        if (partitioned && mf->n_owned_nodes > 0)
+            hipLaunchKernelGGL(l3k::dev::transferCountUnhandledKernel, dim3(gridFor(mf->n_owned_nodes)), dim3(256), 0, st, coarse.owner.ptr,
+                               mf->n_owned_nodes, int32_t(0x7f7f7f7f), flag.ptr + 1);
+        L3K_HIP(hipGetLastError());
+        unsigned long long f[2] = {0, 0};
+        L3K_HIP(hipMemcpyAsync(f, flag.ptr, sizeof f, hipMemcpyDeviceToHost, st)); // (the one readback of the validation)
         L3K_HIP(hipStreamSynchronize(st));
-        if (f != ~0ull)
+        if (f[0] != ~0ull)
         {
             static const char* const why[] = {"", "is mapped outside the coarse mesh", "is mapped to a coarse element that an earlier one "
                                               "already took (the element map is not a permutation)",
                                               "and its coarse partner have different vertices (elem_verts must be bitwise equal)"};
-            setError("l3k_pmg_create: levels %d and %d: fine element %llu %s", l - 1, l, f / 4, why[f % 4]);
+            setError("%s: %s: fine element %llu %s", nm.call.c_str(), nm.both.c_str(), f[0] / 4, why[f[0] % 4]);
+            return -1;
+        }
+        if (f[1] != 0)
+        {
+            setError("%s: %llu owned nodes of %s lie in no element of this rank: nobody would compute their rows of P (a node is owned "
+                     "by the lowest part that touches it, so a partitioned mesh has none)", nm.call.c_str(), f[1], nm.fine.c_str());
             return -1;
         }
     }
-    // ownership of the fine nodes
-    const int     nf = mf->order + 1, nc = mc->order + 1;
-    const int     Nf = l3k::dev::transferPow(nf, mf->dim);
-    const int64_t n_nodes_f = mf->n_owned_nodes;
-    if (int rc = coarse.owner.alloc(size_t(std::max< int64_t >(n_nodes_f, 1))))
-        return rc;
-    L3K_HIP(hipMemsetAsync(coarse.owner.ptr, 0x7f, coarse.owner.n * sizeof(int32_t), st));
-    if (n_elems > 0)
-        hipLaunchKernelGGL(l3k::dev::transferOwnerKernel, dim3(gridFor(n_elems * Nf)), dim3(256), 0, st, mf->elem_nodes.ptr, n_elems * Nf, Nf,
-                           coarse.owner.ptr);
-    L3K_HIP(hipGetLastError());
+    if (!partitioned)
+    {
+        // ownership of the fine nodes
+        const int64_t n_nodes_f = mf->n_owned_nodes;
+        if (int rc = coarse.owner.alloc(size_t(std::max< int64_t >(n_nodes_f, 1))))
+            return rc;
+        L3K_HIP(hipMemsetAsync(coarse.owner.ptr, 0x7f, coarse.owner.n * sizeof(int32_t), st));
+        if (n_elems > 0)
+            hipLaunchKernelGGL(l3k::dev::transferOwnerKernel, dim3(gridFor(n_elems * Nf)), dim3(256), 0, st, mf->elem_nodes.ptr, n_elems * Nf,
+                               Nf, coarse.owner.ptr);
+        L3K_HIP(hipGetLastError());
+    }
     // sweep weights: restriction W[jf][ic] = l_ic(x_jf) is the table of l3k_interp_1d, the prolongation takes its transpose
     const auto            tr = l3k::host::interp1d(mc->order, mf->order);
     std::vector< double > tp(tr.size());
@@ -210,7 +265,8 @@ int buildPair(l3k_pmg* M, int l)
     {
         if (!mc->det_built)
         {
-            setError("l3k_pmg_create: deterministic mode was enabled after the mesh of level %d was created: create the mesh with the mode on", l);
+            setError("%s: deterministic mode was enabled after the mesh of %s was created: create the mesh with the mode on",
+                     nm.call.c_str(), nm.coarse.c_str());
             return -1;
         }
         std::vector< int64_t > map(static_cast< size_t >(n_elems)), order(static_cast< size_t >(n_elems));
@@ -239,6 +295,12 @@ int buildPair(l3k_pmg* M, int l)
         L3K_HIP(hipStreamSynchronize(st));
     }
     return 0;
+}
+int buildPair(l3k_pmg* M, int l)
+{
+    const auto      level = [](int i) { return "level " + std::to_string(i); };
+    const PairNames nm{"l3k_pmg_create", "levels " + std::to_string(l - 1) + " and " + std::to_string(l), level(l - 1), level(l)};
+    return buildPair(M->ctx, nm, M->levels[l - 1].mf->mesh, M->levels[l].mf->mesh, M->levels[l].pair, false);
 }
 int residual(l3k_pmg* M, PmgLevel& L, const double* r, const double* z)
 {
@@ -332,7 +394,7 @@ int l3k_pmg_create(l3k_ctx* ctx, int n_levels, const l3k_pmg_level* levels, l3k_
         L.op        = l3k::solver::mfOp(L.mf);
         L.n         = L.op.n;
         L.ld        = (L.n + 3) / 4 * 4;
-        L.elem_map  = l ? levels[l].d_elem_map : nullptr;
+        L.pair.elem_map = l ? levels[l].d_elem_map : nullptr;
         if (int rc = L.work.alloc(size_t((l ? 6 : 4) * L.ld)))
             return rc;
         L.r = l ? L.work.ptr : nullptr, L.z = l ? L.r + L.ld : nullptr;
@@ -427,5 +489,111 @@ int l3k_pcg_solve_pmg(l3k_mf* mf, const double* d_b, double* d_x, l3k_pmg* M, co
                         return l3k::solver::dotInto(M->ctx, r, z, M->levels[0].n, s, 2);
                     }};
     return l3k::solver::pcgSolvePrecond(l3k::solver::mfOp(mf), "l3k_pcg_solve_pmg", d_b, d_x, P, opts, result);
+}
+int l3k_pmg_residual(l3k_ctx* ctx, double* d_d, const double* d_r, const double* d_az, const double* d_minv, int64_t n)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_d || !d_r || !d_az || !d_minv)))
+    {
+        setError("l3k_pmg_residual: null argument");
+        return -1;
+    }
+    if (n == 0)
+        return 0;
+    L3K_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(pmgResidualKernel, dim3(vecGrid(n)), dim3(cg_threads), 0, ctx->stream, d_d, d_r, d_az, d_minv, n);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
+int l3k_transfer_create(l3k_ctx* ctx, l3k_mesh* mesh_fine, l3k_mesh* mesh_coarse, const int64_t* d_elem_map, l3k_transfer** out)
+{
+    if (!ctx || !mesh_fine || !mesh_coarse || !out)
+    {
+        setError("l3k_transfer_create: null argument");
+        return -1;
+    }
+    if (mesh_fine->ctx != ctx || mesh_coarse->ctx != ctx)
+    {
+        setError("l3k_transfer_create: %s lives on another context", mesh_fine->ctx != ctx ? "the fine mesh" : "the coarse mesh");
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(ctx->device));
+    auto T    = std::make_unique< l3k_transfer >();
+    T->ctx    = ctx;
+    T->fine   = mesh_fine;
+    T->coarse = mesh_coarse;
+    T->pair.elem_map = d_elem_map;
+    const PairNames nm{"l3k_transfer_create", "the fine and the coarse mesh", "the fine mesh", "the coarse mesh"};
+    if (int rc = buildPair(ctx, nm, mesh_fine, mesh_coarse, T->pair, true))
+        return rc;
+    T->info = l3k_transfer_info{mesh_fine->order,
+                                mesh_coarse->order,
+                                mesh_fine->nOwnedDofs(),
+                                mesh_fine->nLocalDofs() - mesh_fine->nOwnedDofs(),
+                                mesh_coarse->nOwnedDofs(),
+                                mesh_coarse->nLocalDofs() - mesh_coarse->nOwnedDofs()};
+    *out    = T.release();
+    return 0;
+}
+int l3k_transfer_info_get(const l3k_transfer* T, l3k_transfer_info* out)
+{
+    if (!T || !out)
+    {
+        setError("l3k_transfer_info_get: null argument");
+        return -1;
+    }
+    *out = T->info;
+    return 0;
+}
+int l3k_transfer_prolong(l3k_transfer* T, const double* d_xc, const double* d_xc_ghost, double* d_xf, int add, const double* d_frozen)
+{
+    if (!T || (T->info.n_owned_dofs_coarse > 0 && !d_xc) || (T->info.n_owned_dofs_fine > 0 && !d_xf))
+    {
+        setError("l3k_transfer_prolong: null argument");
+        return -1;
+    }
+    if (T->info.n_ghost_dofs_coarse > 0 && !d_xc_ghost)
+    {
+        setError("l3k_transfer_prolong: the coarse mesh has ghost nodes: d_xc_ghost must hold their rows (l3k_halo_import), got NULL");
+        return -1;
+    }
+    auto a = pairArgs(T->fine, T->coarse, T->pair);
+    if (a.elem_count == 0)
+        return 0;
+    L3K_HIP(hipSetDevice(T->ctx->device));
+    a.table = T->pair.tab_p.ptr, a.frozen = d_frozen, a.src = d_xc, a.src_ghost = d_xc_ghost, a.dst = d_xf, a.add = add;
+    return l3k::dev::launchKernel("transferKernel<prolong, ghost>", l3k::dev::transferKernel< false, true >,
+                                  dim3(transferGrid(T->ctx, a.elem_count)), dim3(l3k::dev::transfer_threads), T->pair.lds, T->ctx->stream, a);
+}
+int l3k_transfer_restrict(l3k_transfer* T, const double* d_rf, double* d_rc, double* d_rc_ghost)
+{
+    if (!T || (T->info.n_owned_dofs_fine > 0 && !d_rf) || (T->info.n_owned_dofs_coarse > 0 && !d_rc))
+    {
+        setError("l3k_transfer_restrict: null argument");
+        return -1;
+    }
+    if (T->info.n_ghost_dofs_coarse > 0 && !d_rc_ghost)
+    {
+        setError("l3k_transfer_restrict: the coarse mesh has ghost nodes: d_rc_ghost must take their rows (for l3k_halo_export_add), got NULL");
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(T->ctx->device));
+    if (T->info.n_owned_dofs_coarse > 0)
+        L3K_HIP(hipMemsetAsync(d_rc, 0, size_t(T->info.n_owned_dofs_coarse) * sizeof(double), T->ctx->stream));
+    if (T->info.n_ghost_dofs_coarse > 0)
+        L3K_HIP(hipMemsetAsync(d_rc_ghost, 0, size_t(T->info.n_ghost_dofs_coarse) * sizeof(double), T->ctx->stream));
+    auto a = pairArgs(T->fine, T->coarse, T->pair);
+    if (a.elem_count == 0)
+        return 0;
+    a.table = T->pair.tab_r.ptr, a.frozen = nullptr, a.src = d_rf, a.dst = d_rc, a.dst_ghost = d_rc_ghost, a.add = 1;
+    return restrictLaunches(T->ctx, T->pair, a, "transfer", [&](const l3k::dev::TransferGhostArgs& r) {
+        return l3k::dev::launchKernel("transferKernel<restrict, ghost>", l3k::dev::transferKernel< true, true >,
+                                      dim3(transferGrid(T->ctx, r.elem_count)), dim3(l3k::dev::transfer_threads), T->pair.lds,
+                                      T->ctx->stream, r);
+    });
+}
+int l3k_transfer_destroy(l3k_transfer* T)
+{
+    delete T;
+    return 0;
 }
 } // extern "C"

@@ -14,10 +14,19 @@
 // P is made well defined by the OWNERSHIP of the fine nodes: owner[node] = the lowest fine element that contains the node.  An
 // element writes (prolongation) or reads (restriction) only the fine nodes it owns, so P has one row per fine dof -- the values of
 // the coarse basis of the owning element at the node -- and the restriction is its exact transpose, without multiplicity weights.
+//
+// Partitioned meshes (the GHOST instantiations, behind l3k_transfer_*): a vector of a level is two buffers, owned rows and ghost
+// rows, and `local dof < n_owned_dofs` selects the buffer as in the element kernels.  Only OWNED fine nodes take part in the
+// ownership table (ghost fine nodes keep the fill value, which no element index equals, so no element handles them): the owned
+// fine nodes of all ranks are the global fine nodes once each, hence the rows of the ranks' P are the rows of the global P.  The
+// fine side therefore never addresses a ghost row; the coarse side reads (prolongation) or accumulates into (restriction) owned
+// and ghost rows, and the caller's exchange -- import before, export-add after -- completes the global product.
 #ifndef L3K_DEVICE_TRANSFER_HPP
 #define L3K_DEVICE_TRANSFER_HPP
 
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace l3k::dev
 {
@@ -39,6 +48,15 @@ struct TransferArgs
     const double*   src;
     double*         dst;
     int             add;        // prolongation: dst += P src instead of dst = P src
+};
+// ... of the GHOST instantiations (a struct of its own: the single-rank kernels keep their kernel arguments and with them their
+// code): the coarse vector's ghost rows -- read by the prolongation, accumulated into by the restriction -- and the numbers of
+// owned dofs of the two levels
+struct TransferGhostArgs : TransferArgs
+{
+    const double* src_ghost;
+    double*       dst_ghost;
+    int64_t       n_owned_dofs_f, n_owned_dofs_c; // (the fine count states the contract: every fine dof touched is below it)
 };
 
 // out[a * sa_out + i * B + b] = sum_j W[j * n_out + i] in[a * sa_in + j * B + b] for a < A, i < n_out, b < B.  B == 1 (the x sweep): the
@@ -89,9 +107,11 @@ inline size_t transferLdsBytes(int nf, int nc, int dim, int group)
     return sizeof(double) * (size_t(2) * group * transferBufDoubles(nf, dim) + size_t(nf) * nc);
 }
 
-// RESTRICT == false: dst (fine) = or += P src (coarse);  RESTRICT == true: dst (coarse) += P^T src (fine), atomically
-template < bool RESTRICT >
-__global__ __launch_bounds__(transfer_threads) void transferKernel(TransferArgs a)
+// RESTRICT == false: dst (fine) = or += P src (coarse);  RESTRICT == true: dst (coarse) += P^T src (fine), atomically.
+// GHOST: the coarse dofs >= n_owned_dofs_c live in src_ghost / dst_ghost (the fine side is the same code: an element handles
+// owned fine nodes only, the ownership table sees to it)
+template < bool RESTRICT, bool GHOST = false >
+__global__ __launch_bounds__(transfer_threads) void transferKernel(std::conditional_t< GHOST, TransferGhostArgs, TransferArgs > a)
 {
     extern __shared__ double lds[];
     const int nf = a.nf, nc = a.nc, U = a.U, dim = a.dim;
@@ -124,7 +144,12 @@ __global__ __launch_bounds__(transfer_threads) void transferKernel(TransferArgs 
                     const int64_t dof = int64_t(nc_ids[ln]) * U + c0 + c;
                     double        v   = 0.;
                     if (!(a.dirichlet_c && a.dirichlet_c[dof]))
-                        v = a.src[dof];
+                    {
+                        if constexpr (GHOST)
+                            v = dof < a.n_owned_dofs_c ? a.src[dof] : a.src_ghost[dof - a.n_owned_dofs_c];
+                        else
+                            v = a.src[dof];
+                    }
                     buf0[c * cs + (ln / nc) * sxc + ln % nc] = v;
                 }
                 __syncthreads();
@@ -193,7 +218,13 @@ __global__ __launch_bounds__(transfer_threads) void transferKernel(TransferArgs 
                     const int     c = t % g, ln = t / g;
                     const int64_t dof = int64_t(nc_ids[ln]) * U + c0 + c;
                     if (!(a.dirichlet_c && a.dirichlet_c[dof]))
-                        unsafeAtomicAdd(a.dst + dof, in[c * cs + (ln / nc) * sxc + ln % nc]);
+                    {
+                        if constexpr (GHOST)
+                            unsafeAtomicAdd(dof < a.n_owned_dofs_c ? a.dst + dof : a.dst_ghost + (dof - a.n_owned_dofs_c),
+                                            in[c * cs + (ln / nc) * sxc + ln % nc]);
+                        else
+                            unsafeAtomicAdd(a.dst + dof, in[c * cs + (ln / nc) * sxc + ln % nc]);
+                    }
                 }
                 __syncthreads();
             }
@@ -206,6 +237,28 @@ __global__ void transferOwnerKernel(const uint32_t* __restrict__ nodes_f, int64_
 {
     for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n_entries; i += int64_t(gridDim.x) * blockDim.x)
         atomicMin(owner + nodes_f[i], int32_t(i / N));
+}
+
+// ... of a partitioned mesh: only the owned nodes (< n_owned_nodes) enter; owner [owned + ghost nodes], the ghost entries keep the fill
+__global__ void transferOwnerOwnedKernel(const uint32_t* __restrict__ nodes_f, int64_t n_entries, int N, int64_t n_owned_nodes,
+                                         int32_t* __restrict__ owner)
+{
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n_entries; i += int64_t(gridDim.x) * blockDim.x)
+    {
+        const uint32_t node = nodes_f[i];
+        if (node < n_owned_nodes)
+            atomicMin(owner + node, int32_t(i / N));
+    }
+}
+// count += the owned fine nodes that no local element contains (owner still holds `fill`): rows of P nobody would compute
+__global__ void transferCountUnhandledKernel(const int32_t* __restrict__ owner, int64_t n_owned_nodes, int32_t fill,
+                                             unsigned long long* __restrict__ count)
+{
+    unsigned long long mine = 0;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n_owned_nodes; i += int64_t(gridDim.x) * blockDim.x)
+        mine += owner[i] == fill;
+    if (mine)
+        atomicAdd(count, mine);
 }
 
 // Validation of a level pair, one thread per fine element: the coarse partner lies in range, no coarse element is named twice

@@ -323,6 +323,24 @@ class NativeDistributedOperator:
         capi.check(capi.load().l3k_mf_apply_dist(self.mf._h, self.halo._h, vp(X), X.stride(0), vp(Y), Y.stride(0), X.shape[0], alpha, beta))
         return Y
 
+    def diag_rhs(self, dirichlet_vals_owned=None):
+        """DistributedOperator.diag_rhs with the library's exchange: Dirichlet values imported to the ghost rows, local diag / rhs,
+        ghost rows exported and added to their owners (diag and rhs in one exchange), Dirichlet rows finalised.
+        dirichlet_vals_owned: (n_rhs, n_owned_dofs) or None.  Returns (diag [n_owned], rhs (n_rhs, n_owned))."""
+        mf = self.mf
+        n_owned, n_ghost = mf.mesh.n_owned_dofs, mf.mesh.n_ghost_dofs
+        g_all = None
+        if dirichlet_vals_owned is not None:
+            g_all = torch.cat([dirichlet_vals_owned, self.import_ghosts(dirichlet_vals_owned)[:, :n_ghost]], dim=1).contiguous()
+        dev = "cuda" if dirichlet_vals_owned is None else dirichlet_vals_owned.device
+        both_o = torch.zeros((1 + mf.n_rhs, n_owned), dtype=torch.float64, device=dev)
+        both_g = torch.zeros((1 + mf.n_rhs, max(n_ghost, 1)), dtype=torch.float64, device=dev)
+        mf.diag_rhs(g_all, which=2, diag=both_o[0], rhs=both_o[1:], diag_ghost=both_g[0], rhs_ghost=both_g[1:], finalize=False)
+        self.export_add(both_g, both_o)
+        diag, rhs = both_o[0].contiguous(), both_o[1:].contiguous()
+        mf.dirichlet_finalize(dirichlet_vals_owned, diag, rhs)
+        return diag, rhs
+
     def timing_begin(self, n_applies):
         from . import capi
         capi.check(capi.load().l3k_halo_timing_begin(self.halo._h, n_applies))

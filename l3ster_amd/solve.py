@@ -267,6 +267,108 @@ class PMultigrid:
             pass
 
 
+def _operator_mesh(op):
+    """the DeviceMesh under a distributed operator (NativeDistributedOperator.mf, DistributedOperator.backend)"""
+    mf = getattr(op, "mf", None) or op.backend
+    return mf.mesh
+
+
+class DistributedPMultigrid:
+    """The p-multigrid preconditioner of a PARTITIONED system: the cycle of l3k_pmg_apply (include/l3k.h) run from here on the
+    exported pieces, as pcg_distributed runs the Chebyshev iteration -- the hierarchy of a partitioned run lives above the C ABI.
+    `levels`, finest first: (op, minv, smoother, elem_map) with
+      op        a NativeDistributedOperator or DistributedOperator over this rank's owned rows of the level,
+      minv      the level's inverse diagonal over its owned rows (rows with minv == 0 are frozen),
+      smoother  a dict of ChebyshevPreconditioner's options (degree, cond_est, max_power_iters, boost_factor, lambda_max) or an
+                object whose .info has lambda_max, lambda_min and degree; without lambda_max the distributed power method of
+                pcg_distributed estimates it, through `reduce`,
+      elem_map  the element of this level for each element of the level before (system.match_elements on the two parts of this
+                rank; None = identity; ignored on the first level).
+    `reduce(view)`: sums a small device tensor over the ranks in place (None: torch.distributed when initialised, else
+    nothing); pcg_distributed hands over its own.  The smoothers are l3k_cheb_first / _step around op.apply, the residual is
+    l3k_pmg_residual, the transfers are system.Transfer with the coarse level's import_ghosts before each prolongation and its
+    export_add after each restriction; the last level is its smoother alone.  Per level pair a cycle adds one coarse import and
+    one coarse export-add to the exchanges of the applies.  All vectors of all levels are allocated here."""
+
+    def __init__(self, levels, reduce=None):
+        from . import capi
+        from .system import Transfer
+        levels = [tuple(l) + (None,) * (4 - len(l)) for l in levels]
+        if len(levels) < 2:
+            raise capi.L3KError(f"DistributedPMultigrid needs at least two levels, got {len(levels)}")
+        self.levels, self.op, self.minv, self._reduce, self._coeffs = levels, levels[0][0], levels[0][1], reduce, None
+        self._ctx = _operator_mesh(self.op).ctx
+        self._vecs, self.transfers = [], [None]
+        for i, (op, minv, smoother, emap) in enumerate(levels):
+            n = _operator_mesh(op).n_owned_dofs
+            if minv is None or smoother is None or minv.numel() != n or not minv.is_contiguous():
+                raise capi.L3KError(f"DistributedPMultigrid: level {i} needs minv, a contiguous tensor over its {n} owned dofs, "
+                                    "and its smoother")
+            if _operator_mesh(op).ctx is not self._ctx:
+                raise capi.L3KError(f"DistributedPMultigrid: level {i} lives on another context")
+            names = ("d", "e", "w", "az") if i == 0 else ("r", "z", "d", "e", "w", "az")
+            self._vecs.append({k: torch.zeros(n, dtype=torch.float64, device=minv.device) for k in names})
+            if i:
+                self.transfers.append(Transfer(_operator_mesh(levels[i - 1][0]), _operator_mesh(op), emap))
+                ng = max(_operator_mesh(op).n_ghost_dofs, 1)
+                self._vecs[i]["rg"] = torch.zeros((1, ng), dtype=torch.float64, device=minv.device)
+
+    def setup(self, reduce=None):
+        """The Chebyshev coefficients of every level (collective where a level has no lambda_max: the power method reduces its
+        two dot products over the ranks); done once, on the first apply at the latest."""
+        if self._coeffs is None:
+            red = reduce or self._reduce or _default_reduce
+            self._coeffs = [_distributed_chebyshev(sm, op, minv, red) for op, minv, sm, _ in self.levels]
+        return self
+
+    def _smooth(self, l, r, z):  # z <- S_l r (l3k_cheb_apply: zero initial guess)
+        from . import capi
+        lib, h = capi.load(), self._ctx._h
+        (op, minv, _, _), v, (c0, steps) = self.levels[l], self._vecs[l], self._coeffs[l]
+        n = minv.numel()
+        capi.check(lib.l3k_cheb_first(h, _vp(r), _vp(minv), c0, _vp(v["w"]), _vp(z), n, None))
+        for ca, cb in steps:
+            op.apply(z[None, :], v["az"][None, :])
+            capi.check(lib.l3k_cheb_step(h, _vp(r), _vp(v["az"]), _vp(minv), ca, cb, _vp(v["w"]), _vp(z), n, None))
+
+    def _residual(self, l, r, z):  # d <- r - A_l z on the live rows, 0 on the frozen ones
+        from . import capi
+        (op, minv, _, _), v = self.levels[l], self._vecs[l]
+        op.apply(z[None, :], v["az"][None, :])
+        capi.check(capi.load().l3k_pmg_residual(self._ctx._h, _vp(v["d"]), _vp(r), _vp(v["az"]), _vp(minv), minv.numel()))
+
+    def _cycle(self, l, r, z):
+        self._smooth(l, r, z)
+        if l + 1 == len(self.levels):
+            return
+        v, c, T, cop = self._vecs[l], self._vecs[l + 1], self.transfers[l + 1], self.levels[l + 1][0]
+        self._residual(l, r, z)
+        T.restrict(v["d"], c["r"], c["rg"])
+        cop.export_add(c["rg"], c["r"][None, :])
+        self._cycle(l + 1, c["r"], c["z"])
+        T.prolong(c["z"], cop.import_ghosts(c["z"][None, :]), z, add=True, frozen=self.levels[l][1])
+        self._residual(l, r, z)
+        self._smooth(l, v["d"], v["e"])
+        z.add_(v["e"])  # (e is 0 on the frozen rows: the smoother stores it so)
+
+    def apply(self, r, z):
+        """z <- M^-1 r, one symmetric V-cycle; r, z: distinct contiguous vectors over this rank's owned dofs of level 0"""
+        from . import capi
+        n = self.minv.numel()
+        if r.numel() != n or z.numel() != n or not (r.is_contiguous() and z.is_contiguous()):
+            raise capi.L3KError("r and z must be contiguous tensors over the owned dofs of level 0")
+        if n and _overlap(r, z, n):
+            raise capi.L3KError("r and z must be distinct vectors that do not overlap")
+        self.setup()
+        self._cycle(0, r, z)
+        return z
+
+
+def _default_reduce(view):
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(view, op=dist.ReduceOp.SUM)
+
+
 def jacobi_inverse_native(ctx, diag, damping=1.0, threshold=0.0):
     """NativeJacobiImpl::init through the C ABI (l3k_jacobi_inverse)."""
     from . import capi
@@ -340,7 +442,8 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
     rows; the fused l3k_cg_* kernels keep the scalars in a device block that is all-reduced between them (two small
     all-reduces per iteration, as Belos does).
 
-    `precond`: the Chebyshev-Jacobi preconditioner over minv (required then) in place of the diagonal one: a dict of
+    `precond`: a DistributedPMultigrid whose level 0 is `op` (it carries its minv): one V-cycle per iteration, the loop of
+    l3k_pcg_solve_pmg; or the Chebyshev-Jacobi preconditioner over minv (required then) in place of the diagonal one: a dict of
     ChebyshevPreconditioner's options (degree, cond_est, max_power_iters, boost_factor, lambda_max) or an object whose
     .info has lambda_max, lambda_min and degree (a ChebyshevPreconditioner's numbers on another operator).  The
     iteration is then that of l3k_pcg_solve_cheb with the exported pieces (l3k_cheb_first / _step, l3k_cg_update_rx /
@@ -348,6 +451,13 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
     lambda_max -- <x, y> and <y, y> of the power method go through the same reduction hook.  The power method starts
     from power_start_vector over this rank's rows."""
     from . import capi
+    pmg = precond if isinstance(precond, DistributedPMultigrid) else None
+    if pmg is not None:
+        if pmg.op is not op:
+            raise capi.L3KError("pcg_distributed: the p-multigrid hierarchy was built on another operator: its level 0 must be op")
+        if minv is not None and minv is not pmg.minv:
+            raise capi.L3KError("pcg_distributed: give the hierarchy's own minv of level 0, or none")
+        minv = pmg.minv
     if precond is not None and minv is None:
         raise capi.L3KError("pcg_distributed(precond=...) needs minv: the preconditioner is a polynomial in D^-1 A")
     lib, check, h, n = capi.load(), capi.check, ctx._h, b.numel()
@@ -402,11 +512,19 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
             it += 1
             if it % check_every == 0 or it == max_iters:  # (the only host synchronisation of the iteration)
                 res = s[3].item() ** 0.5 / scale
-    else:  # the iteration of l3k_pcg_solve_cheb
+    else:  # the iteration of l3k_pcg_solve_cheb; with a hierarchy: of l3k_pcg_solve_pmg
         r, z, p, ap, w = (torch.empty_like(b) for _ in range(5))
-        c0, steps = _distributed_chebyshev(precond, op, minv, reduce)
+        if pmg is not None:
+            pmg.setup(reduce)
+        else:
+            c0, steps = _distributed_chebyshev(precond, op, minv, reduce)
 
         def cheb():  # z = M^-1 r, reduced s[2] = <r, z> (the last kernel of the application leaves the local sum)
+            if pmg is not None:  # one V-cycle; <r, z> is a dot product behind it
+                pmg.apply(r, z)
+                s[2] = torch.dot(r, z)
+                reduce(s[2:3])
+                return
             check(lib.l3k_cheb_first(h, _vp(r), _vp(minv), c0, _vp(w), _vp(z), n, _vp(None if steps else s)))
             for k, (ca, cb) in enumerate(steps):
                 op.apply(z[None, :], ap[None, :])  # (ap is free here: it holds A z)

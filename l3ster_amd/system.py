@@ -413,6 +413,68 @@ class DeviceMesh:
             self._h = None
 
 
+class Transfer:
+    """Handle of l3k_transfer_create: the inter-order transfer of ONE level pair of a mesh that may be partitioned (include/l3k.h),
+    beside solve.PMultigrid's single-rank pairs.  fine, coarse: DeviceMesh'es of this rank's elements at two orders on one context;
+    elem_map (int64, host or device, or None = identity; match_elements makes it) names the coarse element of each fine one.  A
+    vector of a level is its owned rows plus its ghost rows (the (1, n_ghost_dofs) result of a distributed operator's
+    import_ghosts, or None on a mesh without ghosts).  The meshes and the map are kept alive here."""
+
+    def __init__(self, fine, coarse, elem_map=None):
+        import torch
+        self.fine, self.coarse = fine, coarse
+        self._map = None if elem_map is None else torch.as_tensor(elem_map, dtype=torch.int64).to(torch.device("cuda", fine.ctx.device)).contiguous()
+        self._h = C.c_void_p()
+        check(capi.load().l3k_transfer_create(fine.ctx._h, fine._h, coarse._h, None if self._map is None else self._map.data_ptr(),
+                                              C.byref(self._h)))
+
+    @property
+    def info(self):
+        """order_fine, order_coarse, n_owned_dofs_fine, n_ghost_dofs_fine, n_owned_dofs_coarse, n_ghost_dofs_coarse"""
+        import types
+        i = capi.TransferInfo()
+        check(capi.load().l3k_transfer_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.TransferInfo._fields_})
+
+    @staticmethod
+    def _vec(t, n, name, optional=False):
+        if t is None and (optional or n == 0):
+            return None
+        if t is None or t.numel() < n or (not optional and t.numel() != n) or not t.is_contiguous():
+            raise L3KError(f"{name} must be a contiguous tensor over {n} dofs")
+        return C.c_void_p(t.data_ptr())
+
+    def prolong(self, xc, xc_ghost, xf, add=False, frozen=None):
+        """xf <- P xc, or xf += P xc, on the owned fine rows (l3k_transfer_prolong); xc_ghost: the imported ghost rows of xc;
+        frozen: owned fine rows with frozen == 0 are left alone"""
+        i = self.info
+        check(capi.load().l3k_transfer_prolong(
+            self._h, self._vec(xc, i.n_owned_dofs_coarse, "xc"), self._vec(xc_ghost, i.n_ghost_dofs_coarse, "xc_ghost", True),
+            self._vec(xf, i.n_owned_dofs_fine, "xf"), int(bool(add)),
+            None if frozen is None else self._vec(frozen, i.n_owned_dofs_fine, "frozen")))
+        return xf
+
+    def restrict(self, rf, rc, rc_ghost):
+        """rc, rc_ghost <- this rank's share of P^T rf (l3k_transfer_restrict); the coarse level's export_add of rc_ghost into rc
+        completes the product"""
+        i = self.info
+        check(capi.load().l3k_transfer_restrict(
+            self._h, self._vec(rf, i.n_owned_dofs_fine, "rf"), self._vec(rc, i.n_owned_dofs_coarse, "rc"),
+            self._vec(rc_ghost, i.n_ghost_dofs_coarse, "rc_ghost", True)))
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None) and capi is not None:
+            capi.load().l3k_transfer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+
 def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
