@@ -3,10 +3,10 @@
 // point fails with an error.
 #include "objects.hpp"
 #include "device/launch.hpp"
+#include "host/mesh_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <unordered_map>
 
 using l3k::api::KernelMeta;
 using l3k::api::findKernel;
@@ -195,14 +195,81 @@ double* contextScratch(void* owner, size_t bytes)
     return ctx->scratch;
 }
 
-// `energy` (applies): where a single-column launch adds x^T A x, l3k_mf_energy_begin's target; only the apply kernel reads it
-int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* energy = nullptr)
+// What `which` selects of items that come in two classes (interior first: n_first of n_total): the classes it covers and
+// its range.  3 / 4 = first / second half of the first class (one half overlaps the import, the other the export); colour
+// by colour these become: all of the class / nothing.  valid = false: no such `which`
+struct WhichRange
 {
-    const l3k_mesh* m = mf->mesh;
+    bool    valid, classes[2];
+    int64_t begin, count;
+};
+WhichRange rangeOf(int which, int64_t n_first, int64_t n_total)
+{
+    switch (which)
+    {
+    case 0: return {true, {true, false}, 0, n_first};
+    case 1: return {true, {false, true}, n_first, n_total - n_first};
+    case 2: return {true, {true, true}, 0, n_total};
+    case 3: return {true, {true, false}, 0, n_first / 2};
+    case 4: return {true, {false, false}, n_first / 2, n_first - n_first / 2};
+    default: return {};
+    }
+}
+// A colour plan walked: one launch per non-empty colour of the classes covered, in (class, colour) order
+template < typename Set, typename Launch >
+int walkColourPlan(const std::vector< int64_t > (&det_ptr)[2], const bool (&classes)[2], Set&& set, Launch&& launch)
+{
+    for (int cls = 0; cls < 2; ++cls)
+        if (classes[cls])
+            for (size_t c = 0; c + 1 < det_ptr[cls].size(); ++c)
+            {
+                const int64_t count = det_ptr[cls][c + 1] - det_ptr[cls][c];
+                set(det_ptr[cls][c], count);
+                if (count > 0)
+                    if (int rc = launch())
+                        return rc;
+            }
+    return 0;
+}
+
+// the operands every launch of a term takes: the mesh arrays, the tables, the fields, the time and the dof layout
+void termArgs(const KernelTerm& t, l3k::dev::ElemArgs& a)
+{
+    const l3k_mesh* m = t.mesh;
     a                 = {};
     a.elem_nodes      = m->elem_nodes.ptr;
     a.elem_verts      = m->elem_verts.ptr;
     a.dirichlet       = m->dirichlet.ptr;
+    a.tables          = t.tables.ptr;
+    a.fields          = t.fields;
+    a.ldf             = t.ldf;
+    a.n_owned_dofs    = m->nOwnedDofs();
+    a.time            = t.time;
+    a.dofs_per_node   = m->dofs_per_node;
+    for (int u = 0; u < l3k::dev::max_unknowns; ++u)
+        a.field_inds[u] = t.field_inds[u];
+}
+// ... the vectors of an apply (owned rows and ghost rows of x and y) and of a diag / rhs pass
+void applyOperands(l3k::dev::ElemArgs& a, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, double* d_y, size_t ldy,
+                   double* d_yghost, size_t ldyg, double alpha)
+{
+    a.x = d_x, a.xg = d_xghost, a.y = d_y, a.yg = d_yghost;
+    a.ldx = ldx, a.ldxg = ldxg, a.ldy = ldy, a.ldyg = ldyg;
+    a.alpha = alpha;
+}
+void diagRhsOperands(l3k::dev::ElemArgs& a, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs, size_t ldr,
+                     double* d_diag_ghost, double* d_rhs_ghost, size_t ldrg)
+{
+    a.dirichlet_vals = d_dirichlet_vals;
+    a.ldg            = ldg;
+    a.y = d_rhs, a.ldy = ldr, a.yg = d_rhs_ghost, a.ldyg = ldrg;
+    a.diag = d_diag, a.diag_g = d_diag_ghost;
+}
+// `energy` (applies): where a single-column launch adds x^T A x, l3k_mf_energy_begin's target; only the apply kernel reads it
+int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* energy = nullptr)
+{
+    const l3k_mesh* m = mf->mesh;
+    termArgs(*mf, a);
     a.elem_flags      = m->elem_flags.ptr;
     a.exclusive_node_begin = m->exclusive_begin;
     a.exclusive_node_end   = m->exclusive_end;
@@ -216,13 +283,7 @@ int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* en
     a.energy        = ncols == 1 ? energy : nullptr;
     a.energy_done   = &mf->energy_done;
     a.n_shell              = m->n_shell;
-    a.tables          = mf->tables.ptr;
     a.tables_host     = mf->tables_host.data();
-    a.fields          = mf->fields;
-    a.ldf             = mf->ldf;
-    a.n_owned_dofs    = m->nOwnedDofs();
-    a.time            = mf->time;
-    a.dofs_per_node   = m->dofs_per_node;
 #ifdef L3K_ABLATION // (tools/kbench.py's switches exist in the ablation build only)
     static const int dbg_flags = [] {
         const char* e = std::getenv("L3K_DEBUG_FLAGS");
@@ -230,51 +291,29 @@ int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* en
     }();
     a.dbg    = dbg_flags;
     a.stamps = debugStamps();
-#else
-    a.dbg    = 0;
-    a.stamps = nullptr;
 #endif
     a.dense  = mf->dense;
     a.ref_z0 = mf->ctx->reference_z0 ? 1 : 0;
-    for (int u = 0; u < l3k::dev::max_unknowns; ++u)
-        a.field_inds[u] = mf->field_inds[u];
-    switch (which)
+    const WhichRange r = rangeOf(which, m->n_interior, m->n_elems);
+    if (!r.valid)
     {
-    case 0:
-        a.elem_begin = 0;
-        a.elem_count = m->n_interior;
-        break;
-    case 1:
-        a.elem_begin = m->n_interior;
-        a.elem_count = m->n_elems - m->n_interior;
-        break;
-    case 2:
-        a.elem_begin = 0;
-        a.elem_count = m->n_elems;
-        break;
-    case 3: // first / second half of the interior elements: one half overlaps the import, the other the export
-        a.elem_begin = 0;
-        a.elem_count = m->n_interior / 2;
-        break;
-    case 4:
-        a.elem_begin = m->n_interior / 2;
-        a.elem_count = m->n_interior - m->n_interior / 2;
-        break;
-    default:
         setError("which must be 0 (interior), 1 (border), 2 (all), 3 or 4 (first / second half of the interior)");
         return -1;
     }
-    if (mf->kp.n_fields > 0 && !mf->fields)
-    {
-        setError("kernel reads %d external fields but l3k_mf_set_fields was not called", mf->kp.n_fields);
-        return -1;
-    }
-    if (ncols < 1 || ncols > mf->n_rhs)
-    {
-        // algsys/MatrixFreeSystem.hpp:1035-1037
-        setError("number of columns (%d) must be in [1, n_rhs = %d]", ncols, mf->n_rhs);
-        return -1;
-    }
+    a.elem_begin = r.begin;
+    a.elem_count = r.count;
+    if (int rc = checkFieldsSet(mf))
+        return rc;
+    return checkColumns(ncols, mf->n_rhs);
+}
+// ... of a LocalAssembly launch: all columns of the elements [first, first + count), written from position 0 of the output
+int assemblyArgs(l3k_mf* mf, int64_t first, int64_t count, l3k::dev::ElemArgs& a)
+{
+    if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+        return rc;
+    a.elem_begin     = first;
+    a.elem_count     = count;
+    a.elem_begin_out = 0;
     return 0;
 }
 } // namespace
@@ -285,6 +324,15 @@ const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols)
         setError("no device instantiation for kernel %d, order %d, nq %d, ncols %d: add it to L3K_FOR_EACH_INSTANCE "
                  "(l3ster_amd/csrc/user_kernels.hpp) and rebuild",
                  mf->kernel_id, mf->mesh->order, mf->nq, ncols);
+    return inst;
+}
+const l3k::dev::BoundaryInstance* boundaryInstanceFor(const l3k_bnd* b, int ncols, const char* what)
+{
+    const auto* inst = l3k::dev::findBoundaryInstance(b->kernel_id, b->mesh->order, b->nq, ncols);
+    if (!inst)
+        setError("%s%sno device instantiation for boundary kernel %d, order %d, nq %d, ncols %d: add it to "
+                 "L3K_FOR_EACH_BOUNDARY_INSTANCE (l3ster_amd/csrc/user_kernels.hpp) and rebuild",
+                 what ? what : "", what ? ": " : "", b->kernel_id, b->mesh->order, b->nq, ncols);
     return inst;
 }
 namespace
@@ -365,50 +413,20 @@ namespace
 {
 int bndArgs(const l3k_bnd* b, int which, int ncols, l3k::dev::ElemArgs& a)
 {
-    const l3k_mesh* m = b->mesh;
-    a                 = {};
-    a.elem_nodes      = m->elem_nodes.ptr;
-    a.elem_verts      = m->elem_verts.ptr;
-    a.dirichlet       = m->dirichlet.ptr;
-    a.tables          = b->tables.ptr;
-    a.fields          = b->fields;
-    a.ldf             = b->ldf;
-    a.n_owned_dofs    = m->nOwnedDofs();
-    a.time            = b->time;
-    a.dofs_per_node   = m->dofs_per_node;
-    a.face_elem       = b->face_elem.ptr;
-    a.face_side       = b->face_side.ptr;
-    for (int u = 0; u < l3k::dev::max_unknowns; ++u)
-        a.field_inds[u] = b->field_inds[u];
-    switch (which)
+    termArgs(*b, a);
+    a.face_elem = b->face_elem.ptr;
+    a.face_side = b->face_side.ptr;
+    const WhichRange r = rangeOf(which, b->n_interior_faces, b->n_faces);
+    if (which > 2 || !r.valid) // (sides have no halves)
     {
-    case 0:
-        a.face_begin = 0;
-        a.face_count = b->n_interior_faces;
-        break;
-    case 1:
-        a.face_begin = b->n_interior_faces;
-        a.face_count = b->n_faces - b->n_interior_faces;
-        break;
-    case 2:
-        a.face_begin = 0;
-        a.face_count = b->n_faces;
-        break;
-    default:
         setError("which must be 0 (sides of interior elements), 1 (of border elements) or 2 (all)");
         return -1;
     }
-    if (b->kp.n_fields > 0 && !b->fields)
-    {
-        setError("boundary kernel reads %d external fields but l3k_bnd_set_fields was not called", b->kp.n_fields);
-        return -1;
-    }
-    if (ncols < 1 || ncols > b->n_rhs)
-    {
-        setError("number of columns (%d) must be in [1, n_rhs = %d]", ncols, b->n_rhs);
-        return -1;
-    }
-    return 0;
+    a.face_begin = r.begin;
+    a.face_count = r.count;
+    if (int rc = checkFieldsSet(b))
+        return rc;
+    return checkColumns(ncols, b->n_rhs);
 }
 // the launch ranges of a side call: the caller's range, or in deterministic mode one launch per colour of the classes it
 // covers (the ELEMENTS of the sides of one colour share no node: the order of the additions to a row is the order of the launches)
@@ -422,27 +440,9 @@ int forEachSideRange(const l3k_bnd* b, int which, l3k::dev::ElemArgs& a, F&& lau
         setError("deterministic mode was enabled after this boundary term was created: create it with the mode on");
         return -1;
     }
-    const bool classes[2] = {which == 0 || which == 2, which == 1 || which == 2};
-    for (int cls = 0; cls < 2; ++cls)
-        if (classes[cls])
-            for (size_t c = 0; c + 1 < b->det_ptr[cls].size(); ++c)
-            {
-                a.face_begin = b->det_ptr[cls][c];
-                a.face_count = b->det_ptr[cls][c + 1] - b->det_ptr[cls][c];
-                if (a.face_count > 0)
-                    if (int rc = launch(a))
-                        return rc;
-            }
-    return 0;
-}
-const l3k::dev::BoundaryInstance* bndInstance(const l3k_bnd* b, int ncols)
-{
-    const auto* inst = l3k::dev::findBoundaryInstance(b->kernel_id, b->mesh->order, b->nq, ncols);
-    if (!inst)
-        setError("no device instantiation for boundary kernel %d, order %d, nq %d, ncols %d: add it to "
-                 "L3K_FOR_EACH_BOUNDARY_INSTANCE (l3ster_amd/csrc/user_kernels.hpp) and rebuild",
-                 b->kernel_id, b->mesh->order, b->nq, ncols);
-    return inst;
+    return walkColourPlan(
+        b->det_ptr, rangeOf(which, b->n_interior_faces, b->n_faces).classes, [&](int64_t begin, int64_t count) { a.face_begin = begin, a.face_count = count; },
+        [&] { return launch(a); });
 }
 int bndApplyImpl(l3k_bnd* b, int which, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, double* d_y,
                  size_t ldy, double* d_yghost, size_t ldyg, int ncols, double alpha)
@@ -461,13 +461,11 @@ int bndApplyImpl(l3k_bnd* b, int which, const double* d_x, size_t ldx, const dou
         setError("mesh has ghost nodes: sides of border elements need the ghost import/export buffers");
         return -1;
     }
-    a.x = d_x, a.xg = d_xghost, a.y = d_y, a.yg = d_yghost;
-    a.ldx = ldx, a.ldxg = ldxg, a.ldy = ldy, a.ldyg = ldyg;
-    a.alpha = alpha;
-    const auto* inst = bndInstance(b, ncols);
+    applyOperands(a, d_x, ldx, d_xghost, ldxg, d_y, ldy, d_yghost, ldyg, alpha);
+    const auto* inst = boundaryInstanceFor(b, ncols);
     if (!inst)
         return -4;
-    return forEachSideRange(b, which, a, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, b->blob.empty() ? nullptr : b->blob.data(), b->ctx->stream); });
+    return forEachSideRange(b, which, a, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, b->blobPtr(), b->ctx->stream); });
 }
 int bndDiagRhsImpl(l3k_bnd* b, int which, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs,
                    size_t ldr, double* d_diag_ghost, double* d_rhs_ghost, size_t ldrg)
@@ -480,14 +478,11 @@ int bndDiagRhsImpl(l3k_bnd* b, int which, const double* d_dirichlet_vals, size_t
         setError("mesh has ghost nodes: sides of border elements need the ghost diag / rhs buffers");
         return -1;
     }
-    a.dirichlet_vals = d_dirichlet_vals;
-    a.ldg            = ldg;
-    a.y = d_rhs, a.ldy = ldr, a.yg = d_rhs_ghost, a.ldyg = ldrg;
-    a.diag = d_diag, a.diag_g = d_diag_ghost;
-    const auto* inst = bndInstance(b, b->n_rhs);
+    diagRhsOperands(a, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, d_diag_ghost, d_rhs_ghost, ldrg);
+    const auto* inst = boundaryInstanceFor(b, b->n_rhs);
     if (!inst)
         return -4;
-    return forEachSideRange(b, which, a, [&](l3k::dev::ElemArgs& r) { return inst->diag_rhs(r, b->blob.empty() ? nullptr : b->blob.data(), b->ctx->stream); });
+    return forEachSideRange(b, which, a, [&](l3k::dev::ElemArgs& r) { return inst->diag_rhs(r, b->blobPtr(), b->ctx->stream); });
 }
 } // namespace
 
@@ -500,60 +495,17 @@ namespace
 // one class adds at most once to any row, so the order of the additions to a row is the order of the launches.
 int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vector< uint8_t >& flags)
 {
-    const int     n1 = d->order + 1, nv = 1 << d->dim; // (quads: the 4 corners, v = i + 2j)
+    const int     n1 = d->order + 1, nv = 1 << d->dim;
     const int64_t N  = d->dim == 2 ? int64_t(n1) * n1 : int64_t(n1) * n1 * n1;
-    int           corner[8];
-    for (int v = 0; v < nv; ++v)
-        corner[v] = ((v & 1) ? n1 - 1 : 0) + n1 * (((v >> 1) & 1) ? n1 - 1 : 0) + n1 * n1 * (((v >> 2) & 1) ? n1 - 1 : 0);
-    std::unordered_map< uint32_t, uint64_t > used; // corner node -> colours taken by the elements around it
-    used.reserve(static_cast< size_t >(d->n_elems) * 2);
-    std::vector< uint8_t > colour(static_cast< size_t >(d->n_elems));
-    int                    n_colours = 0;
+    m.det_corner_nodes = l3k::host::cornerNodes(d->dim, d->order, d->n_elems, d->elem_nodes); // (kept: the colouring of boundary sides)
+    std::vector< int64_t > self(static_cast< size_t >(d->n_elems)); // (every element is its own item)
     for (int64_t e = 0; e < d->n_elems; ++e)
-    {
-        uint64_t taken = 0;
-        for (int v = 0; v < nv; ++v)
-        {
-            const auto it = used.find(d->elem_nodes[e * N + corner[v]]);
-            if (it != used.end())
-                taken |= it->second;
-        }
-        int c = 0;
-        while (c < 64 && ((taken >> c) & 1u))
-            ++c;
-        if (c == 64)
-        {
-            setError("deterministic mode: more than 64 colours needed");
-            return -1;
-        }
-        colour[e] = uint8_t(c);
-        n_colours = std::max(n_colours, c + 1);
-        for (int v = 0; v < nv; ++v)
-            used[d->elem_nodes[e * N + corner[v]]] |= uint64_t(1) << c;
-    }
-    m.det_corner_nodes.resize(static_cast< size_t >(d->n_elems) * nv); // (the colouring of boundary sides)
-    for (int64_t e = 0; e < d->n_elems; ++e)
-        for (int v = 0; v < nv; ++v)
-            m.det_corner_nodes[size_t(e) * nv + v] = d->elem_nodes[e * N + corner[v]];
-    std::vector< int64_t > order(static_cast< size_t >(d->n_elems));
-    for (int64_t e = 0; e < d->n_elems; ++e)
-        order[e] = e;
-    const int64_t n_int = d->n_interior_elems;
-    auto          by_colour = [&](int64_t x, int64_t y) { return colour[x] < colour[y]; };
-    std::stable_sort(order.begin(), order.begin() + n_int, by_colour);
-    std::stable_sort(order.begin() + n_int, order.end(), by_colour);
-    for (int cls = 0; cls < 2; ++cls)
-    {
-        const int64_t b = cls ? n_int : 0, e = cls ? d->n_elems : n_int;
-        m.det_ptr[cls].assign(static_cast< size_t >(n_colours) + 1, e);
-        int64_t i = b;
-        for (int c = 0; c < n_colours; ++c)
-        {
-            m.det_ptr[cls][c] = i;
-            while (i < e && colour[order[i]] == c)
-                ++i;
-        }
-    }
+        self[e] = e;
+    l3k::host::ColourPlan plan;
+    if (int rc = l3k::host::colourItems(d->n_elems, d->n_interior_elems, self.data(), m.det_corner_nodes.data(), nv, "", plan))
+        return rc;
+    const auto& order = plan.order;
+    std::swap(m.det_ptr, plan.ptr);
     std::vector< uint32_t > nodes(static_cast< size_t >(d->n_elems * N));
     const int               nvd = nv * 3; // vertex doubles per element
     std::vector< double >   verts(static_cast< size_t >(d->n_elems) * nvd);
@@ -575,7 +527,7 @@ int buildDeterministicPlan(l3k_mesh& m, const l3k_mesh_desc* d, const std::vecto
         if (int rc = m.det_elem_flags.upload(fl.data(), fl.size(), s))
             return rc;
     L3K_HIP(hipStreamSynchronize(s)); // (the staging vectors are locals)
-    m.det_colour = std::move(colour);
+    m.det_colour = std::move(plan.colour);
     m.det_built  = true;
     return 0;
 }
@@ -596,18 +548,9 @@ int forEachLaunchRange(const l3k_mf* mf, int which, l3k::dev::ElemArgs& a, F&& l
     a.elem_verts = m->det_elem_verts.ptr;
     a.elem_flags = m->det_elem_flags.ptr;
     a.energy     = nullptr; // (the fused <x, A x> is an atomic accumulation: the caller takes the fixed-order dot product)
-    const bool classes[2] = {which == 0 || which == 2 || which == 3, which == 1 || which == 2};
-    for (int cls = 0; cls < 2; ++cls)
-        if (classes[cls])
-            for (size_t c = 0; c + 1 < m->det_ptr[cls].size(); ++c)
-            {
-                a.elem_begin = m->det_ptr[cls][c];
-                a.elem_count = m->det_ptr[cls][c + 1] - m->det_ptr[cls][c];
-                if (a.elem_count > 0)
-                    if (int rc = launch(a))
-                        return rc;
-            }
-    return 0;
+    return walkColourPlan(
+        m->det_ptr, rangeOf(which, m->n_interior, m->n_elems).classes, [&](int64_t begin, int64_t count) { a.elem_begin = begin, a.elem_count = count; },
+        [&] { return launch(a); });
 }
 } // namespace
 
@@ -886,152 +829,40 @@ int l3k_mesh_create(l3k_ctx* ctx, const l3k_mesh_desc* d, l3k_mesh** out)
         setError("too many local dofs");
         return -1;
     }
-    // operand shapes must match what the kernels assume: every node id inside [0, n_nodes)
-    for (int64_t i = 0; i < d->n_elems * N; ++i)
-        if (d->elem_nodes[i] >= static_cast< uint64_t >(n_nodes))
-        {
-            setError("elem_nodes[%lld] = %u is outside the local node range [0,%lld)", (long long)i, d->elem_nodes[i],
-                     (long long)n_nodes);
-            return -1;
-        }
+    l3k::host::MeshPlan plan; // (host staging: outlives the synchronisation below)
+    if (int rc = l3k::host::analyseMesh(d, plan))
+        return rc;
     L3K_HIP(hipSetDevice(ctx->device));
-    auto m           = std::make_unique< l3k_mesh >();
-    m->ctx           = ctx;
-    m->dim           = d->dim;
-    m->order         = d->order;
-    m->dofs_per_node = d->dofs_per_node;
-    m->n_elems       = d->n_elems;
-    m->n_interior    = d->n_interior_elems;
-    m->n_owned_nodes = d->n_owned_nodes;
-    m->n_ghost_nodes = d->n_ghost_nodes;
+    auto m             = std::make_unique< l3k_mesh >();
+    m->ctx             = ctx;
+    m->dim             = d->dim;
+    m->order           = d->order;
+    m->dofs_per_node   = d->dofs_per_node;
+    m->n_elems         = d->n_elems;
+    m->n_interior      = d->n_interior_elems;
+    m->n_owned_nodes   = d->n_owned_nodes;
+    m->n_ghost_nodes   = d->n_ghost_nodes;
+    m->exclusive_begin = plan.exclusive_begin;
+    m->exclusive_end   = plan.exclusive_end;
+    m->n_shell         = plan.n_shell;
+    m->all_affine      = plan.all_affine;
     if (int rc = m->elem_nodes.upload(d->elem_nodes, size_t(d->n_elems * N), ctx->stream))
         return rc;
     if (int rc = m->elem_verts.upload(d->elem_verts, size_t(d->n_elems) * nvd, ctx->stream))
         return rc;
-    // nodes referenced by exactly one element (the element-internal nodes of the reference's numbering,
-    // mesh/LocalMeshView.hpp:425-458) can be scattered with plain stores: find the maximal owned tail range
-    {
-        std::vector< uint8_t > count(static_cast< size_t >(n_nodes), 0);
-        for (int64_t i = 0; i < d->n_elems * N; ++i)
-            if (count[d->elem_nodes[i]] < 2)
-                ++count[d->elem_nodes[i]];
-        int64_t b = d->n_owned_nodes;
-        while (b > 0 && count[b - 1] == 1) // exactly one: a node no element touches still needs the beta scaling
-            --b;
-        m->exclusive_begin = b;
-        m->exclusive_end   = d->n_owned_nodes;
-        // The single-wave kernel decides "exclusive" by the LOCAL position (element-internal or not) instead of testing
-        // every node id: shrink the range until it holds no node that sits on an element's shell, and drop it altogether
-        // if some element-internal node lies outside it (numberings that do not put the internal nodes last).
-        const int n1 = d->order + 1;
-        auto      internal = [&](int64_t i) {
-            const int ix = int(i % n1), iy = int((i / n1) % n1), iz = int(i / (n1 * n1));
-            if (dim == 2)
-                return ix > 0 && ix < n1 - 1 && iy > 0 && iy < n1 - 1;
-            return ix > 0 && ix < n1 - 1 && iy > 0 && iy < n1 - 1 && iz > 0 && iz < n1 - 1;
-        };
-        int64_t max_shell = -1, min_internal = n_nodes;
-        for (int64_t e = 0; e < d->n_elems; ++e)
-            for (int64_t i = 0; i < N; ++i)
-            {
-                const int64_t id = d->elem_nodes[e * N + i];
-                if (internal(i))
-                    min_internal = std::min(min_internal, id);
-                else if (id < d->n_owned_nodes)
-                    max_shell = std::max(max_shell, id);
-            }
-        m->exclusive_begin = std::max(m->exclusive_begin, max_shell + 1);
-        if (d->n_elems == 0 || d->order < 2 || min_internal < m->exclusive_begin)
-            m->exclusive_begin = m->exclusive_end; // empty: every node is scattered with atomics
-        // scatter slots: local nodes of a typical element (the middle one of the traversal) in ascending id order --
-        // rows that are contiguous in y become contiguous slots; internal positions last.  Hexes only: the quad kernel
-        // scatters in lexicographic order
-        if (dim == 3 && d->n_elems > 0 && n1 <= 8)
-        {
-            const uint32_t*        ids = d->elem_nodes + (d->n_elems / 2) * N;
-            std::vector< int32_t > order(static_cast< size_t >(N));
-            for (int64_t i = 0; i < N; ++i)
-                order[i] = int32_t(i);
-            std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-                const bool ix = internal(x), iy = internal(y);
-                return ix != iy ? iy : ids[x] < ids[y];
-            });
-            std::vector< uint16_t > tab(static_cast< size_t >(n1 * n1 * 8), 0);
-            int                     n_shell = 0;
-            for (int64_t s = 0; s < N; ++s)
-            {
-                const int32_t i                           = order[s];
-                tab[(i % (n1 * n1)) * 8 + i / (n1 * n1)] = uint16_t(s);
-                n_shell += !internal(i);
-            }
-            m->n_shell = n_shell;
-            if (int rc = m->slot_tab.upload(tab.data(), tab.size(), ctx->stream))
-                return rc;
-            L3K_HIP(hipStreamSynchronize(ctx->stream)); // (tab is a local)
-        }
-    }
-    std::vector< int64_t > rows;
-    // per-element flags: bit 0 = the element touches a Dirichlet dof, bit 1 = its tri-linear map is affine (a
-    // parallelepiped: the bilinear and trilinear coefficient vectors of the 8 vertices vanish), so its Jacobian is one
-    // matrix -- the element kernel then inverts it once per element instead of once per quadrature point
-    std::vector< uint8_t > flags(static_cast< size_t >(d->n_elems), 0); // (host staging: outlives the synchronisation below)
-    for (int64_t e = 0; e < d->n_elems; ++e)
-    {
-        const double* v = d->elem_verts + e * nvd;
-        double        scale = 0., dev = 0.;
-        if (dim == 2) // bilinear quad: a parallelogram when the coefficient of xi*eta vanishes
-        {
-            for (int s = 0; s < 2; ++s)
-            {
-                const double c10 = -v[0 * 3 + s] + v[1 * 3 + s] - v[2 * 3 + s] + v[3 * 3 + s];
-                const double c01 = -v[0 * 3 + s] - v[1 * 3 + s] + v[2 * 3 + s] + v[3 * 3 + s];
-                const double c11 = v[0 * 3 + s] - v[1 * 3 + s] - v[2 * 3 + s] + v[3 * 3 + s];
-                scale            = std::max({scale, std::fabs(c10), std::fabs(c01)});
-                dev              = std::max(dev, std::fabs(c11));
-            }
-            if (dev <= 1e-14 * scale)
-                flags[e] |= 2;
-            continue;
-        }
-        for (int s = 0; s < 3; ++s)
-        {
-            auto c = [&](int sx, int sy, int sz) { // coefficient of xi^sx eta^sy zeta^sz (x 8)
-                double acc = 0.;
-                for (int k = 0; k < 8; ++k)
-                    acc += ((sx && !(k & 1)) ? -1. : 1.) * ((sy && !(k & 2)) ? -1. : 1.) * ((sz && !(k & 4)) ? -1. : 1.) * v[k * 3 + s];
-                return acc;
-            };
-            scale = std::max({scale, std::fabs(c(1, 0, 0)), std::fabs(c(0, 1, 0)), std::fabs(c(0, 0, 1))});
-            dev   = std::max({dev, std::fabs(c(1, 1, 0)), std::fabs(c(1, 0, 1)), std::fabs(c(0, 1, 1)), std::fabs(c(1, 1, 1))});
-        }
-        if (dev <= 1e-14 * scale)
-            flags[e] |= 2;
-    }
-    m->all_affine = d->n_elems > 0;
-    for (uint8_t f : flags)
-        m->all_affine = m->all_affine && (f & 2);
+    if (int rc = m->slot_tab.upload(plan.slot_tab.data(), plan.slot_tab.size(), ctx->stream))
+        return rc;
     if (d->dirichlet)
     {
-        for (int64_t e = 0; e < d->n_elems; ++e)
-            for (int64_t i = 0; i < N && !(flags[e] & 1); ++i)
-                for (int k = 0; k < d->dofs_per_node; ++k)
-                    if (d->dirichlet[int64_t(d->elem_nodes[e * N + i]) * d->dofs_per_node + k])
-                    {
-                        flags[e] |= 1;
-                        break;
-                    }
         if (int rc = m->dirichlet.upload(d->dirichlet, size_t(n_nodes * d->dofs_per_node), ctx->stream))
             return rc;
-        for (int64_t i = 0; i < d->n_owned_nodes * d->dofs_per_node; ++i) // getOwnedDirichletDofs
-            if (d->dirichlet[i])
-                rows.push_back(i);
-        if (int rc = m->owned_dirichlet_rows.upload(rows.data(), rows.size(), ctx->stream))
+        if (int rc = m->owned_dirichlet_rows.upload(plan.owned_dirichlet_rows.data(), plan.owned_dirichlet_rows.size(), ctx->stream))
             return rc;
     }
-    if (int rc = m->elem_flags.upload(flags.data(), flags.size(), ctx->stream))
+    if (int rc = m->elem_flags.upload(plan.elem_flags.data(), plan.elem_flags.size(), ctx->stream))
         return rc;
     if (ctx->deterministic)
-        if (int rc = buildDeterministicPlan(*m, d, flags))
+        if (int rc = buildDeterministicPlan(*m, d, plan.elem_flags))
             return rc;
     L3K_HIP(hipStreamSynchronize(ctx->stream)); // host arrays may be freed by the caller after return
     *out = m.release();
@@ -1062,63 +893,34 @@ int l3k_mf_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpara
         setError("kernel %s is a boundary equation kernel: use l3k_bnd_create", k->name);
         return -1;
     }
-    if (k->kp.dimension != mesh->dim)
-    {
-        setError("kernel dimension %d != mesh dimension %d", k->kp.dimension, mesh->dim);
-        return -1;
-    }
-    if (kparam_blob && kparam_bytes != k->bytes)
-    {
-        setError("kernel %s expects a %zu-byte parameter block, got %zu", k->name, k->bytes, kparam_bytes);
-        return -1;
-    }
+    if (int rc = checkKernelDim(k->kp, mesh))
+        return rc;
+    if (int rc = checkParamBlock(*k, kparam_blob, kparam_bytes))
+        return rc;
     if (n_rhs < 1)
     {
         setError("n_rhs must be >= 1");
         return -1;
     }
-    const l3k_asmopts o  = opts ? *opts : l3k_asmopts{1, 0, 0};
-    const int         nq = l3k_n_qps1d(mesh->order, o.value_order, o.derivative_order);
-    if (nq < mesh->order + 1)
-    {
-        setError("nq = %d < p+1 = %d: the collocation-derivative device algorithm needs nq >= p+1", nq, mesh->order + 1);
-        return -1;
-    }
-    auto mf       = std::make_unique< l3k_mf >();
-    mf->ctx       = ctx;
-    mf->mesh      = mesh;
-    mf->kernel_id = kernel_id;
-    mf->nq        = nq;
-    mf->n_rhs     = n_rhs;
-    mf->kp        = k->kp;
-    if (kparam_blob)
-        mf->blob.assign(static_cast< const char* >(kparam_blob), static_cast< const char* >(kparam_blob) + kparam_bytes);
-    for (int u = 0; u < l3k::dev::max_unknowns; ++u)
-        mf->field_inds[u] = 0;
+    const int nq = quadraturePoints(mesh, opts);
+    if (int rc = checkCollocation(nq, mesh))
+        return rc;
+    auto mf = std::make_unique< l3k_mf >();
+    mf->init(ctx, mesh, *k, nq, n_rhs, kparam_blob, kparam_bytes);
     if (k->kp.n_unknowns > l3k::dev::max_unknowns)
     {
         setError("n_unknowns > %d unsupported", l3k::dev::max_unknowns);
         return -1;
     }
-    for (int u = 0; u < k->kp.n_unknowns; ++u)
-    {
-        const int fi = field_inds ? field_inds[u] : u;
-        if (fi < 0 || fi >= mesh->dofs_per_node)
-        {
-            setError("field_inds[%d] = %d outside [0, dofs_per_node = %d)", u, fi, mesh->dofs_per_node);
-            return -1;
-        }
-        mf->field_inds[u] = fi;
-    }
+    if (int rc = resolveFieldInds(field_inds, k->kp.n_unknowns, mesh, mf->field_inds))
+        return rc;
     mf->dense = k->kp.n_unknowns == mesh->dofs_per_node;
     for (int u = 0; u < k->kp.n_unknowns; ++u)
         mf->dense = mf->dense && mf->field_inds[u] == u;
     // rows of nodes touched by one element only are written (not accumulated) by the element kernel, see l3k_mf_scale
     mf->fuse = mf->dense && mesh->exclusive_end > mesh->exclusive_begin;
     L3K_HIP(hipSetDevice(ctx->device));
-    mf->tables_host  = l3k::host::deviceTableBlock(mesh->order, nq);
-    const auto& block = mf->tables_host;
-    if (int rc = mf->tables.upload(block.data(), block.size(), ctx->stream))
+    if (int rc = uploadTables(mesh, nq, ctx->stream, mf->tables_host, mf->tables))
         return rc;
     L3K_HIP(hipStreamSynchronize(ctx->stream));
     *out = mf.release();
@@ -1136,14 +938,7 @@ int l3k_mf_set_fields(l3k_mf* mf, const double* d_soa, size_t ld)
         setError("null mf");
         return -1;
     }
-    if (d_soa && ld < size_t(mf->mesh->n_owned_nodes + mf->mesh->n_ghost_nodes))
-    {
-        setError("field leading dimension %zu < number of local nodes", ld);
-        return -1;
-    }
-    mf->fields = d_soa;
-    mf->ldf    = ld;
-    return 0;
+    return setFields(*mf, d_soa, ld);
 }
 int l3k_mf_set_time(l3k_mf* mf, double time)
 {
@@ -1160,17 +955,10 @@ extern "C++" int checkApplyOperands(const l3k_mf* mf, int ncols, const double* d
                        size_t ldy, const double* d_yghost, size_t ldyg)
 {
     const l3k_mesh* m = mf->mesh;
-    if (mf->kp.n_fields > 0 && !mf->fields)
-    {
-        setError("kernel reads %d external fields but l3k_mf_set_fields was not called", mf->kp.n_fields);
-        return -1;
-    }
-    if (ncols < 1 || ncols > mf->n_rhs)
-    {
-        // algsys/MatrixFreeSystem.hpp:1035-1037
-        setError("number of columns (%d) must be in [1, n_rhs = %d]", ncols, mf->n_rhs);
-        return -1;
-    }
+    if (int rc = checkFieldsSet(mf))
+        return rc;
+    if (int rc = checkColumns(ncols, mf->n_rhs))
+        return rc;
     if (ldx < size_t(m->nOwnedDofs()) || ldy < size_t(m->nOwnedDofs()))
     {
         setError("leading dimension smaller than the number of owned dofs");
@@ -1297,20 +1085,11 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
         setError("mesh has ghost nodes: border elements need the ghost import/export buffers");
         return -1;
     }
-    a.x     = d_x;
-    a.xg    = d_xghost;
-    a.y     = d_y;
-    a.yg    = d_yghost;
-    a.ldx   = ldx;
-    a.ldxg  = ldxg;
-    a.ldy   = ldy;
-    a.ldyg  = ldyg;
-    a.alpha     = alpha;
+    applyOperands(a, d_x, ldx, d_xghost, ldxg, d_y, ldy, d_yghost, ldyg, alpha);
     a.beta      = beta;
     a.fuse_beta = mf->fuse;
-    const void* blob   = mf->blob.empty() ? nullptr : mf->blob.data();
     const auto  launch = [&](const l3k::dev::Instance* inst, l3k::dev::ElemArgs& ac) {
-        return forEachLaunchRange(mf, which, ac, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, blob, mf->ctx->stream); });
+        return forEachLaunchRange(mf, which, ac, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, mf->blobPtr(), mf->ctx->stream); });
     };
     ColumnPlan  plan;
     const auto* inst = planColumns(mf, ncols, plan);
@@ -1323,7 +1102,7 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     {
         a.n_cols = ncols;
         a.energy = nullptr;
-        rc       = inst->apply_cols(a, blob, mf->ctx->stream);
+        rc       = inst->apply_cols(a, mf->blobPtr(), mf->ctx->stream);
     }
     else
         rc = l3k::dev::forEachColumn(a, ncols, [&](l3k::dev::ElemArgs& ac) { return launch(inst, ac); });
@@ -1492,14 +1271,7 @@ int l3k_mf_diag_rhs(l3k_mf* mf, int which, const double* d_dirichlet_vals, size_
     l3k::dev::ElemArgs a;
     if (int rc = fillArgs(mf, which, mf->n_rhs, a))
         return rc;
-    a.dirichlet_vals = d_dirichlet_vals;
-    a.ldg            = ldg;
-    a.y              = d_rhs;
-    a.ldy            = ldr;
-    a.yg             = d_rhs_ghost;
-    a.ldyg           = ldrg;
-    a.diag           = d_diag;
-    a.diag_g         = d_diag_ghost;
+    diagRhsOperands(a, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, d_diag_ghost, d_rhs_ghost, ldrg);
     if (mf->mesh->n_ghost_nodes > 0 && which != 0 && (!d_rhs_ghost || (d_diag && !d_diag_ghost)))
     {
         setError("mesh has ghost nodes: border elements need the ghost diag / rhs buffers");
@@ -1509,20 +1281,13 @@ int l3k_mf_diag_rhs(l3k_mf* mf, int which, const double* d_dirichlet_vals, size_
     if (!inst)
         return -4;
     if (int rc = forEachLaunchRange(mf, which, a, [&](l3k::dev::ElemArgs& r) {
-            return inst->diag_rhs(r, mf->blob.empty() ? nullptr : mf->blob.data(), mf->ctx->stream);
+            return inst->diag_rhs(r, mf->blobPtr(), mf->ctx->stream);
         }))
         return rc;
     for (l3k_bnd* b : mf->boundary_terms)
         if (int rc = bndDiagRhsImpl(b, which, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, d_diag_ghost, d_rhs_ghost, ldrg))
             return rc;
-    if (finalize && mf->mesh->owned_dirichlet_rows.n > 0 && d_diag)
-    {
-        const auto& rows = mf->mesh->owned_dirichlet_rows;
-        hipLaunchKernelGGL(dirichletFinalizeKernel, dim3(gridFor(int64_t(rows.n))), dim3(256), 0, mf->ctx->stream, rows.ptr,
-                           int64_t(rows.n), d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, mf->n_rhs);
-        L3K_HIP(hipGetLastError());
-    }
-    return 0;
+    return finalize && d_diag ? l3k_mf_dirichlet_finalize(mf, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr) : 0;
 }
 
 int l3k_mf_dirichlet_finalize(l3k_mf* mf, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs, size_t ldr)
@@ -1561,7 +1326,6 @@ static int assembleRowMajorViaTiled(l3k_mf* mf, const l3k::dev::Instance* inst, 
     if (int rc = g.ensure(kd + wd, true))
         return rc;
     hipStream_t sa   = mf->ctx->stream;
-    const void* blob = mf->blob.empty() ? nullptr : mf->blob.data();
     // bitwise symmetric matrices, as the reference returns them: the x-major tiled layout and the one-pass mirroring transposition
     // (api_assembled.hip).  l3k_tuning::assemble_no_symmetrise: the plain tiled layout and the plain transposition (K[i][j] and
     // K[j][i] then differ by rounding) -- the cross-check of the former
@@ -1574,15 +1338,12 @@ static int assembleRowMajorViaTiled(l3k_mf* mf, const l3k::dev::Instance* inst, 
             g, sa, first, count, nb,
             [&](int k, int64_t at, int64_t n) {
                 l3k::dev::ElemArgs a;
-                if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+                if (int rc = assemblyArgs(mf, at, n, a))
                     return rc;
-                a.elem_begin     = at;
-                a.elem_count     = n;
-                a.elem_begin_out = 0;
                 a.K              = g.buf[k];
                 a.K_tiled        = sym ? 2 : 1;
                 a.workspace      = g.buf[k] + kd + size_t(nb - n) * inst->assemble_ws_doubles; // (the flag keeps one position per half)
-                return inst->assemble(a, blob, sa);
+                return inst->assemble(a, mf->blobPtr(), sa);
             },
             [&](int k, int64_t at, int64_t n) { // the transposition
                 double* out = d_K + size_t(at - first) * mat;
@@ -1622,16 +1383,12 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
     if (!inst)
         return -4;
     l3k::dev::ElemArgs a;
-    if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+    if (int rc = assemblyArgs(mf, first, count, a))
         return rc;
-    a.elem_begin     = first;
-    a.elem_count     = count;
-    a.elem_begin_out = 0;
     a.K              = d_K;
     a.F              = d_F;
     a.checksum       = d_checksum;
     hipStream_t s    = mf->ctx->stream;
-    const void* blob = mf->blob.empty() ? nullptr : mf->blob.data();
     // Stored row-major matrices: formed in the tiled layout (coalesced stores) and turned by a transposition kernel on a second
     // stream, sub-batch by sub-batch -- the assembly kernels cannot fill the 64-byte lines of a row-major K_e (four workgroups and
     // two iterations per line: 3.9 x write traffic).  l3k_tuning::assemble_direct_store keeps the direct store (cross-check).
@@ -1654,7 +1411,7 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
         a.workspace = mf->ws;
         if (d_checksum)
             L3K_HIP(hipMemsetAsync(d_checksum, 0, sizeof(double) * size_t(count), s));
-        if (int rc = inst->assemble(a, blob, s))
+        if (int rc = inst->assemble(a, mf->blobPtr(), s))
             return rc;
         if (int rc = readDegenerateFlags(s, flag))
             return rc;
@@ -1662,7 +1419,7 @@ int l3k_local_assemble(l3k_mf* mf, int64_t first, int64_t count, double* d_K, do
     if (d_F)
     {
         elementLocalRhs(a, d_F);
-        if (int rc = inst->diag_rhs(a, blob, s))
+        if (int rc = inst->diag_rhs(a, mf->blobPtr(), s))
             return rc;
     }
     if (sides) // the finished row-major K_e, F_e take the side systems of their elements (on the tiled route: after the transposition)
@@ -1699,11 +1456,8 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
         return -1;
     }
     l3k::dev::ElemArgs a;
-    if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+    if (int rc = assemblyArgs(mf, first, count, a))
         return rc;
-    a.elem_begin     = first;
-    a.elem_count     = count;
-    a.elem_begin_out = 0;
     a.K              = d_Kt;
     a.K_tiled        = 1;
     hipStream_t s    = mf->ctx->stream;
@@ -1711,7 +1465,7 @@ int l3k_local_assemble_tiled(l3k_mf* mf, int64_t first, int64_t count, double* d
     if (int rc = assemblyWorkspace(mf, inst, count, flag))
         return rc;
     a.workspace = mf->ws;
-    if (int rc = inst->assemble(a, mf->blob.empty() ? nullptr : mf->blob.data(), s))
+    if (int rc = inst->assemble(a, mf->blobPtr(), s))
         return rc;
     return readDegenerateFlags(s, flag);
 }
@@ -1769,7 +1523,6 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
     if (int rc = g.ensure(kd + fd + wd, true))
         return rc;
     hipStream_t         sa      = mf->ctx->stream;
-    const void*         blob    = mf->blob.empty() ? nullptr : mf->blob.data();
     unsigned long long* d_count = n_missing ? mf->ctx->missCounter() : nullptr;
     if (d_count)
         L3K_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), sa));
@@ -1781,11 +1534,8 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
             g, sa, first, count, nb,
             [&](int k, int64_t at, int64_t n) {
                 l3k::dev::ElemArgs a;
-                if (int rc = fillArgs(mf, 2, mf->n_rhs, a))
+                if (int rc = assemblyArgs(mf, at, n, a))
                     return rc;
-                a.elem_begin     = at;
-                a.elem_count     = n;
-                a.elem_begin_out = 0;
                 a.K              = g.buf[k];
                 a.K_tiled        = tiled;
                 a.F              = d_rhs ? g.buf[k] + kd : nullptr;
@@ -1793,13 +1543,13 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
                 // (the kernels keep the degenerate-element flag behind the coefficients of THEIR elem_count elements: a short last
                 // sub-batch works in the tail of the half, so that the flag has one position per half)
                 a.workspace      = g.buf[k] + kd + fd + size_t(nb - n) * inst->assemble_ws_doubles;
-                if (int rc = inst->assemble(a, blob, sa))
+                if (int rc = inst->assemble(a, mf->blobPtr(), sa))
                     return rc;
                 if (!d_rhs)
                     return 0;
                 L3K_HIP(hipMemsetAsync(a.F, 0, sizeof(double) * size_t(n) * Nd * R, sa));
                 elementLocalRhs(a, a.F);
-                return inst->diag_rhs(a, blob, sa);
+                return inst->diag_rhs(a, mf->blobPtr(), sa);
             },
             [&](int k, int64_t at, int64_t n) {
                 return launchAssembledScatter(mf, at, n, g.buf[k], d_rhs ? g.buf[k] + kd : nullptr, d_row_ptr, d_col_ind, d_values, d_rhs, ldr,
@@ -1829,61 +1579,25 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
         setError("kernel id %d is not a boundary equation kernel", kernel_id);
         return -1;
     }
-    if (k->kp.dimension != mesh->dim)
-    {
-        setError("kernel dimension %d != mesh dimension %d%s", k->kp.dimension, mesh->dim, quadsNote(mesh));
-        return -1;
-    }
-    if (kparam_blob && kparam_bytes != k->bytes)
-    {
-        setError("kernel %s expects a %zu-byte parameter block, got %zu", k->name, k->bytes, kparam_bytes);
-        return -1;
-    }
+    if (int rc = checkKernelDim(k->kp, mesh))
+        return rc;
+    if (int rc = checkParamBlock(*k, kparam_blob, kparam_bytes))
+        return rc;
     if (n_rhs < 1 || k->kp.n_unknowns > l3k::dev::max_unknowns)
     {
         setError("n_rhs must be >= 1 and n_unknowns <= %d", l3k::dev::max_unknowns);
         return -1;
     }
-    for (int64_t i = 0; i < n_faces; ++i) // operand shapes must match what the kernel assumes
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
-        {
-            setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
-                     int(face_side[i]));
-            return -1;
-        }
-    const l3k_asmopts o = opts ? *opts : l3k_asmopts{1, 0, 0};
-    auto              b = std::make_unique< l3k_bnd >();
-    b->ctx = ctx, b->mesh = mesh, b->kernel_id = kernel_id, b->n_rhs = n_rhs, b->kp = k->kp;
-    b->nq = l3k_n_qps1d(mesh->order, o.value_order, o.derivative_order);
-    if (kparam_blob)
-        b->blob.assign(static_cast< const char* >(kparam_blob), static_cast< const char* >(kparam_blob) + kparam_bytes);
-    for (int u = 0; u < l3k::dev::max_unknowns; ++u)
-        b->field_inds[u] = 0;
-    for (int u = 0; u < k->kp.n_unknowns; ++u)
-    {
-        const int fi = field_inds ? field_inds[u] : u;
-        if (fi < 0 || fi >= mesh->dofs_per_node)
-        {
-            setError("field_inds[%d] = %d outside [0, dofs_per_node = %d)", u, fi, mesh->dofs_per_node);
-            return -1;
-        }
-        b->field_inds[u] = fi;
-    }
-    // sides of interior elements first (they need no ghost data, like the interior elements themselves)
+    if (int rc = l3k::host::checkSides(mesh->dim, mesh->n_elems, n_faces, face_elem, face_side))
+        return rc;
+    auto b = std::make_unique< l3k_bnd >();
+    b->init(ctx, mesh, *k, quadraturePoints(mesh, opts), n_rhs, kparam_blob, kparam_bytes);
+    if (int rc = resolveFieldInds(field_inds, k->kp.n_unknowns, mesh, b->field_inds))
+        return rc;
     std::vector< int64_t > fe;
     std::vector< uint8_t > fs;
-    for (int pass = 0; pass < 2; ++pass)
-    {
-        for (int64_t i = 0; i < n_faces; ++i)
-            if ((face_elem[i] >= mesh->n_interior) == (pass == 1))
-            {
-                fe.push_back(face_elem[i]);
-                fs.push_back(face_side[i]);
-            }
-        if (pass == 0)
-            b->n_interior_faces = int64_t(fe.size());
-    }
-    b->n_faces = n_faces;
+    b->n_interior_faces = l3k::host::interiorSidesFirst(mesh->n_interior, n_faces, face_elem, face_side, fe, fs);
+    b->n_faces          = n_faces;
     b->list_elem.assign(face_elem, face_elem + n_faces); // (the caller's order: what the assembly entry points index)
     b->list_side.assign(face_side, face_side + n_faces);
     if (ctx->deterministic)
@@ -1898,60 +1612,21 @@ int l3k_bnd_create(l3k_ctx* ctx, l3k_mesh* mesh, int kernel_id, const void* kpar
             setError("deterministic mode was enabled after this mesh was created: create the mesh with the mode on");
             return -1;
         }
-        const int                                nv = 1 << mesh->dim;
-        std::unordered_map< uint32_t, uint64_t > used;
-        std::vector< uint8_t >                   colour(fe.size());
-        int                                      n_colours = 0;
-        for (size_t i = 0; i < fe.size(); ++i)
-        {
-            uint64_t taken = 0;
-            for (int v = 0; v < nv; ++v)
-            {
-                const auto it = used.find(mesh->det_corner_nodes[size_t(fe[i]) * nv + v]);
-                if (it != used.end())
-                    taken |= it->second;
-            }
-            int c = 0;
-            while (c < 64 && ((taken >> c) & 1u))
-                ++c;
-            if (c == 64)
-            {
-                setError("deterministic mode: more than 64 colours needed for the boundary sides");
-                return -1;
-            }
-            colour[i] = uint8_t(c);
-            n_colours = std::max(n_colours, c + 1);
-            for (int v = 0; v < nv; ++v)
-                used[mesh->det_corner_nodes[size_t(fe[i]) * nv + v]] |= uint64_t(1) << c;
-        }
-        std::vector< size_t > order(fe.size());
-        for (size_t i = 0; i < order.size(); ++i)
-            order[i] = i;
-        auto by_colour = [&](size_t x, size_t y) { return colour[x] < colour[y]; };
-        std::stable_sort(order.begin(), order.begin() + b->n_interior_faces, by_colour);
-        std::stable_sort(order.begin() + b->n_interior_faces, order.end(), by_colour);
+        l3k::host::ColourPlan plan;
+        if (int rc = l3k::host::colourItems(n_faces, b->n_interior_faces, fe.data(), mesh->det_corner_nodes.data(), 1 << mesh->dim,
+                                            " for the boundary sides", plan))
+            return rc;
         std::vector< int64_t > fe2(fe.size());
         std::vector< uint8_t > fs2(fs.size());
-        for (size_t i = 0; i < order.size(); ++i)
-            fe2[i] = fe[order[i]], fs2[i] = fs[order[i]];
-        for (int cls = 0; cls < 2; ++cls)
-        {
-            const int64_t lo = cls ? b->n_interior_faces : 0, hi = cls ? n_faces : b->n_interior_faces;
-            b->det_ptr[cls].assign(static_cast< size_t >(n_colours) + 1, hi);
-            int64_t i = lo;
-            for (int c = 0; c < n_colours; ++c)
-            {
-                b->det_ptr[cls][c] = i;
-                while (i < hi && colour[order[size_t(i)]] == c)
-                    ++i;
-            }
-        }
+        for (size_t i = 0; i < fe.size(); ++i)
+            fe2[i] = fe[size_t(plan.order[i])], fs2[i] = fs[size_t(plan.order[i])];
+        std::swap(b->det_ptr, plan.ptr);
         fe.swap(fe2);
         fs.swap(fs2);
     }
     L3K_HIP(hipSetDevice(ctx->device));
-    const auto block = l3k::host::deviceTableBlock(mesh->order, b->nq);
-    if (int rc = b->tables.upload(block.data(), block.size(), ctx->stream))
+    std::vector< double > block; // (host staging: outlives the synchronisation below)
+    if (int rc = uploadTables(mesh, b->nq, ctx->stream, block, b->tables))
         return rc;
     if (int rc = b->face_elem.upload(fe.data(), fe.size(), ctx->stream))
         return rc;
@@ -1973,14 +1648,7 @@ int l3k_bnd_set_fields(l3k_bnd* bnd, const double* d_soa, size_t ld)
         setError("null bnd");
         return -1;
     }
-    if (d_soa && ld < size_t(bnd->mesh->n_owned_nodes + bnd->mesh->n_ghost_nodes))
-    {
-        setError("field leading dimension %zu < number of local nodes", ld);
-        return -1;
-    }
-    bnd->fields = d_soa;
-    bnd->ldf    = ld;
-    return 0;
+    return setFields(*bnd, d_soa, ld);
 }
 int l3k_bnd_set_time(l3k_bnd* bnd, double time)
 {

@@ -102,14 +102,9 @@ struct SideShape
 };
 const l3k::dev::BoundaryInstance* sideInstance(const l3k_bnd* b, const char* what, SideShape& sh)
 {
-    const auto* inst = l3k::dev::findBoundaryInstance(b->kernel_id, b->mesh->order, b->nq, b->n_rhs);
+    const auto* inst = boundaryInstanceFor(b, b->n_rhs, what);
     if (!inst)
-    {
-        setError("%s: no device instantiation for boundary kernel %d, order %d, nq %d, ncols %d: add it to "
-                 "L3K_FOR_EACH_BOUNDARY_INSTANCE (l3ster_amd/csrc/user_kernels.hpp) and rebuild",
-                 what, b->kernel_id, b->mesh->order, b->nq, b->n_rhs);
         return nullptr;
-    }
     if (!inst->assemble)
     {
         setError("%s: this boundary kernel shape has no assembly launcher", what);
@@ -123,15 +118,6 @@ const l3k::dev::BoundaryInstance* sideInstance(const l3k_bnd* b, const char* wha
     sh.max_sides = sh.max_sides < 1 ? 1 : sh.max_sides;
     sh.coef      = inst->assemble_ws_doubles;
     return inst;
-}
-int checkFields(const l3k_bnd* b, const char* what)
-{
-    if (b->kp.n_fields > 0 && !b->fields)
-    {
-        setError("%s: boundary kernel reads %d external fields but l3k_bnd_set_fields was not called", what, b->kp.n_fields);
-        return -1;
-    }
-    return 0;
 }
 l3k::dev::SideAsmArgs sideArgs(const l3k_bnd* b, const l3k_bnd::SideList& l)
 {
@@ -154,10 +140,6 @@ int ensureCoef(l3k_bnd* b, size_t doubles)
     b->coef_ws = DevBuf< double >{};
     return b->coef_ws.alloc(doubles);
 }
-const void* blobOf(const l3k_bnd* b)
-{
-    return b->blob.empty() ? nullptr : b->blob.data();
-}
 
 // The sides [lo, lo + count) of list `l` of the term, formed in sub-batches and summed into the CSR values / rhs
 int sidesIntoGlobal(l3k_bnd* b, const l3k_bnd::SideList& l, int64_t lo, int64_t count, const int64_t* d_row_ptr, const int32_t* d_col_ind,
@@ -170,7 +152,7 @@ int sidesIntoGlobal(l3k_bnd* b, const l3k_bnd::SideList& l, int64_t lo, int64_t 
     const auto* inst = sideInstance(b, what, sh);
     if (!inst)
         return -4;
-    if (int rc = checkFields(b, what))
+    if (int rc = checkFieldsSet(b, what))
         return rc;
     L3K_HIP(hipSetDevice(b->ctx->device));
     const size_t per_side = sizeof(double) * (size_t(sh.Nd) * sh.Nd + size_t(sh.Nd) * sh.R + sh.coef);
@@ -196,7 +178,7 @@ int sidesIntoGlobal(l3k_bnd* b, const l3k_bnd::SideList& l, int64_t lo, int64_t 
                 a.K                     = g.buf[k];
                 a.F                     = d_rhs ? g.buf[k] + kd : nullptr;
                 a.coef                  = g.buf[k] + kd + fd;
-                return inst->assemble(a, blobOf(b), sa);
+                return inst->assemble(a, b->blobPtr(), sa);
             },
             [&](int k, int64_t at, int64_t n) {
                 return launchAssembledScatterRows(b->ctx, b->mesh, l.nodes.ptr, b->kp.n_unknowns, b->n_rhs, b->field_inds, at, n, g.buf[k],
@@ -249,7 +231,7 @@ int checkAssembleBoundary(const l3k_mf* mf, const char* what)
         SideShape sh;
         if (!sideInstance(b, what, sh))
             return -1;
-        if (int rc = checkFields(b, what))
+        if (int rc = checkFieldsSet(b, what))
             return rc;
     }
     return 0;
@@ -298,7 +280,7 @@ int accumulateBoundarySides(l3k_mf* mf, int64_t first, int64_t count, double* d_
             a.elem_base             = first;
             a.accumulate            = 1;
             for (a.round = 0; a.round < rounds; ++a.round)
-                if (int rc = inst->assemble(a, blobOf(b), s))
+                if (int rc = inst->assemble(a, b->blobPtr(), s))
                     return rc;
             at = end;
         }
@@ -345,7 +327,7 @@ int l3k_bnd_local_assemble(l3k_bnd* bnd, int64_t first, int64_t count, double* d
     const auto* inst = sideInstance(bnd, "l3k_bnd_local_assemble", sh);
     if (!inst)
         return -4;
-    if (int rc = checkFields(bnd, "l3k_bnd_local_assemble"))
+    if (int rc = checkFieldsSet(bnd, "l3k_bnd_local_assemble"))
         return rc;
     if (int rc = ensureInOrder(bnd))
         return rc;
@@ -361,7 +343,7 @@ int l3k_bnd_local_assemble(l3k_bnd* bnd, int64_t first, int64_t count, double* d
         a.K                     = d_K ? d_K + size_t(done) * sh.Nd * sh.Nd : nullptr;
         a.F                     = d_F ? d_F + size_t(done) * sh.Nd * sh.R : nullptr;
         a.coef                  = bnd->coef_ws.ptr;
-        if (int rc = inst->assemble(a, blobOf(bnd), bnd->ctx->stream))
+        if (int rc = inst->assemble(a, bnd->blobPtr(), bnd->ctx->stream))
             return rc;
         done += n;
         if (done < count) // (the next launch reuses, and may regrow, the coefficient workspace)

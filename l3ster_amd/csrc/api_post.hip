@@ -1,5 +1,6 @@
 // api_post.hip -- post-processing entry points of libl3k.so: integrals / L2 norms of residual kernels and values at nodes.
 #include "objects.hpp"
+#include "host/mesh_plan.hpp"
 
 using l3k::api::findResidual;
 
@@ -35,6 +36,46 @@ __global__ void averageValuesKernel(const double* __restrict__ sum, const double
         if (count[i] > 0.)
             values[i] = sum[i] / count[i];
 }
+// the fields a residual kernel reads are passed with the call
+int checkFieldsGiven(const l3k::api::KernelMeta& k, const l3k_mesh* mesh, const double* d_fields, size_t ldf)
+{
+    if (k.kp.n_fields == 0 || (d_fields && ldf >= size_t(mesh->n_owned_nodes + mesh->n_ghost_nodes)))
+        return 0;
+    setError("kernel %s reads %d fields: pass them as SoA with ld >= number of local nodes", k.name, k.kp.n_fields);
+    return -1;
+}
+// What a post-processing call puts on the device: the tables of (order, nq) and, for n_faces >= 0, the side list (the host
+// staging lives as long as they do), and the launch over all elements / all sides of the list that reads them
+struct PostOperands
+{
+    DevBuf< double >      tables;
+    DevBuf< int64_t >     fe;
+    DevBuf< uint8_t >     fs;
+    std::vector< double > block;
+    int upload(const l3k_mesh* mesh, int nq, hipStream_t s, int64_t n_faces, const int64_t* face_elem, const uint8_t* face_side)
+    {
+        if (int rc = uploadTables(mesh, nq, s, block, tables))
+            return rc;
+        if (n_faces < 0)
+            return 0;
+        if (int rc = fe.upload(face_elem, size_t(n_faces), s))
+            return rc;
+        return fs.upload(face_side, size_t(n_faces), s);
+    }
+    l3k::dev::ElemArgs args(const l3k_mesh* mesh, const double* d_fields, size_t ldf, double time, int64_t n_faces) const
+    {
+        l3k::dev::ElemArgs a{};
+        a.elem_nodes = mesh->elem_nodes.ptr;
+        a.elem_verts = mesh->elem_verts.ptr;
+        a.tables     = tables.ptr;
+        a.fields     = d_fields;
+        a.ldf        = ldf;
+        a.time       = time;
+        a.elem_begin = 0, a.elem_count = mesh->n_elems;
+        a.face_elem = fe.ptr, a.face_side = fs.ptr, a.face_begin = 0, a.face_count = n_faces >= 0 ? n_faces : 0;
+        return a;
+    }
+};
 } // namespace
 
 extern "C" {
@@ -71,42 +112,24 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
         setError("unknown residual kernel id %d", residual_id);
         return -1;
     }
-    if (k->kp.dimension != mesh->dim)
-    {
-        setError("kernel dimension %d != mesh dimension %d%s", k->kp.dimension, mesh->dim, quadsNote(mesh));
-        return -1;
-    }
-    if (kparam_blob && kparam_bytes != k->bytes)
-    {
-        setError("kernel %s expects a %zu-byte parameter block, got %zu", k->name, k->bytes, kparam_bytes);
-        return -1;
-    }
-    if (k->kp.n_fields > 0 && (!d_fields || ldf < size_t(mesh->n_owned_nodes + mesh->n_ghost_nodes)))
-    {
-        setError("kernel %s reads %d fields: pass them as SoA with ld >= number of local nodes", k->name, k->kp.n_fields);
-        return -1;
-    }
+    if (int rc = checkKernelDim(k->kp, mesh))
+        return rc;
+    if (int rc = checkParamBlock(*k, kparam_blob, kparam_bytes))
+        return rc;
+    if (int rc = checkFieldsGiven(*k, mesh, d_fields, ldf))
+        return rc;
     const bool side = n_faces >= 0;
-    for (int64_t i = 0; i < n_faces; ++i)
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
-        {
-            setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
-                     int(face_side[i]));
-            return -1;
-        }
+    if (int rc = l3k::host::checkSides(mesh->dim, mesh->n_elems, n_faces, face_elem, face_side))
+        return rc;
     const int E = k->kp.n_equations;
     for (int i = 0; i < E; ++i)
         h_out[i] = 0.;
     const int64_t count = side ? n_faces : mesh->n_elems;
     if (count == 0)
         return 0;
-    const l3k_asmopts o  = opts ? *opts : l3k_asmopts{1, 0, 0};
-    const int         nq = l3k_n_qps1d(mesh->order, o.value_order, o.derivative_order);
-    if (nq < mesh->order + 1)
-    {
-        setError("nq = %d < p+1 = %d: the collocation-derivative device algorithm needs nq >= p+1", nq, mesh->order + 1);
-        return -1;
-    }
+    const int nq = quadraturePoints(mesh, opts);
+    if (int rc = checkCollocation(nq, mesh))
+        return rc;
     const auto* inst = l3k::dev::findIntegralInstance(residual_id, mesh->order, nq);
     if (!inst)
     {
@@ -116,31 +139,14 @@ int l3k_integrate(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const void* kpa
         return -4;
     }
     L3K_HIP(hipSetDevice(ctx->device));
-    hipStream_t        s = ctx->stream;
-    DevBuf< double >   tables, partial;
-    DevBuf< int64_t >  fe;
-    DevBuf< uint8_t >  fs;
-    const auto         block = l3k::host::deviceTableBlock(mesh->order, nq);
-    if (int rc = tables.upload(block.data(), block.size(), s))
+    hipStream_t      s = ctx->stream;
+    PostOperands     ops;
+    DevBuf< double > partial;
+    if (int rc = ops.upload(mesh, nq, s, n_faces, face_elem, face_side))
         return rc;
-    if (side)
-    {
-        if (int rc = fe.upload(face_elem, size_t(n_faces), s))
-            return rc;
-        if (int rc = fs.upload(face_side, size_t(n_faces), s))
-            return rc;
-    }
     partial.n = size_t(count + 1) * E; // [count][E] partial sums + [E] result
     L3K_HIP(hipMalloc(reinterpret_cast< void** >(&partial.ptr), partial.n * sizeof(double)));
-    l3k::dev::ElemArgs a{};
-    a.elem_nodes = mesh->elem_nodes.ptr;
-    a.elem_verts = mesh->elem_verts.ptr;
-    a.tables     = tables.ptr;
-    a.fields     = d_fields;
-    a.ldf        = ldf;
-    a.time       = time;
-    a.elem_begin = 0, a.elem_count = mesh->n_elems;
-    a.face_elem = fe.ptr, a.face_side = fs.ptr, a.face_begin = 0, a.face_count = side ? n_faces : 0;
+    l3k::dev::ElemArgs a = ops.args(mesh, d_fields, ldf, time, n_faces);
     a.partial = partial.ptr;
     a.square  = square;
     if (int rc = (side ? inst->boundary : inst->domain)(a, kparam_blob, s))
@@ -175,29 +181,18 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
                  k->kp.dimension != mesh->dim ? quadsNote(mesh) : "");
         return -1;
     }
-    if (kparam_blob && kparam_bytes != k->bytes)
-    {
-        setError("kernel %s expects a %zu-byte parameter block, got %zu", k->name, k->bytes, kparam_bytes);
-        return -1;
-    }
-    if (k->kp.n_fields > 0 && (!d_fields || ldf < size_t(mesh->n_owned_nodes + mesh->n_ghost_nodes)))
-    {
-        setError("kernel %s reads %d fields: pass them as SoA with ld >= number of local nodes", k->name, k->kp.n_fields);
-        return -1;
-    }
+    if (int rc = checkParamBlock(*k, kparam_blob, kparam_bytes))
+        return rc;
+    if (int rc = checkFieldsGiven(*k, mesh, d_fields, ldf))
+        return rc;
     for (int e = 0; e < k->kp.n_equations; ++e)
         if (dof_inds[e] < 0 || dof_inds[e] >= mesh->dofs_per_node)
         {
             setError("dof_inds[%d] = %d outside [0, dofs_per_node = %d)", e, dof_inds[e], mesh->dofs_per_node);
             return -1;
         }
-    for (int64_t i = 0; i < n_faces; ++i)
-        if (face_elem[i] < 0 || face_elem[i] >= mesh->n_elems || face_side[i] >= 2 * mesh->dim)
-        {
-            setError("side %lld = (element %lld, side %d) is outside the mesh", (long long)i, (long long)face_elem[i],
-                     int(face_side[i]));
-            return -1;
-        }
+    if (int rc = l3k::host::checkSides(mesh->dim, mesh->n_elems, n_faces, face_elem, face_side))
+        return rc;
     const bool    side  = n_faces >= 0;
     const int64_t count = side ? n_faces : mesh->n_elems;
     if (count == 0)
@@ -210,30 +205,12 @@ int l3k_values_at_nodes(l3k_ctx* ctx, l3k_mesh* mesh, int residual_id, const voi
         return -4;
     }
     L3K_HIP(hipSetDevice(ctx->device));
-    hipStream_t       s = ctx->stream;
-    DevBuf< double >  tables;
-    DevBuf< int64_t > fe;
-    DevBuf< uint8_t > fs;
-    const auto        block = l3k::host::deviceTableBlock(mesh->order, inst->nq);
-    if (int rc = tables.upload(block.data(), block.size(), s))
+    hipStream_t  s = ctx->stream;
+    PostOperands ops;
+    if (int rc = ops.upload(mesh, inst->nq, s, n_faces, face_elem, face_side))
         return rc;
-    if (side)
-    {
-        if (int rc = fe.upload(face_elem, size_t(n_faces), s))
-            return rc;
-        if (int rc = fs.upload(face_side, size_t(n_faces), s))
-            return rc;
-    }
-    l3k::dev::ElemArgs a{};
-    a.elem_nodes = mesh->elem_nodes.ptr;
-    a.elem_verts = mesh->elem_verts.ptr;
-    a.tables     = tables.ptr;
-    a.fields     = d_fields;
-    a.ldf        = ldf;
-    a.time       = time;
-    a.dofs_per_node = mesh->dofs_per_node;
-    a.elem_begin = 0, a.elem_count = mesh->n_elems;
-    a.face_elem = side ? fe.ptr : nullptr, a.face_side = fs.ptr, a.face_begin = 0, a.face_count = side ? n_faces : 0;
+    l3k::dev::ElemArgs a = ops.args(mesh, d_fields, ldf, time, n_faces);
+    a.dofs_per_node      = mesh->dofs_per_node;
     for (int e = 0; e < k->kp.n_equations; ++e)
         a.field_inds[e] = dof_inds[e];
     a.node_sum   = d_sum;

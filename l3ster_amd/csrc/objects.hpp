@@ -198,6 +198,119 @@ inline int checkRange(const l3k_mesh* m, int64_t first, int64_t count)
     return 0;
 }
 struct l3k_bnd;
+namespace l3k::api
+{
+struct KernelMeta
+{
+    int         id;
+    l3k_kparams kp;
+    const char* name;
+    size_t      bytes;
+    bool        boundary = false;
+};
+// registered equation kernels (built in or announced by a plugin) / residual kernels by id; nullptr if unknown
+const KernelMeta* findKernel(int id);
+const KernelMeta* findResidual(int id);
+} // namespace l3k::api
+// What a domain system (l3k_mf) and a boundary term (l3k_bnd) share: an equation kernel on a mesh with its operands
+struct KernelTerm
+{
+    l3k_ctx*            ctx  = nullptr;
+    l3k_mesh*           mesh = nullptr;
+    int                 kernel_id = 0, nq = 0, n_rhs = 0;
+    l3k_kparams         kp{};
+    std::vector< char > blob;
+    int                 field_inds[l3k::dev::max_unknowns] = {};
+    DevBuf< double >    tables;
+    const double*       fields = nullptr;
+    size_t              ldf    = 0;
+    double              time   = 0.;
+    const void* blobPtr() const { return blob.empty() ? nullptr : blob.data(); } // the kernel's parameter block, if it has one
+    void        init(l3k_ctx* c, l3k_mesh* m, const l3k::api::KernelMeta& k, int nq_, int n_rhs_, const void* kparam_blob, size_t kparam_bytes)
+    {
+        ctx = c, mesh = m, kernel_id = k.id, nq = nq_, n_rhs = n_rhs_, kp = k.kp;
+        if (kparam_blob)
+            blob.assign(static_cast< const char* >(kparam_blob), static_cast< const char* >(kparam_blob) + kparam_bytes);
+    }
+};
+// The checks of what comes from outside, one each (0, or -1 with the error set); every entry point calls the ones it makes
+inline int checkKernelDim(const l3k_kparams& kp, const l3k_mesh* mesh)
+{
+    if (kp.dimension == mesh->dim)
+        return 0;
+    setError("kernel dimension %d != mesh dimension %d%s", kp.dimension, mesh->dim, quadsNote(mesh));
+    return -1;
+}
+inline int checkParamBlock(const l3k::api::KernelMeta& k, const void* kparam_blob, size_t kparam_bytes)
+{
+    if (!kparam_blob || kparam_bytes == k.bytes)
+        return 0;
+    setError("kernel %s expects a %zu-byte parameter block, got %zu", k.name, k.bytes, kparam_bytes);
+    return -1;
+}
+// out[u] = field_inds[u] (null: u) for the kernel's unknowns, each inside [0, dofs_per_node)
+inline int resolveFieldInds(const int* field_inds, int n_unknowns, const l3k_mesh* mesh, int* out)
+{
+    for (int u = 0; u < n_unknowns; ++u)
+    {
+        const int fi = field_inds ? field_inds[u] : u;
+        if (fi < 0 || fi >= mesh->dofs_per_node)
+        {
+            setError("field_inds[%d] = %d outside [0, dofs_per_node = %d)", u, fi, mesh->dofs_per_node);
+            return -1;
+        }
+        out[u] = fi;
+    }
+    return 0;
+}
+// quadrature points per direction from the assembly options (null: value order 1)
+inline int quadraturePoints(const l3k_mesh* mesh, const l3k_asmopts* opts)
+{
+    const l3k_asmopts o = opts ? *opts : l3k_asmopts{1, 0, 0};
+    return l3k_n_qps1d(mesh->order, o.value_order, o.derivative_order);
+}
+inline int checkCollocation(int nq, const l3k_mesh* mesh)
+{
+    if (nq >= mesh->order + 1)
+        return 0;
+    setError("nq = %d < p+1 = %d: the collocation-derivative device algorithm needs nq >= p+1", nq, mesh->order + 1);
+    return -1;
+}
+// the 1-D table block of (order, nq) into `block` and from there to the device; `block` must outlive the copy on s
+inline int uploadTables(const l3k_mesh* mesh, int nq, hipStream_t s, std::vector< double >& block, DevBuf< double >& tables)
+{
+    block = l3k::host::deviceTableBlock(mesh->order, nq);
+    return tables.upload(block.data(), block.size(), s);
+}
+// the fields a kernel reads were set (T = l3k_mf / l3k_bnd names the kernel kind and the setter; `what`: optional prefix)
+template < typename T >
+int checkFieldsSet(const T* t, const char* what = nullptr)
+{
+    if (t->kp.n_fields == 0 || t->fields)
+        return 0;
+    setError("%s%s%s reads %d external fields but %s was not called", what ? what : "", what ? ": " : "", T::kernel_noun, t->kp.n_fields,
+             T::fields_setter);
+    return -1;
+}
+inline int checkColumns(int ncols, int n_rhs)
+{
+    if (ncols >= 1 && ncols <= n_rhs)
+        return 0;
+    setError("number of columns (%d) must be in [1, n_rhs = %d]", ncols, n_rhs); // algsys/MatrixFreeSystem.hpp:1035-1037
+    return -1;
+}
+// l3k_*_set_fields: SoA fields with a leading dimension of at least the local nodes (null: none)
+inline int setFields(KernelTerm& t, const double* d_soa, size_t ld)
+{
+    if (d_soa && ld < size_t(t.mesh->n_owned_nodes + t.mesh->n_ghost_nodes))
+    {
+        setError("field leading dimension %zu < number of local nodes", ld);
+        return -1;
+    }
+    t.fields = d_soa;
+    t.ldf    = ld;
+    return 0;
+}
 // The sub-batch pipeline of the assembled path (runSubBatches below): two halves of element-system buffers, a
 // second stream that consumes half i & 1 while the context's stream forms sub-batch i + 1 into the other, and the events that
 // order the reuse of the halves.  Kept across calls (allocating gigabytes per call cost more than the pipeline saved)
@@ -252,20 +365,11 @@ struct SubBatchPipe
         return 0;
     }
 };
-struct l3k_mf
+struct l3k_mf : KernelTerm
 {
+    static constexpr const char *kernel_noun = "kernel", *fields_setter = "l3k_mf_set_fields";
     std::vector< l3k_bnd* > boundary_terms; // attached boundary equation kernels (not owned)
-    l3k_ctx*            ctx;
-    l3k_mesh*           mesh;
-    int                 kernel_id, nq, n_rhs;
-    l3k_kparams         kp;
-    std::vector< char > blob;
-    int                 field_inds[l3k::dev::max_unknowns];
-    DevBuf< double >    tables;
     std::vector< double > tables_host;
-    const double*       fields = nullptr;
-    size_t              ldf    = 0;
-    double              time   = 0.;
     bool                dense = false, fuse = false;
     double*             energy_target = nullptr; // l3k_mf_apply_energy: where the element kernel adds x^T A x (device)
     int                 energy_done   = 0;       // ... how many element launches did (the launcher counts)
@@ -343,24 +447,15 @@ struct l3k_csr
 };
 
 // a boundary equation kernel on a list of element sides (assembleProblem(kernel, boundary_ids) of the reference)
-struct l3k_bnd
+struct l3k_bnd : KernelTerm
 {
-    l3k_ctx*              ctx;
-    l3k_mesh*             mesh;
-    int                   kernel_id, nq, n_rhs;
-    l3k_kparams           kp;
-    std::vector< char >   blob;
-    int                   field_inds[l3k::dev::max_unknowns];
-    DevBuf< double >      tables;
+    static constexpr const char *kernel_noun = "boundary kernel", *fields_setter = "l3k_bnd_set_fields";
     DevBuf< int64_t >     face_elem; // sides of interior elements first
     DevBuf< uint8_t >     face_side;
     int64_t               n_faces = 0, n_interior_faces = 0;
     // deterministic mode: the two classes of sides sorted by colour (sides of one colour share no node); det_ptr[cls][c] ..
     // det_ptr[cls][c + 1] = positions of colour c in face_elem / face_side
     std::vector< int64_t > det_ptr[2];
-    const double*         fields = nullptr;
-    size_t                ldf    = 0;
-    double                time   = 0.;
     // ---- assembly of the side systems (api_bnd_assemble.hip): two more orders of the list, built on first use
     struct SideList
     {
@@ -379,23 +474,10 @@ struct l3k_bnd
     DevBuf< double >       coef_ws;      // coefficient workspace of l3k_bnd_local_assemble and of the accumulating route
 };
 
-
-namespace l3k::api
-{
-struct KernelMeta
-{
-    int         id;
-    l3k_kparams kp;
-    const char* name;
-    size_t      bytes;
-    bool        boundary = false;
-};
-// registered equation kernels (built in or announced by a plugin) / residual kernels by id; nullptr if unknown
-const KernelMeta* findKernel(int id);
-const KernelMeta* findResidual(int id);
-} // namespace l3k::api
 // api.hip: the system's device instantiation for `ncols` columns, or nullptr with the error set (callers return -4)
 const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols);
+// ... of a boundary term (`what`: optional prefix of the message)
+const l3k::dev::BoundaryInstance* boundaryInstanceFor(const l3k_bnd* b, int ncols, const char* what = nullptr);
 // api.hip: the refusals of an apply that its operands alone decide (fields set, number of columns, leading dimensions, alignment
 // of x, y and, where given, the ghost buffers): 0, or -1 with the error set.  The apply entry points call it before their first launch
 int checkApplyOperands(const l3k_mf* mf, int ncols, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, const double* d_y,

@@ -1,6 +1,6 @@
 """Sanitizer leg on the CPU build (the reference's CI runs its tests under ASan and UBSan, .github/workflows/ci.yml:39-134;
 GPU AddressSanitizer is not available on the pool).  tests/sanitize/san_driver.cpp links the HOST-side product code -- 1-D tables, the
-cube-mesh partitioner, the native mesh / results files -- and the CPU oracle into one executable; built once with
+cube-mesh partitioner, the mesh plan, the native mesh / results files -- and the CPU oracle into one executable; built once with
 -fsanitize=address,undefined and once with -fsanitize=thread (the oracle's threaded element loop adds into the result vector with atomic
 adds, the reference's TBB + atomic_ref scheme), both with -fno-sanitize-recover: any report aborts the run."""
 import os
@@ -13,7 +13,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ["tests/sanitize/san_driver.cpp", "l3ster_amd/csrc/host/tables.cpp", "l3ster_amd/csrc/host/cube_mesh.cpp",
-           "l3ster_amd/csrc/host/mesh_file.cpp", "l3ster_amd/csrc/host/native_io.cpp", "oracle/oracle.cpp"]
+           "l3ster_amd/csrc/host/mesh_file.cpp", "l3ster_amd/csrc/host/native_io.cpp", "l3ster_amd/csrc/host/mesh_plan.cpp",
+           "oracle/oracle.cpp"]
 LEGS = {"asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "tsan": ["-fsanitize=thread"]}
 
 
