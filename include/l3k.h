@@ -866,6 +866,28 @@ int l3k_hostmesh_view_get(const l3k_hostmesh* hm, l3k_hostmesh_view* out);
  * Shared edges / faces are found by sorting their vertex keys on the device; every element is processed in parallel.    */
 int l3k_elevate_order(l3k_ctx* ctx, int64_t n_elems, const uint32_t* conn, int64_t n_vertices, int order, uint32_t* elem_nodes,
                       int64_t* n_nodes, int64_t* n_noninternal);
+/* The quad twin (mesh::convertMeshToOrder on Quad elements, mesh/ConvertMeshToOrder.hpp:51-104): conn host, [n_elems][4], local
+ * vertex v = i + 2j; elem_nodes host, [n_elems][(order+1)^2], local node i + n j, numbered [vertices | (order-1) per unique edge |
+ * (order-1)^2 per element, contiguous per element and lexicographic].  Unique edges are numbered in the order of their sorted
+ * vertex pair; positions inside an edge run from its lower vertex id, so two elements that see an edge in opposite directions
+ * agree.  order 1..8; otherwise the argument checks of l3k_elevate_order.                                                       */
+int l3k_elevate_order_quads(l3k_ctx* ctx, int64_t n_elems, const uint32_t* conn, int64_t n_vertices, int order,
+                            uint32_t* elem_nodes, int64_t* n_nodes, int64_t* n_noninternal);
+
+/* ---- boundary elements -> (element, side) (the reference reads the dim-1 elements of a gmsh file into the domain of their
+ * entity's physical tag, mesh/ReadMesh.hpp:197-242,286-302, and MeshPartition::getBoundary(id) pairs each with the element it
+ * is a side of) -----------------------------------------------------------------------------------------------------------
+ * dim 3: conn [n_elems][8] (v = i + 2j + 4k), bnd_conn [n_bnd][4] in any order; dim 2: conn [n_elems][4] (v = i + 2j), bnd_conn
+ * [n_bnd][2].  All pointers are host pointers.  For every boundary element: the element and side (numbered as for
+ * l3k_bnd_create above: hexes 0..5 = z-, z+, y-, y+, x-, x+; quads 0..3 = y-, y+, x-, x+) whose vertex SET equals its own.  No
+ * such side, or a boundary element that repeats a vertex: face_elem = -1, face_side = 255, counted in *n_unmatched.  The sides of
+ * two elements have the set (an interface inside the mesh): the lower element index is returned and the case is counted in
+ * *n_interior.  Every element side emits its sorted vertices as a key with the value e * 2 dim + side, the pairs are sorted on
+ * the device, every boundary element takes the lower bound of its own sorted vertices: memory is two key arrays of n_elems * 2 dim
+ * entries, nothing quadratic; no floating point and one writer per output, so every run gives the same answer.
+ * Errors (-1): dim outside {2, 3}, negative counts, null arrays with non-zero counts, n_elems * 2 dim >= 2^32.                  */
+int l3k_boundary_match(l3k_ctx* ctx, int dim, int64_t n_elems, const uint32_t* conn, int64_t n_bnd, const uint32_t* bnd_conn,
+                       int64_t* face_elem, uint8_t* face_side, int64_t* n_unmatched, int64_t* n_interior);
 
 /* ---- native results file (host only; post/NativeIO.hpp:15-60 save, :115-146 LoadedResults, :277-295 loadResultsImpl) --
  * "L3STER results file\nv1.0\n// <comment>\n", size_t n_fields, size_t n_nodes_global, then n_fields arrays of

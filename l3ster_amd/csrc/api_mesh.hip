@@ -267,3 +267,271 @@ extern "C" int l3k_elevate_order(l3k_ctx* ctx, int64_t n_elems, const uint32_t* 
     *n_nodes       = *n_noninternal + n_elems * m * m * m;
     return 0;
 }
+
+// ---- quads: order elevation, and the matching of boundary elements to element sides (hexes and quads) ----------------------------
+// The reference reads the boundary elements of a gmsh file as elements of their own domain (the physical tag of their entity,
+// mesh/ReadMesh.hpp:197-242,286-302) and finds the element each one is a side of when the boundary views are built
+// (MeshPartition::getBoundary).  Here the (element, side) lists the boundary entry points take are made by the same device sort of
+// vertex keys that the elevation uses.
+namespace
+{
+// quad local vertex v = i + 2j; sides (= edges) 0 y- (v 0,1), 1 y+ (2,3), 2 x- (0,2), 3 x+ (1,3) (mesh/ElementTraits.hpp:84-95)
+__host__ __device__ inline int quadSideVert(int side, int q)
+{
+    return side < 2 ? q + 2 * side : (side - 2) + 2 * q;
+}
+__host__ __device__ inline EdgeKey sortedKey(uint32_t a, uint32_t b)
+{
+    return EdgeKey{a < b ? a : b, a < b ? b : a};
+}
+__host__ __device__ inline FaceKey sortedKey(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
+{
+    uint32_t v[4] = {a, b, c, d};
+    auto     cs   = [&](int i, int j) {
+        if (v[j] < v[i])
+        {
+            const uint32_t x = v[i];
+            v[i]             = v[j];
+            v[j]             = x;
+        }
+    };
+    cs(0, 1), cs(2, 3), cs(0, 2), cs(1, 3), cs(1, 2);
+    return FaceKey{{v[0], v[1], v[2], v[3]}};
+}
+
+template < int DIM >
+struct SideTraits;
+template <>
+struct SideTraits< 3 >
+{
+    using Key  = FaceKey;
+    using Less = FaceLess;
+    static constexpr int n_sides = 6, n_side_verts = 4, n_elem_verts = 8;
+    __host__ __device__ static Key ofElement(const uint32_t* c, int side)
+    {
+        return sortedKey(c[faceVert(side, 0, 0)], c[faceVert(side, 1, 0)], c[faceVert(side, 0, 1)], c[faceVert(side, 1, 1)]);
+    }
+    __host__ __device__ static Key  ofBoundary(const uint32_t* b) { return sortedKey(b[0], b[1], b[2], b[3]); }
+    __host__ __device__ static bool repeats(const Key& k) { return k.v[0] == k.v[1] || k.v[1] == k.v[2] || k.v[2] == k.v[3]; }
+};
+template <>
+struct SideTraits< 2 >
+{
+    using Key  = EdgeKey;
+    using Less = EdgeLess;
+    static constexpr int n_sides = 4, n_side_verts = 2, n_elem_verts = 4;
+    __host__ __device__ static Key ofElement(const uint32_t* c, int side)
+    {
+        return sortedKey(c[quadSideVert(side, 0)], c[quadSideVert(side, 1)]);
+    }
+    __host__ __device__ static Key  ofBoundary(const uint32_t* b) { return sortedKey(b[0], b[1]); }
+    __host__ __device__ static bool repeats(const Key& k) { return k.a == k.b; }
+};
+
+// every (element, side) emits the sorted vertices of the side with the value e * n_sides + side
+template < int DIM >
+__global__ void emitSideKeys(const uint32_t* conn, int64_t n_elems, typename SideTraits< DIM >::Key* keys, uint32_t* vals)
+{
+    using T         = SideTraits< DIM >;
+    const int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t >= n_elems * T::n_sides)
+        return;
+    const int64_t e = t / T::n_sides;
+    keys[t]         = T::ofElement(conn + e * T::n_elem_verts, int(t - e * T::n_sides));
+    vals[t]         = uint32_t(t);
+}
+
+// one boundary element per thread: lower bound of its key among the n sorted side keys, then the lowest value of the run of equal
+// keys (two entries on an interface inside the mesh; the scan does not lean on the stability of the sort).  flag: 1 = no side has
+// this vertex set, 2 = the sides of two or more elements have it, 0 otherwise.  One writer per output.
+template < int DIM >
+__global__ void matchBoundary(const typename SideTraits< DIM >::Key* keys, const uint32_t* vals, int64_t n, const uint32_t* bnd_conn,
+                              int64_t n_bnd, int64_t* face_elem, uint8_t* face_side, uint8_t* flag)
+{
+    using T         = SideTraits< DIM >;
+    const int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t >= n_bnd)
+        return;
+    const typename T::Key  k = T::ofBoundary(bnd_conn + t * T::n_side_verts);
+    const typename T::Less less;
+    int64_t                lo = 0, hi = n; // first slot whose key is not less than k
+    while (lo < hi)
+    {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (less(keys[mid], k))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    uint32_t best  = 0xffffffffu;
+    int      count = 0;
+    if (!T::repeats(k))
+        for (int64_t s = lo; s < n && !less(k, keys[s]); ++s, ++count)
+            best = vals[s] < best ? vals[s] : best;
+    if (count == 0)
+    {
+        face_elem[t] = -1;
+        face_side[t] = 255;
+        flag[t]      = 1;
+    }
+    else
+    {
+        face_elem[t] = int64_t(best / uint32_t(T::n_sides));
+        face_side[t] = uint8_t(best % uint32_t(T::n_sides));
+        flag[t]      = count > 1 ? 2 : 0;
+    }
+}
+
+__global__ void numberQuadNodes(const uint32_t* conn, int64_t n_elems, int p, uint32_t n_vertices, uint32_t n_edges,
+                                const uint32_t* edge_id, uint32_t* out)
+{
+    const int     n1 = p + 1, N = n1 * n1, m = p - 1;
+    const int64_t t  = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t >= n_elems * N)
+        return;
+    const int64_t   e  = t / N;
+    const int       ln = int(t - e * N), i = ln % n1, j = ln / n1;
+    const uint32_t* c  = conn + e * 4;
+    const bool      bi = i == 0 || i == p, bj = j == 0 || j == p;
+    const uint32_t  edge_base = n_vertices, int_base = edge_base + n_edges * uint32_t(m);
+    uint32_t        id;
+    if (bi && bj)
+        id = c[(i ? 1 : 0) + 2 * (j ? 1 : 0)];
+    else if (bi || bj)
+    {
+        // the edge is the side the node lies on; parameter 1..p-1 from the side's first local vertex
+        const int      side = bj ? (j ? 1 : 0) : 2 + (i ? 1 : 0), tpar = bj ? i : j;
+        const uint32_t a = c[quadSideVert(side, 0)], b = c[quadSideVert(side, 1)];
+        const int      pos = a < b ? tpar - 1 : p - 1 - tpar;
+        id                 = edge_base + edge_id[e * 4 + side] * uint32_t(m) + uint32_t(pos);
+    }
+    else
+        id = int_base + uint32_t(e) * uint32_t(m * m) + uint32_t((i - 1) + m * (j - 1));
+    out[t] = id;
+}
+
+template < int DIM >
+int boundaryMatch(l3k_ctx* ctx, int64_t n_elems, const uint32_t* conn, int64_t n_bnd, const uint32_t* bnd_conn, int64_t* face_elem,
+                  uint8_t* face_side, int64_t* n_unmatched, int64_t* n_interior)
+{
+    using T = SideTraits< DIM >;
+    using K = typename T::Key;
+    L3K_HIP(hipSetDevice(ctx->device));
+    hipStream_t        s = ctx->stream;
+    const int64_t      n = n_elems * T::n_sides;
+    DevBuf< uint32_t > d_conn, d_bnd, vals, vals_sorted;
+    DevBuf< K >        keys, keys_sorted;
+    DevBuf< int64_t >  d_elem;
+    DevBuf< uint8_t >  d_side, d_flag;
+    DevBuf< char >     tmp;
+    if (int rc = d_bnd.upload(bnd_conn, size_t(n_bnd * T::n_side_verts), s))
+        return rc;
+    if (d_elem.alloc(size_t(n_bnd)) || d_side.alloc(size_t(n_bnd)) || d_flag.alloc(size_t(n_bnd)))
+        return -3;
+    if (n > 0)
+    {
+        if (int rc = d_conn.upload(conn, size_t(n_elems * T::n_elem_verts), s))
+            return rc;
+        if (keys.alloc(size_t(n)) || keys_sorted.alloc(size_t(n)) || vals.alloc(size_t(n)) || vals_sorted.alloc(size_t(n)))
+            return -3;
+        hipLaunchKernelGGL(emitSideKeys< DIM >, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, d_conn.ptr, n_elems, keys.ptr, vals.ptr);
+        size_t tmp_bytes = 0;
+        L3K_HIP(rocprim::merge_sort(nullptr, tmp_bytes, keys.ptr, keys_sorted.ptr, vals.ptr, vals_sorted.ptr, size_t(n),
+                                    typename T::Less{}, s));
+        if (int rc = tmp.alloc(tmp_bytes ? tmp_bytes : 1))
+            return rc;
+        L3K_HIP(rocprim::merge_sort(tmp.ptr, tmp_bytes, keys.ptr, keys_sorted.ptr, vals.ptr, vals_sorted.ptr, size_t(n),
+                                    typename T::Less{}, s));
+    }
+    hipLaunchKernelGGL(matchBoundary< DIM >, dim3(unsigned((n_bnd + 255) / 256)), dim3(256), 0, s, keys_sorted.ptr, vals_sorted.ptr, n,
+                       d_bnd.ptr, n_bnd, d_elem.ptr, d_side.ptr, d_flag.ptr);
+    L3K_HIP(hipGetLastError());
+    std::vector< uint8_t > flag(size_t(n_bnd), uint8_t{0});
+    L3K_HIP(hipMemcpyAsync(face_elem, d_elem.ptr, sizeof(int64_t) * size_t(n_bnd), hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipMemcpyAsync(face_side, d_side.ptr, size_t(n_bnd), hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipMemcpyAsync(flag.data(), d_flag.ptr, size_t(n_bnd), hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipStreamSynchronize(s));
+    for (uint8_t f : flag)
+        *n_unmatched += f == 1, *n_interior += f == 2;
+    return 0;
+}
+} // namespace
+
+extern "C" int l3k_elevate_order_quads(l3k_ctx* ctx, int64_t n_elems, const uint32_t* conn, int64_t n_vertices, int order,
+                                       uint32_t* elem_nodes, int64_t* n_nodes, int64_t* n_noninternal)
+{
+    if (!ctx || n_elems < 0 || (n_elems > 0 && (!conn || !elem_nodes)) || n_vertices < 0 || order < 1 || order > 8 || !n_nodes ||
+        !n_noninternal)
+    {
+        setError("l3k_elevate_order_quads: bad arguments");
+        return -1;
+    }
+    for (int64_t i = 0; i < n_elems * 4; ++i)
+        if (conn[i] >= uint64_t(n_vertices))
+        {
+            setError("l3k_elevate_order_quads: conn[%lld] = %u is outside [0,%lld)", (long long)i, conn[i], (long long)n_vertices);
+            return -1;
+        }
+    const int64_t N = int64_t(order + 1) * (order + 1), m = order - 1;
+    if (n_vertices + n_elems * (4 * m + m * m) >= (int64_t(1) << 32)) // worst case: no shared edge
+    {
+        setError("l3k_elevate_order_quads: the elevated mesh may exceed 2^32 nodes");
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(ctx->device));
+    hipStream_t        s = ctx->stream;
+    DevBuf< uint32_t > d_conn, ev, edge_id, d_out;
+    DevBuf< EdgeKey >  ek;
+    uint32_t           n_edges = 0;
+    if (n_elems > 0)
+    {
+        if (int rc = d_conn.upload(conn, size_t(n_elems * 4), s))
+            return rc;
+        if (ek.alloc(size_t(n_elems * 4)) || ev.alloc(size_t(n_elems * 4)) || edge_id.alloc(size_t(n_elems * 4)) ||
+            d_out.alloc(size_t(n_elems * N)))
+            return -3;
+        hipLaunchKernelGGL(emitSideKeys< 2 >, dim3(unsigned((n_elems * 4 + 255) / 256)), dim3(256), 0, s, d_conn.ptr, n_elems, ek.ptr,
+                           ev.ptr); // (a quad's edges are its sides)
+        if (int rc = uniqueIds(ek.ptr, ev.ptr, n_elems * 4, EdgeLess{}, edge_id.ptr, n_edges, s))
+            return rc;
+        hipLaunchKernelGGL(numberQuadNodes, dim3(unsigned((n_elems * N + 255) / 256)), dim3(256), 0, s, d_conn.ptr, n_elems, order,
+                           uint32_t(n_vertices), n_edges, edge_id.ptr, d_out.ptr);
+        L3K_HIP(hipGetLastError());
+        L3K_HIP(hipMemcpyAsync(elem_nodes, d_out.ptr, sizeof(uint32_t) * size_t(n_elems * N), hipMemcpyDeviceToHost, s));
+        L3K_HIP(hipStreamSynchronize(s));
+    }
+    *n_noninternal = n_vertices + int64_t(n_edges) * m;
+    *n_nodes       = *n_noninternal + n_elems * m * m;
+    return 0;
+}
+
+extern "C" int l3k_boundary_match(l3k_ctx* ctx, int dim, int64_t n_elems, const uint32_t* conn, int64_t n_bnd,
+                                  const uint32_t* bnd_conn, int64_t* face_elem, uint8_t* face_side, int64_t* n_unmatched,
+                                  int64_t* n_interior)
+{
+    if (!ctx || !n_unmatched || !n_interior)
+    {
+        setError("l3k_boundary_match: null context or counters");
+        return -1;
+    }
+    if (dim != 2 && dim != 3)
+    {
+        setError("l3k_boundary_match: dim = %d, only quads (2) and hexes (3) have sides to match", dim);
+        return -1;
+    }
+    if (n_elems < 0 || n_bnd < 0 || (n_elems > 0 && !conn) || (n_bnd > 0 && (!bnd_conn || !face_elem || !face_side)))
+    {
+        setError("l3k_boundary_match: negative counts or null arrays with non-zero counts");
+        return -1;
+    }
+    if (n_elems * 2 * dim >= (int64_t(1) << 32)) // the sort's values e * 2 dim + side are 32-bit
+    {
+        setError("l3k_boundary_match: %lld elements have 2^32 sides or more", (long long)n_elems);
+        return -1;
+    }
+    *n_unmatched = *n_interior = 0;
+    if (n_bnd == 0)
+        return 0;
+    return dim == 3 ? boundaryMatch< 3 >(ctx, n_elems, conn, n_bnd, bnd_conn, face_elem, face_side, n_unmatched, n_interior)
+                    : boundaryMatch< 2 >(ctx, n_elems, conn, n_bnd, bnd_conn, face_elem, face_side, n_unmatched, n_interior);
+}

@@ -106,3 +106,20 @@ def rcb_partition(elem_verts, n_parts):
 
     split(np.arange(c.shape[0]), 0, int(n_parts))
     return out
+
+
+def local_sides(pmesh, face_elem, face_side):
+    """The element sides of the whole mesh (element indices of the global mesh, e.g. system.ElevatedMesh.boundary_sides) that
+    belong to elements this rank holds, with the element indices mapped to local ones through pmesh.elem_global; the order of the
+    input is kept.  Every element has one rank, so the union over the ranks is the input, each side once.  Returns
+    (int64[m], uint8[m])."""
+    fe = np.asarray(face_elem, dtype=np.int64).reshape(-1)
+    fs = np.asarray(face_side, dtype=np.uint8).reshape(-1)
+    if fe.shape != fs.shape:
+        raise ValueError("face_elem and face_side must have the same length")
+    eg = np.asarray(pmesh.elem_global, dtype=np.int64)
+    order = np.argsort(eg, kind="stable")
+    at = np.searchsorted(eg[order], fe)
+    mine = at < eg.size
+    mine[mine] = eg[order][at[mine]] == fe[mine]
+    return order[at[mine]].astype(np.int64), fs[mine].copy()

@@ -4,6 +4,7 @@ Mirrors (names, argument meaning, error behaviour) for this path only:
   * tables            -- math::getLobattoRuleAbsc, quad::getReferenceQuadrature, SumFactorization tables
   * CubePartition     -- generateAndDistributeMesh for structured cubes (comm/DistributeMesh.hpp:284-299)
   * SquarePartition   -- makeSquareMesh + convertMeshToOrder on one part (quads, mesh/primitives/SquareMesh.hpp)
+  * ElevatedMesh      -- readMesh + convertMeshToOrder for unstructured quads / hexes, boundaries by physical id (getBoundary)
   * MatrixFreeSystem  -- algsys::MatrixFreeSystem: assembleProblem -> Operator.apply(X, Y, alpha, beta)
                          (algsys/MatrixFreeSystem.hpp:24-89,1020-1140)
 Vectors are torch tensors of shape (ncols, n_owned_dofs), i.e. column-major [row][col] multivectors with owned rows
@@ -383,6 +384,119 @@ class ElevatedHexMesh:
 
     n_local_nodes = CubePartition.n_local_nodes
     node_coords = CubePartition.node_coords
+
+
+def elevate_order_quads(ctx, conn, n_vertices, order):
+    """The quad twin of elevate_order (l3k_elevate_order_quads): conn [n_elems][4] vertex ids (local vertex i + 2j) ->
+    (elem_nodes [n_elems][(order+1)^2] uint32, n_nodes, n_noninternal)."""
+    lib = capi.load()
+    c = np.ascontiguousarray(conn, dtype=np.uint32).reshape(-1, 4)
+    out = np.empty((c.shape[0], (order + 1) ** 2), dtype=np.uint32)
+    nn, nni = C.c_int64(), C.c_int64()
+    capi.check(lib.l3k_elevate_order_quads(ctx._h, c.shape[0], c.ctypes.data_as(capi.c_uint32_p), int(n_vertices), int(order),
+                                           out.ctypes.data_as(capi.c_uint32_p), C.byref(nn), C.byref(nni)))
+    return out, nn.value, nni.value
+
+
+def boundary_match(ctx, conn, bnd_conn):
+    """The element and side of every boundary element (l3k_boundary_match): conn [n_elems][2^dim] and bnd_conn
+    [n_bnd][2^(dim-1)] vertex ids, dim from conn's width.  Returns (face_elem int64 [n_bnd], face_side uint8 [n_bnd], n_unmatched,
+    n_interior); an unmatched boundary element has face_elem -1 and face_side 255."""
+    conn = np.asarray(conn)
+    if conn.ndim != 2 or conn.shape[1] not in (4, 8):
+        raise L3KError("conn must be [n_elems][4] (quads) or [n_elems][8] (hexes)")
+    dim = 2 if conn.shape[1] == 4 else 3
+    c = np.ascontiguousarray(conn, dtype=np.uint32)
+    b = np.ascontiguousarray(bnd_conn, dtype=np.uint32).reshape(-1, 2 ** (dim - 1))
+    fe = np.empty(b.shape[0], dtype=np.int64)
+    fs = np.empty(b.shape[0], dtype=np.uint8)
+    nu, ni = C.c_int64(), C.c_int64()
+    capi.check(capi.load().l3k_boundary_match(ctx._h, dim, c.shape[0], c.ctypes.data_as(capi.c_uint32_p), b.shape[0],
+                                              b.ctypes.data_as(capi.c_uint32_p), fe.ctypes.data_as(capi.c_int64_p),
+                                              fs.ctypes.data_as(capi.c_uint8_p), C.byref(nu), C.byref(ni)))
+    return fe, fs, nu.value, ni.value
+
+
+def side_nodes(dim, order):
+    """[2 dim][(order+1)^(dim-1)] element-local node indices of every side of an order-p quad (i + n j) or hex (i + n (j + n k)),
+    sides numbered as for BoundaryTerm: the last axis first, low side before high side."""
+    n = order + 1
+    idx = np.arange(n ** dim).reshape((n,) * dim)  # [k][j][i] / [j][i]
+    return np.stack([np.take(idx, at, axis=axis).reshape(-1) for axis in range(dim) for at in (0, order)])
+
+
+class ElevatedMesh:
+    """A single-rank order-p quad or hex mesh made from an unstructured order-1 one on the device, with its boundary by
+    physical id: what mesh::readMesh + convertMeshToOrder give the reference (gmsh.read_mesh supplies the arguments).  The
+    attributes of ElevatedHexMesh (DeviceMesh, MatrixFreeSystem, partition.PartitionedMesh and solve.PMultigrid take it as they take
+    that class; quads keep elem_verts [n][4][3]), plus boundary_ids (sorted unique), elem_domain, and the (element, side) of every
+    boundary element from l3k_boundary_match."""
+
+    def __init__(self, ctx, verts, conn, order, bnd_conn=None, bnd_id=None, elem_domain=None):
+        verts = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        conn = np.asarray(conn)
+        if conn.ndim != 2 or conn.shape[1] not in (4, 8):
+            raise L3KError("conn must be [n_elems][4] (quads) or [n_elems][8] (hexes)")
+        conn = np.ascontiguousarray(conn, dtype=np.uint32)
+        self.dim = 2 if conn.shape[1] == 4 else 3
+        self.order, self.rank, self.parts = order, 0, (1,) * self.dim
+        elevate = elevate_order_quads if self.dim == 2 else elevate_order
+        self.elem_nodes, n_nodes, self.n_noninternal = elevate(ctx, conn, verts.shape[0], order)
+        self.elem_verts = verts[conn.astype(np.int64)]  # [n_elems][2^dim][3]
+        self.n_elems = self.n_interior_elems = conn.shape[0]
+        self.n_owned_nodes, self.n_ghost_nodes = n_nodes, 0
+        self.global_node_base, self.n_global_nodes = 0, n_nodes
+        self.nbr_rank, self.send_nodes, self.ghost_ranges = [], [], []
+        self.elem_domain = np.zeros(conn.shape[0], np.int32) if elem_domain is None else np.asarray(elem_domain, dtype=np.int32)
+        if self.elem_domain.shape != (conn.shape[0],):
+            raise L3KError("elem_domain must hold one id per element")
+        n_side_verts = 2 ** (self.dim - 1)
+        bnd_conn = np.zeros((0, n_side_verts), np.uint32) if bnd_conn is None else np.asarray(bnd_conn).reshape(-1, n_side_verts)
+        self.bnd_id = np.zeros(0, np.int32) if bnd_id is None else np.asarray(bnd_id, dtype=np.int32).reshape(-1)
+        if self.bnd_id.size != bnd_conn.shape[0]:
+            raise L3KError("bnd_id must hold one id per boundary element")
+        self.boundary_ids = np.unique(self.bnd_id)
+        self.face_elem, self.face_side, self.n_unmatched, self.n_interior = boundary_match(ctx, conn, bnd_conn)
+
+    n_local_nodes = CubePartition.n_local_nodes
+    node_coords = CubePartition.node_coords
+
+    def _select(self, ids):
+        ids = np.atleast_1d(np.asarray(self.boundary_ids if ids is None else ids, dtype=np.int64))
+        missing = np.setdiff1d(ids, self.boundary_ids)
+        if missing.size:
+            raise L3KError(f"the mesh has no boundary with id {missing.tolist()}")  # getBoundary throws (tests/MeshTests.cpp:40)
+        sel = np.nonzero(np.isin(self.bnd_id, ids))[0]
+        lost = sel[self.face_elem[sel] < 0]
+        if lost.size:
+            raise L3KError(f"{lost.size} boundary elements (the first: number {int(lost[0])} of the file, id "
+                           f"{int(self.bnd_id[lost[0]])}) are the side of no element")
+        return sel
+
+    def boundary_sides(self, ids=None):
+        """(element index, side) of the boundary elements with the listed physical ids (default: all), in the order of the
+        file: MeshPartition::getBoundary(id).  Returns (int64[m], uint8[m]); L3KError for an id the mesh does not have and for a
+        listed boundary element that is the side of no element."""
+        sel = self._select(ids)
+        return self.face_elem[sel].copy(), self.face_side[sel].copy()
+
+    def dirichlet_mask(self, dofs_per_node, unknowns=(0,), ids=None):
+        """Byte mask over local dofs: the listed unknowns at the nodes of the sides with the listed boundary ids (default: all)
+        (BCDefinition::defineDirichlet)."""
+        fe, fs = self.boundary_sides(ids)
+        nodes = self.elem_nodes[fe[:, None], side_nodes(self.dim, self.order)[fs]].reshape(-1)
+        mask = np.zeros((self.n_local_nodes, dofs_per_node), dtype=np.uint8)
+        for u in unknowns:
+            mask[nodes, u] = 1
+        return mask.reshape(-1)
+
+    def elements_of(self, domain_ids):
+        """Indices of the elements with the listed domain (physical) ids, ascending; L3KError for an id no element has."""
+        ids = np.atleast_1d(np.asarray(domain_ids, dtype=np.int64))
+        missing = np.setdiff1d(ids, self.elem_domain)
+        if missing.size:
+            raise L3KError(f"the mesh has no domain with id {missing.tolist()}")
+        return np.nonzero(np.isin(self.elem_domain, ids))[0]
 
 
 class DeviceMesh:
