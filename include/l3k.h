@@ -889,6 +889,58 @@ int l3k_elevate_order_quads(l3k_ctx* ctx, int64_t n_elems, const uint32_t* conn,
 int l3k_boundary_match(l3k_ctx* ctx, int dim, int64_t n_elems, const uint32_t* conn, int64_t n_bnd, const uint32_t* bnd_conn,
                        int64_t* face_elem, uint8_t* face_side, int64_t* n_unmatched, int64_t* n_interior);
 
+/* ---- periodic boundary conditions (BCDefinition::definePeriodic(src_ids, dst_ids, translation), bcs/BCDefinition.hpp:92-104;
+ * bcs/PeriodicBC.hpp: getNodeLocationData, NodeMatcher, getComponents) ---------------------------------------------------------
+ * Two steps: l3k_periodic_match finds, from geometry, the destination node every source node is the image of; l3k_periodic_merge
+ * carries the identification out on the connectivity, which gives an ordinary mesh: l3k_mesh_create, the operators, the
+ * partitioner and the sparsity graph take it as any other, since all of them read the node sharing off elem_nodes.
+ *
+ * l3k_periodic_match.  All pointers are host pointers.  elem_nodes [n_elems][(order+1)^dim] and elem_verts [n_elems][2^dim][3] as in
+ * l3k_mesh_desc; (src_elem, src_side) and (dst_elem, dst_side) list element sides, numbered as for l3k_bnd_create.  The side nodes
+ * of a listed side are the (order+1)^(dim-1) local nodes of that side; the location of a node is the bi-/tri-linear map of its
+ * element's vertices at the GLL reference position (mesh/NodePhysicalLocation.hpp); with dim == 2, z and translation[2] are
+ * ignored.  A node listed through several sides is one node (its location is taken from the first side that lists it; they agree
+ * to rounding).  Source node s matches destination node d iff |x_s + translation - x_d|_2 < tolerance (strict, as in the reference,
+ * whose default is 1e-12).  Several destinations qualify: the nearest wins, ties go to the lowest node id, and the source node is
+ * counted in *n_ambiguous.  None qualifies: the source node is counted in *n_unmatched, and *first_unmatched is the lowest such
+ * node id (-1 if there is none) -- the reference's contract is that each node at X belonging to the source has a node at X +
+ * translation.  Destination nodes nobody matches are not an error.  Output: one (pair_src[i], pair_dst[i]) per matched source node,
+ * ascending in the source node; pairs with s == d are dropped; *n_pairs of them (capacity n_src * (order+1)^(dim-1)).  Every run gives
+ * the same answer.
+ * Only the vertices and the side node ids of the listed sides are uploaded.  A kernel evaluates the locations, the nodes are made
+ * unique by a device sort on the node id, the destination nodes are binned on a uniform grid whose cell edge is at least 2 tolerance
+ * and sorted by cell, and every source node looks into its own and the adjacent 3^dim - 1 cells by binary search.  Memory grows with
+ * the number of listed side nodes and nothing is quadratic as long as the tolerance is below the node spacing; a tolerance above the
+ * node spacing is legal and merely slow.
+ * Errors (-1, l3k_last_error names the call): dim outside {2, 3}, order outside 1..8, negative counts, null arrays with non-zero
+ * counts, a listed side whose element index or side is "outside the mesh", a vertex of a listed side or a translation that is not
+ * finite, a tolerance that is not finite and positive.
+ *
+ * l3k_periodic_merge (host only, no context).  pair_a / pair_b: n_pairs node pairs, e.g. concatenated from several
+ * l3k_periodic_match calls -- all computed on the UNMERGED numbering (periodic in x and in y on a square: the four corner nodes
+ * form one component); a == b and duplicate pairs are accepted.  n_noninternal: the first n_noninternal node ids are the nodes that
+ * lie on element boundaries (as l3k_elevate_order returns it).  The connected components of the pair graph are formed, the
+ * representative of a component is its lowest node id, node_map[old] (out, [n_nodes]) is the rank of old's representative among the
+ * kept nodes in ascending old id, and the n_entries entries of elem_nodes are rewritten through it: ids stay compact, and the
+ * numbering [non-internal | internal, contiguous per element] survives.  *n_nodes_out: the kept nodes; *n_noninternal_out =
+ * n_noninternal - (n_nodes - *n_nodes_out); *n_components: the components of two nodes or more.
+ * Errors (-1, nothing written): a pair id >= n_noninternal (an element-internal or out-of-range node), an elem_nodes entry >=
+ * n_nodes, null arrays with non-zero counts, n_noninternal outside [0, n_nodes].
+ *
+ * A mesh one element wide along a periodic axis is legal: an element then names a node twice.  Applies, diag and rhs on it are
+ * correct; bitwise reproducibility in deterministic mode is not claimed for that shape (the colouring separates elements that
+ * share a node, not the repeated rows inside one element).
+ * Out of scope: periodicity restricted to a subset of a node's dofs (the reference's dof_inds: dofs here are node * dofs_per_node +
+ * k with no indirection to carry it), rotational periodicity, and matching across ranks (every rank holds the whole order-p
+ * connectivity before it partitions, so none is needed).                                                                          */
+int l3k_periodic_match(l3k_ctx* ctx, int dim, int order, int64_t n_elems, const uint32_t* elem_nodes, const double* elem_verts,
+                       int64_t n_src, const int64_t* src_elem, const uint8_t* src_side, int64_t n_dst, const int64_t* dst_elem,
+                       const uint8_t* dst_side, const double translation[3], double tolerance, uint32_t* pair_src,
+                       uint32_t* pair_dst, int64_t* n_pairs, int64_t* n_unmatched, int64_t* n_ambiguous, int64_t* first_unmatched);
+int l3k_periodic_merge(int64_t n_nodes, int64_t n_noninternal, int64_t n_pairs, const uint32_t* pair_a, const uint32_t* pair_b,
+                       int64_t n_entries, uint32_t* elem_nodes, uint32_t* node_map, int64_t* n_nodes_out, int64_t* n_noninternal_out,
+                       int64_t* n_components);
+
 /* ---- native results file (host only; post/NativeIO.hpp:15-60 save, :115-146 LoadedResults, :277-295 loadResultsImpl) --
  * "L3STER results file\nv1.0\n// <comment>\n", size_t n_fields, size_t n_nodes_global, then n_fields arrays of
  * n_nodes_global doubles indexed by global node id.  Every rank saves its owned slice [node_begin, node_begin + n_local)

@@ -589,6 +589,55 @@ inline std::vector< uint32_t > elevateOrder(Context& ctx, std::span< const uint3
     return elem_nodes;
 }
 
+// BCDefinition::definePeriodic(src_ids, dst_ids, translation) (bcs/BCDefinition.hpp:92-104, bcs/PeriodicBC.hpp) in two steps, as in
+// l3k.h.  periodicMatch: the node pairs (source node, the destination node it is the image of) of the listed element sides, found
+// from geometry on the device; throws through check() on bad arguments, reports unmatched source nodes in the result.
+struct PeriodicPairs
+{
+    std::vector< uint32_t > src, dst;
+    int64_t                 n_unmatched = 0, n_ambiguous = 0, first_unmatched = -1;
+};
+inline PeriodicPairs periodicMatch(Context& ctx, int dim, int order, std::span< const uint32_t > elem_nodes,
+                                   std::span< const double > elem_verts, std::span< const int64_t > src_elem,
+                                   std::span< const uint8_t > src_side, std::span< const int64_t > dst_elem,
+                                   std::span< const uint8_t > dst_side, const std::array< double, 3 >& translation,
+                                   double tolerance = 1e-12)
+{
+    int64_t nodes_per_elem = 1, nodes_per_side = 1;
+    for (int a = 0; a < dim; ++a)
+        nodes_per_side = nodes_per_elem, nodes_per_elem *= order + 1;
+    const int64_t n_elems = nodes_per_elem ? int64_t(elem_nodes.size()) / nodes_per_elem : 0;
+    PeriodicPairs out;
+    out.src.resize(src_elem.size() * size_t(nodes_per_side));
+    out.dst.resize(out.src.size());
+    int64_t n_pairs = 0;
+    check(l3k_periodic_match(ctx.get(), dim, order, n_elems, elem_nodes.data(), elem_verts.data(), int64_t(src_elem.size()),
+                             src_elem.data(), src_side.data(), int64_t(dst_elem.size()), dst_elem.data(), dst_side.data(),
+                             translation.data(), tolerance, out.src.data(), out.dst.data(), &n_pairs, &out.n_unmatched,
+                             &out.n_ambiguous, &out.first_unmatched));
+    out.src.resize(size_t(n_pairs));
+    out.dst.resize(size_t(n_pairs));
+    return out;
+}
+// periodicMerge: the pairs (of one or several periodicMatch calls on the unmerged mesh) carried out on elem_nodes in place; returns
+// node_map (old -> new); n_nodes and n_noninternal are updated.
+inline std::vector< uint32_t > periodicMerge(std::span< uint32_t > elem_nodes, int64_t& n_nodes, int64_t& n_noninternal,
+                                             std::span< const uint32_t > pair_a, std::span< const uint32_t > pair_b,
+                                             int64_t* n_components = nullptr)
+{
+    if (pair_a.size() != pair_b.size())
+        throw std::runtime_error{"periodicMerge: pair_a and pair_b must have the same length"};
+    std::vector< uint32_t > node_map(size_t(n_nodes > 0 ? n_nodes : 0));
+    int64_t                 nn = 0, nni = 0, nc = 0;
+    check(l3k_periodic_merge(n_nodes, n_noninternal, int64_t(pair_a.size()), pair_a.data(), pair_b.data(), int64_t(elem_nodes.size()),
+                             elem_nodes.data(), node_map.data(), &nn, &nni, &nc));
+    n_nodes       = nn;
+    n_noninternal = nni;
+    if (n_components)
+        *n_components = nc;
+    return node_map;
+}
+
 // save(comm, mesh, solution_manager, path, inds, comment) / Loader::loadResults of post/NativeIO.hpp for this rank's owned
 // nodes [node_begin, node_begin + n_local): fields = [n_fields][ld] host values
 inline void saveResults(const char* path, const char* comment, size_t n_fields, int64_t n_global_nodes, int64_t node_begin,

@@ -264,6 +264,11 @@ SIGNATURES = {
     "l3k_elevate_order_quads": (C.c_int, [_vp, C.c_int64, c_uint32_p, C.c_int64, C.c_int, c_uint32_p, c_int64_p, c_int64_p]),
     "l3k_boundary_match": (C.c_int, [_vp, C.c_int, C.c_int64, c_uint32_p, C.c_int64, c_uint32_p, c_int64_p, c_uint8_p, c_int64_p,
                                      c_int64_p]),
+    "l3k_periodic_match": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int64, c_uint32_p, c_double_p, C.c_int64, c_int64_p, c_uint8_p,
+                                     C.c_int64, c_int64_p, c_uint8_p, c_double_p, C.c_double, c_uint32_p, c_uint32_p, c_int64_p,
+                                     c_int64_p, c_int64_p, c_int64_p]),
+    "l3k_periodic_merge": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, c_uint32_p, c_uint32_p, C.c_int64, c_uint32_p, c_uint32_p,
+                                     c_int64_p, c_int64_p, c_int64_p]),
     "l3k_results_save": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, c_double_p, C.c_size_t,
                                    C.c_int]),
     "l3k_results_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

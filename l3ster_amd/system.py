@@ -425,6 +425,49 @@ def side_nodes(dim, order):
     return np.stack([np.take(idx, at, axis=axis).reshape(-1) for axis in range(dim) for at in (0, order)])
 
 
+def periodic_match(ctx, mesh, src, dst, translation, tolerance=1e-12):
+    """The destination node every source node is the image of (l3k_periodic_match; bcs/PeriodicBC.hpp): mesh supplies dim, order,
+    elem_nodes and elem_verts; src and dst are (face_elem, face_side) lists of element sides; source node s matches destination
+    node d iff |x_s + translation - x_d| < tolerance, the nearest wins, ties to the lowest id.  Returns (pair_src uint32 [n],
+    pair_dst uint32 [n], n_unmatched, n_ambiguous, first_unmatched), pairs ascending in the source node."""
+    en = np.ascontiguousarray(mesh.elem_nodes, dtype=np.uint32)
+    ev = np.ascontiguousarray(mesh.elem_verts, dtype=np.float64)
+    se, ss = _sides(*src)
+    de, ds = _sides(*dst)
+    t = np.zeros(3)
+    tr = np.asarray(translation, dtype=np.float64).reshape(-1)
+    if tr.size not in (mesh.dim, 3):
+        raise L3KError("the translation has one entry per dimension")
+    t[:tr.size] = tr
+    cap = se.size * (mesh.order + 1) ** (mesh.dim - 1)
+    ps, pd = np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.uint32)
+    n_pairs, n_unmatched, n_ambiguous, first = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    check(capi.load().l3k_periodic_match(
+        ctx._h, mesh.dim, mesh.order, en.shape[0], en.ctypes.data_as(capi.c_uint32_p), ev.ctypes.data_as(capi.c_double_p),
+        se.size, se.ctypes.data_as(capi.c_int64_p), ss.ctypes.data_as(capi.c_uint8_p), de.size, de.ctypes.data_as(capi.c_int64_p),
+        ds.ctypes.data_as(capi.c_uint8_p), t.ctypes.data_as(capi.c_double_p), float(tolerance), ps.ctypes.data_as(capi.c_uint32_p),
+        pd.ctypes.data_as(capi.c_uint32_p), C.byref(n_pairs), C.byref(n_unmatched), C.byref(n_ambiguous), C.byref(first)))
+    return ps[:n_pairs.value].copy(), pd[:n_pairs.value].copy(), n_unmatched.value, n_ambiguous.value, first.value
+
+
+def periodic_merge(elem_nodes, n_nodes, n_noninternal, pair_a, pair_b):
+    """The node pairs carried out on a connectivity (l3k_periodic_merge, host only): every connected component of the pair graph
+    becomes its lowest node, ids stay compact and the [non-internal | internal] numbering survives.  The pairs may come from several
+    periodic_match calls on the UNMERGED mesh.  Returns (new elem_nodes uint32, node_map uint32 [n_nodes] old -> new, n_nodes,
+    n_noninternal, n_components); elem_nodes itself is not touched."""
+    en = np.array(elem_nodes, dtype=np.uint32, order="C")
+    a = np.ascontiguousarray(pair_a, dtype=np.uint32).reshape(-1)
+    b = np.ascontiguousarray(pair_b, dtype=np.uint32).reshape(-1)
+    if a.size != b.size:
+        raise L3KError("pair_a and pair_b must have the same length")
+    node_map = np.empty(int(n_nodes), dtype=np.uint32)
+    nn, nni, nc = C.c_int64(), C.c_int64(), C.c_int64()
+    check(capi.load().l3k_periodic_merge(int(n_nodes), int(n_noninternal), a.size, a.ctypes.data_as(capi.c_uint32_p),
+                                         b.ctypes.data_as(capi.c_uint32_p), en.size, en.ctypes.data_as(capi.c_uint32_p),
+                                         node_map.ctypes.data_as(capi.c_uint32_p), C.byref(nn), C.byref(nni), C.byref(nc)))
+    return en, node_map, nn.value, nni.value, nc.value
+
+
 class ElevatedMesh:
     """A single-rank order-p quad or hex mesh made from an unstructured order-1 one on the device, with its boundary by
     physical id: what mesh::readMesh + convertMeshToOrder give the reference (gmsh.read_mesh supplies the arguments).  The
@@ -439,7 +482,7 @@ class ElevatedMesh:
             raise L3KError("conn must be [n_elems][4] (quads) or [n_elems][8] (hexes)")
         conn = np.ascontiguousarray(conn, dtype=np.uint32)
         self.dim = 2 if conn.shape[1] == 4 else 3
-        self.order, self.rank, self.parts = order, 0, (1,) * self.dim
+        self.ctx, self.order, self.rank, self.parts = ctx, order, 0, (1,) * self.dim
         elevate = elevate_order_quads if self.dim == 2 else elevate_order
         self.elem_nodes, n_nodes, self.n_noninternal = elevate(ctx, conn, verts.shape[0], order)
         self.elem_verts = verts[conn.astype(np.int64)]  # [n_elems][2^dim][3]
@@ -489,6 +532,36 @@ class ElevatedMesh:
         for u in unknowns:
             mask[nodes, u] = 1
         return mask.reshape(-1)
+
+    def periodic(self, definitions, tolerance=1e-12):
+        """BCDefinition::definePeriodic (bcs/BCDefinition.hpp:92-104) for every (src_ids, dst_ids, translation) of `definitions`, by
+        boundary id: a new mesh in which every node of the source boundaries is the node of the destination boundaries it is the
+        image of.  All definitions are matched on this (unmerged) mesh and merged at once, so the corners of a mesh periodic along
+        several axes become one node.  Raises L3KError naming the definition and the lowest unmatched node when a source node has
+        no partner ("each node at X belonging to source must have a corresponding node at X + translation").
+        The new mesh is taken by everything that takes this one (DeviceMesh, MatrixFreeSystem, BoundaryTerm,
+        partition.PartitionedMesh, solve.PMultigrid, SparsityGraph); it has the same elem_verts, face_elem / face_side, bnd_id,
+        boundary_ids and elem_domain, new elem_nodes, n_owned_nodes, n_global_nodes and n_noninternal, and carries node_map (old
+        -> new), n_pairs and n_ambiguous.  dirichlet_mask and boundary_sides work on it as here.  node_coords() of an identified
+        node returns the location of one of its images."""
+        import copy
+        pa, pb, n_ambiguous = [], [], 0
+        for k, (src_ids, dst_ids, translation) in enumerate(definitions):
+            s, d, n_unmatched, amb, first = periodic_match(self.ctx, self, self.boundary_sides(src_ids), self.boundary_sides(dst_ids),
+                                                           translation, tolerance)
+            if n_unmatched:
+                raise L3KError(f"periodic definition {k} ({list(np.atleast_1d(src_ids))} -> {list(np.atleast_1d(dst_ids))}): "
+                               f"{n_unmatched} source nodes have no node at X + translation, the first: node {first}")
+            pa.append(s), pb.append(d)
+            n_ambiguous += amb
+        pa = np.concatenate(pa) if pa else np.zeros(0, np.uint32)
+        pb = np.concatenate(pb) if pb else np.zeros(0, np.uint32)
+        new = copy.copy(self)
+        new.elem_nodes, new.node_map, n_nodes, new.n_noninternal, new.n_components = periodic_merge(
+            self.elem_nodes, self.n_owned_nodes, self.n_noninternal, pa, pb)
+        new.n_owned_nodes = new.n_global_nodes = n_nodes
+        new.n_pairs, new.n_ambiguous = int(pa.size), n_ambiguous
+        return new
 
     def elements_of(self, domain_ids):
         """Indices of the elements with the listed domain (physical) ids, ascending; L3KError for an id no element has."""
