@@ -727,6 +727,69 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
                         double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes,
                         int64_t* n_missing);
 
+/* ---- the assembled system as one object: hexes and quads ---------------------------------------------------------------------
+ * algsys::AssembledSystem of the reference (algsys/AssembledSystem.hpp: beginAssembly / assembleProblem / endAssembly, then the
+ * solver on the matrix), for one rank.  The calls above it in this header stay what they are (hexes; quads refused); this route
+ * has entry points of its own and takes both element types.
+ *
+ * l3k_asm_element_systems: assembleLocalSystem for the elements [first, first + count) of a domain term
+ *   (algsys/AssembleLocalSystem.hpp:234-256): d_K [count][Nd][Nd] row-major, bitwise symmetric (the mirrored lower triangle, as
+ *   the selfadjointView copy, :176-182), d_F [count][n_rhs][Nd], Nd = (p+1)^dim U; either may be NULL.  Hexes: what
+ *   l3k_local_assemble returns, through the same launchers.  Quads: device/quad_assemble.hpp -- every entry written, no atomics
+ *   (the same bits on every run), no mask and no lifting.  A quadrature point with |J| <= 0: -2, "Encountered degenerate
+ *   element" (:249).
+ * l3k_asm_side_systems: assembleLocalSystem on a BoundaryElementView (algsys/AssembleLocalSystem.hpp:77-216) for the sides
+ *   [first, first + count) of a boundary term, in the order of its list: the local system of the whole element from the side
+ *   quadrature, layouts as above.  Hexes: what l3k_bnd_local_assemble returns.  Quads: the side kernel of quad_assemble.hpp.
+ *
+ * l3k_asm_create: the system over the local dofs of `mesh` (n = n_nodes * dofs_per_node): builds the full sparsity graph of
+ *   field_inds with l3k_graph_create's machinery and rules (strictly ascending indices inside [0, dofs_per_node); NULL with
+ *   n_fields = 0: all dofs; the union of the terms' dofs) and owns row_ptr, col_ind, values and rhs [n_rhs][ldr].  workspace_bytes
+ *   (two halves, 0 = 1 GiB, as l3k_assemble_global) sizes the sub-batches: on quads the workspace is the object's own, allocated on
+ *   first use; on hexes it is that of each term, as with l3k_assemble_global / l3k_bnd_assemble_global.  Single rank: a mesh
+ *   with ghost nodes is refused (-1, "partitioned"); the CSR operator is single-rank.  The mesh must outlive the object.
+ * l3k_asm_begin: beginAssembly (AssembledSystem.hpp: setAllToScalar(0) on matrix and rhs): values and rhs <- 0, the system is
+ *   open.  Allowed in any state (the reference calls it again after a solve); the operator is not handed out while the system is open.
+ * l3k_asm_add_domain / l3k_asm_add_boundary: assembleProblem(kernel, domain ids / boundary ids): assembleGlobalSystem
+ *   (algsys/AssembleGlobalSystem.hpp:20-53 / :55-96) for the elements / sides [first, first + count) of the term, summed into
+ *   the object's arrays sub-batch by sub-batch; the local systems never leave the device.  The plain sum of the reference's
+ *   assembled path (skip_dirichlet = 0 of l3k_assembled_scatter).  Hexes go through the pipelines behind l3k_assemble_global
+ *   and l3k_bnd_assemble_global, quads through the kernels of quad_assemble.hpp in front of the same scatter kernel.  Refused
+ *   with -1 and a message naming the offence: a system that is not open, a term of another dimension, a term on another mesh,
+ *   field_inds that are not a subset of the system's, another n_rhs, a shape without an assembly launcher, a range outside the
+ *   term, a domain term with l3k_mf_assemble_boundary on (add its boundary terms here instead).  Entries outside the graph
+ *   cannot happen by construction; they are counted all the same (l3k_asm_info::n_missing).  -2: a degenerate element.  The
+ *   calls return when the work is complete.
+ * l3k_asm_end: endAssembly, then DirichletBCAlgebraic::apply (bcs/DirichletBC.hpp:82-150) through l3k_csr_dirichlet with the
+ *   mesh's own Dirichlet mask and the prescribed values d_dirichlet_vals [n_rhs][ldg] (NULL: homogeneous); a mesh without a
+ *   mask skips that step.  Creates the l3k_csr over the object's arrays (nothing copied); the system is closed.  -1, still
+ *   open: a system that is not open, ldg < n, whatever l3k_csr_create or l3k_csr_dirichlet refuse.
+ * l3k_asm_info_get: sizes, state, n_missing, the device pointers of the four arrays (valid as long as the object) and, on a
+ *   closed system, the operator: solving is l3k_csr_diag / l3k_csr_pcg_solve* / l3k_csr_cheb_create on that handle, which the
+ *   object owns (do not destroy it).
+ * Static condensation is not part of this object (hexes: l3k_condense_*; quads: not there yet), nor is partitioned assembly. */
+typedef struct l3k_asm l3k_asm;
+enum { L3K_ASM_NEW = 0, L3K_ASM_OPEN = 1, L3K_ASM_CLOSED = 2 };
+typedef struct
+{
+    int64_t        n, nnz, n_missing;
+    size_t         ldr;
+    int            n_rhs, state;
+    const int64_t* d_row_ptr;
+    const int32_t* d_col_ind;
+    double *       d_values, *d_rhs;
+    l3k_csr*       csr; /* NULL unless state == L3K_ASM_CLOSED */
+} l3k_asm_info;
+int l3k_asm_element_systems(l3k_mf* term, int64_t first, int64_t count, double* d_K, double* d_F);
+int l3k_asm_side_systems(l3k_bnd* term, int64_t first, int64_t count, double* d_K, double* d_F);
+int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out);
+int l3k_asm_begin(l3k_asm* A);
+int l3k_asm_add_domain(l3k_asm* A, l3k_mf* term, int64_t first, int64_t count);
+int l3k_asm_add_boundary(l3k_asm* A, l3k_bnd* term, int64_t first, int64_t count);
+int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg);
+int l3k_asm_info_get(const l3k_asm* A, l3k_asm_info* out);
+int l3k_asm_destroy(l3k_asm* A);
+
 /* ---- static condensation of the element-internal dofs (hexes) -----------------------------------------------------------
  * The reference's CondensationPolicy::ElementBoundary (algsys/StaticCondensationManager.hpp).  Per element, with the primary
  * dofs b (nodes on the element boundary) and the internal dofs i (nodes with 1 <= ix, iy, iz <= p-1), both in ascending

@@ -12,6 +12,8 @@
 //       .scatterLocalSystems(...)   ~ scatterLocalSystem / assembleGlobalSystem             algsys/ScatterLocalSystem.hpp:24-54
 //   l3k::Halo                    ~ comm::ImportExportContext + comm::Import / comm::Export  comm/ImportExport.hpp:29-72,130-215
 //   l3k::Transfer                ~ (no counterpart: the p-multigrid transfer of a partitioned mesh, next to l3k_pmg_*)
+//   l3k::SquareMesh              ~ makeSquareMesh(...) at an order, one rank              mesh/primitives/SquareMesh.hpp
+//   l3k::AssembledSystem         ~ algsys::AssembledSystem: beginAssembly / assembleProblem / endAssembly, hexes and quads
 //   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
 //   l3k::computeIntegral / computeNormL2 ~ post/Integral.hpp:113-128, post/NormL2.hpp:31-62 (one rank)
@@ -125,10 +127,56 @@ private:
     l3k_hostmesh_view m_view{};
 };
 
+// The single-rank structured quad mesh of [0,1]^2 (l3k_square_mesh_create): the same view with dim = 2, elem_verts [n_elems][4][3]
+// and the quad side order 0 y=0, 1 y=1, 2 x=0, 3 x=1 (mesh/ElementTraits.hpp:84-95)
+class SquareMesh
+{
+public:
+    using Sides = CubeMesh::Sides;
+    SquareMesh(std::array< int, 2 > ne, int order, double perturb = 0.)
+    {
+        check(l3k_square_mesh_create(ne.data(), order, perturb, &m_mesh));
+        check(l3k_hostmesh_view_get(m_mesh, &m_view));
+    }
+    SquareMesh(const SquareMesh&)            = delete;
+    SquareMesh& operator=(const SquareMesh&) = delete;
+    ~SquareMesh() { l3k_hostmesh_destroy(m_mesh); }
+    const l3k_hostmesh_view& view() const { return m_view; }
+    int64_t                  nLocalNodes() const { return m_view.n_owned_nodes + m_view.n_ghost_nodes; }
+    Sides                    boundarySides(unsigned sides = 0xf) const
+    {
+        Sides out;
+        for (int s = 0; s < 4; ++s)
+            if (sides & (1u << s))
+                for (int64_t e = 0; e < m_view.n_elems; ++e)
+                    if (m_view.elem_boundary[e] & (1u << s))
+                    {
+                        out.elems.push_back(e);
+                        out.sides.push_back(static_cast< uint8_t >(s));
+                    }
+        return out;
+    }
+    std::vector< uint8_t > dirichletMask(int dofs_per_node, std::span< const int > unknowns, unsigned sides = 0xf) const
+    {
+        std::vector< uint8_t > mask(static_cast< size_t >(nLocalNodes()) * dofs_per_node, 0);
+        for (int64_t n = 0; n < nLocalNodes(); ++n)
+            if (m_view.node_boundary[n] & sides)
+                for (int u : unknowns)
+                    mask[n * dofs_per_node + u] = 1;
+        return mask;
+    }
+
+private:
+    l3k_hostmesh*     m_mesh{};
+    l3k_hostmesh_view m_view{};
+};
+
 class DeviceMesh
 {
 public:
-    DeviceMesh(Context& ctx, const CubeMesh& mesh, int dofs_per_node, const uint8_t* dirichlet = nullptr) : m_dpn{dofs_per_node}
+    // Mesh: CubeMesh or SquareMesh (anything with the l3k_hostmesh_view of its arrays)
+    template < typename Mesh >
+    DeviceMesh(Context& ctx, const Mesh& mesh, int dofs_per_node, const uint8_t* dirichlet = nullptr) : m_dpn{dofs_per_node}
     {
         const auto&         v = mesh.view();
         const l3k_mesh_desc d{v.dim, v.order, v.n_elems, v.n_interior_elems, v.elem_nodes, v.elem_verts, v.n_owned_nodes,
@@ -574,6 +622,72 @@ public:
 
 private:
     l3k_graph* m_graph{};
+};
+
+// algsys::AssembledSystem for one rank, on hexes and on quads (l3k_asm_*): the object owns the CSR arrays of the full sparsity graph
+// of field_inds (empty: all dofs of the node) and the right-hand sides; workspace_bytes sizes the sub-batches.  RAII, move-only.
+//   beginAssembly          ~ AssembledSystem::beginAssembly: values and rhs <- 0, the system is open (any state)
+//   assembleProblem(term)  ~ assembleProblem(domain kernel, domain ids) / (boundary kernel, boundary ids): the element / side
+//                            systems of the term's elements / sides [first, first + count) summed into values and rhs
+//   endAssembly            ~ endAssembly + DirichletBCAlgebraic::apply with the mesh's mask; d_dirichlet_vals [n_rhs][ldg] or nullptr
+//   solve                  ~ alg_sys.solve(CG{opts, NativeJacobiOpts{}}): Jacobi PCG on the closed system's CSR operator, column 0
+//   info                   ~ n, nnz, n_missing, ldr, n_rhs, state, the device arrays and (closed) the l3k_csr handle for l3k_csr_*
+class AssembledSystem
+{
+public:
+    AssembledSystem(const DeviceMesh& mesh, std::span< const int > field_inds = {}, int n_rhs = 1, size_t workspace_bytes = 0)
+    {
+        check(l3k_asm_create(mesh.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), n_rhs, workspace_bytes,
+                             &m_asm));
+    }
+    AssembledSystem(const AssembledSystem&)            = delete;
+    AssembledSystem& operator=(const AssembledSystem&) = delete;
+    AssembledSystem(AssembledSystem&& o) noexcept : m_asm{o.m_asm} { o.m_asm = nullptr; }
+    AssembledSystem& operator=(AssembledSystem&& o) noexcept
+    {
+        if (this != &o)
+        {
+            l3k_asm_destroy(m_asm);
+            m_asm   = o.m_asm;
+            o.m_asm = nullptr;
+        }
+        return *this;
+    }
+    ~AssembledSystem() { l3k_asm_destroy(m_asm); }
+    void beginAssembly() { check(l3k_asm_begin(m_asm)); }
+    void assembleProblem(const MatrixFreeSystem& term, int64_t first, int64_t count)
+    {
+        check(l3k_asm_add_domain(m_asm, term.get(), first, count));
+    }
+    void assembleProblem(const BoundaryTerm& term, int64_t first, int64_t count)
+    {
+        check(l3k_asm_add_boundary(m_asm, term.get(), first, count));
+    }
+    void endAssembly(const double* d_dirichlet_vals = nullptr, size_t ldg = 0) { check(l3k_asm_end(m_asm, d_dirichlet_vals, ldg)); }
+    l3k_asm_info info() const
+    {
+        l3k_asm_info i{};
+        check(l3k_asm_info_get(m_asm, &i));
+        return i;
+    }
+    // d_x holds the initial guess and the result, d_minv [n] receives the Jacobi preconditioner of the matrix; throws if the
+    // system is not closed or the solver does not converge
+    l3k_cg_result solve(double* d_x, double* d_minv, l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        const l3k_asm_info i = info();
+        if (!i.csr)
+            throw std::runtime_error{"AssembledSystem::solve: the system is not closed (endAssembly)"};
+        check(l3k_csr_diag(i.csr, nullptr, 1., 0., d_minv));
+        l3k_cg_result res{};
+        check(l3k_csr_pcg_solve(i.csr, i.d_rhs, d_x, d_minv, &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    l3k_asm* get() const { return m_asm; }
+
+private:
+    l3k_asm* m_asm{};
 };
 
 // convertMeshToOrder< order >(mesh_o1) for one rank's hexahedra (mesh/ConvertMeshToOrder.hpp:51-104), on the device:

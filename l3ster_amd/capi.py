@@ -73,6 +73,13 @@ class GraphInfo(C.Structure):
                 ("lds_key_capacity", C.c_int)]
 
 
+class AsmInfo(C.Structure):
+    """l3k_asm_info: sizes, state, entries outside the graph, the device pointers of the four arrays and the operator"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_missing", C.c_int64), ("ldr", C.c_size_t), ("n_rhs", C.c_int),
+                ("state", C.c_int), ("d_row_ptr", C.c_void_p), ("d_col_ind", C.c_void_p), ("d_values", C.c_void_p),
+                ("d_rhs", C.c_void_p), ("csr", C.c_void_p)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -256,6 +263,15 @@ SIGNATURES = {
     "l3k_graph_info_get": (C.c_int, [_vp, C.POINTER(GraphInfo)]),
     "l3k_graph_fill": (C.c_int, [_vp, _vp, _vp]),
     "l3k_graph_destroy": (C.c_int, [_vp]),
+    "l3k_asm_element_systems": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "l3k_asm_side_systems": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "l3k_asm_create": (C.c_int, [_vp, C.c_int, c_int_p, C.c_int, C.c_size_t, C.POINTER(_vp)]),
+    "l3k_asm_begin": (C.c_int, [_vp]),
+    "l3k_asm_add_domain": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64]),
+    "l3k_asm_add_boundary": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64]),
+    "l3k_asm_end": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "l3k_asm_info_get": (C.c_int, [_vp, C.POINTER(AsmInfo)]),
+    "l3k_asm_destroy": (C.c_int, [_vp]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

@@ -306,6 +306,7 @@ int fillArgs(l3k_mf* mf, int which, int ncols, l3k::dev::ElemArgs& a, double* en
         return rc;
     return checkColumns(ncols, mf->n_rhs);
 }
+} // namespace
 // ... of a LocalAssembly launch: all columns of the elements [first, first + count), written from position 0 of the output
 int assemblyArgs(l3k_mf* mf, int64_t first, int64_t count, l3k::dev::ElemArgs& a)
 {
@@ -316,7 +317,6 @@ int assemblyArgs(l3k_mf* mf, int64_t first, int64_t count, l3k::dev::ElemArgs& a
     a.elem_begin_out = 0;
     return 0;
 }
-} // namespace
 const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols)
 {
     const auto* inst = l3k::dev::findInstance(mf->kernel_id, mf->mesh->order, mf->nq, ncols);
@@ -358,6 +358,7 @@ const l3k::dev::Instance* planColumns(const l3k_mf* mf, int ncols, ColumnPlan& p
                                                                                                             : ColumnPlan::per_column;
     return inst;
 }
+} // namespace
 // LocalAssembly: mf->ws grown to the coefficient workspace of `count` elements; flag = its trailing double, which the assembly
 // kernels set on a degenerate element, cleared on the context's stream
 int assemblyWorkspace(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t count, double*& flag)
@@ -377,8 +378,7 @@ int assemblyWorkspace(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t count,
 }
 // ... and the flag (or the two of a pipeline's halves) read back on s, which is synchronised: -2 if one is set.  The miss counter of
 // l3k_assemble_global rides on the same synchronisation
-int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_flag1 = nullptr, const unsigned long long* d_count = nullptr,
-                        int64_t* n_missing = nullptr)
+int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_flag1, const unsigned long long* d_count, int64_t* n_missing)
 {
     double             flags[2] = {0., 0.};
     unsigned long long h        = 0;
@@ -397,6 +397,8 @@ int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_fl
     }
     return 0;
 }
+namespace
+{
 // F_e = sum_q w detJ B_q^T f_q into d_F: the sum-factorised RHS-mode kernel without Dirichlet lifting, element-local output
 void elementLocalRhs(l3k::dev::ElemArgs& a, double* d_F)
 {

@@ -1,0 +1,466 @@
+// api_asm.hip -- the assembled system as one object (include/l3k.h: l3k_asm_*), on hexes and on quads.
+//
+// Reference: algsys::AssembledSystem (algsys/AssembledSystem.hpp): beginAssembly / assembleProblem(domain kernel | boundary kernel) /
+// endAssembly, then the solver on the matrix.  The object owns the CSR arrays of the full graph of its mesh and the right-hand sides.
+// Hexes go through the existing entry points (l3k_local_assemble, l3k_bnd_local_assemble, l3k_assemble_global,
+// l3k_bnd_assemble_global: the same launchers, and the sub-batch pipelines of the TERMS, sized by the object's workspace_bytes); quads
+// through the element and side kernels of device/quad_assemble.hpp in front of the row-major scatter kernel of api_assembled.hip, on
+// the object's own sub-batch pipeline (sumQuadSystems below; runSubBatches, objects.hpp).
+#include "objects.hpp"
+
+#include <algorithm>
+
+struct l3k_asm
+{
+    l3k_ctx*           ctx  = nullptr;
+    l3k_mesh*          mesh = nullptr;
+    std::vector< int > field_inds;
+    int                n_rhs = 1, state = L3K_ASM_NEW;
+    size_t             workspace_bytes = 0, ldr = 0;
+    int64_t            n = 0, nnz = 0, n_missing = 0;
+    DevBuf< int64_t >  row_ptr;
+    DevBuf< int32_t >  col_ind;
+    DevBuf< double >   values, rhs, zero_vals;
+    SubBatchPipe       pipe;
+    l3k_csr*           csr = nullptr;
+    ~l3k_asm()
+    {
+        if (csr)
+            (void)l3k_csr_destroy(csr);
+    }
+};
+
+namespace
+{
+int nodesPerElem(const l3k_mesh* m)
+{
+    const int N1 = m->order + 1;
+    return m->dim == 2 ? N1 * N1 : N1 * N1 * N1;
+}
+// the side arguments of a term over its list in the caller's order
+l3k::dev::SideAsmArgs sideArgsInOrder(const l3k_bnd* b)
+{
+    l3k::dev::SideAsmArgs a{};
+    a.elem_nodes = b->mesh->elem_nodes.ptr;
+    a.elem_verts = b->mesh->elem_verts.ptr;
+    a.tables     = b->tables.ptr;
+    a.fields     = b->fields;
+    a.ldf        = b->ldf;
+    a.time       = b->time;
+    a.face_elem  = b->in_order.elem.ptr;
+    a.face_side  = b->in_order.side.ptr;
+    a.face_rank  = b->in_order.rank.ptr;
+    return a;
+}
+const l3k::dev::Instance* quadElementInstance(const l3k_mf* mf, const char* what)
+{
+    const auto* inst = instanceFor(mf, mf->n_rhs);
+    if (inst && !inst->assemble)
+    {
+        setError("%s: this kernel shape has no assembly launcher", what);
+        return nullptr;
+    }
+    return inst;
+}
+const l3k::dev::BoundaryInstance* quadSideInstance(const l3k_bnd* b, const char* what)
+{
+    const auto* inst = boundaryInstanceFor(b, b->n_rhs, what);
+    if (inst && !inst->assemble)
+    {
+        setError("%s: this boundary kernel shape has no assembly launcher", what);
+        return nullptr;
+    }
+    return inst;
+}
+int checkSideRange(const l3k_bnd* b, int64_t first, int64_t count, const char* what)
+{
+    if (first < 0 || count < 0 || first + count > b->n_faces)
+    {
+        setError("%s: side range [%lld, %lld) outside [0, %lld)", what, (long long)first, (long long)(first + count), (long long)b->n_faces);
+        return -1;
+    }
+    return 0;
+}
+// sub-batch size of systems of `per_system` bytes in two halves of the workspace, at most `cap` (launch limits) and `count`
+int64_t subBatch(size_t workspace_bytes, size_t per_system, int64_t count, int64_t cap)
+{
+    if (workspace_bytes == 0)
+        workspace_bytes = size_t(1) << 30;
+    int64_t nb = int64_t(workspace_bytes / 2 / per_system);
+    nb         = std::min(nb, std::min(count, cap));
+    return nb < 1 ? 1 : nb;
+}
+// The quad route of both l3k_asm_add_* calls: the local systems [first, first + count) of a term -- Nd = NN U dofs each, their node
+// rows d_nodes[first + i] -- formed by form(at, n, d_K, d_F, d_flag) on the context's stream into one half of the object's pipeline
+// while the other half is summed into the object's arrays on the second stream.  Entries outside the graph are added to
+// A->n_missing; -2 if a forming kernel raised a half's degenerate-element flag
+template < typename Form >
+int sumQuadSystems(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, int64_t first, int64_t count, Form&& form)
+{
+    const l3k_mesh* m = A->mesh;
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    const int     NN = nodesPerElem(m), U = t.kp.n_unknowns, Nd = NN * U, R = t.n_rhs;
+    const size_t  kd1 = size_t(Nd) * Nd, fd1 = size_t(Nd) * R;
+    const int64_t nb  = subBatch(A->workspace_bytes, sizeof(double) * (kd1 + fd1), count, int64_t(0x7fffffff) / NN);
+    const size_t  kd = size_t(nb) * kd1, fd = size_t(nb) * fd1;
+    auto&         g  = A->pipe;
+    if (int rc = g.ensure(kd + fd + 1, true))
+        return rc;
+    hipStream_t         sa      = A->ctx->stream;
+    unsigned long long* d_count = A->ctx->missCounter();
+    L3K_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), sa));
+    double* const flag[2] = {g.buf[0] + kd + fd, g.buf[1] + kd + fd}; // the degenerate-element flag of each half
+    for (int k = 0; k < 2; ++k)
+        L3K_HIP(hipMemsetAsync(flag[k], 0, sizeof(double), sa));
+    if (int rc = runSubBatches(
+            g, sa, first, count, nb, [&](int k, int64_t at, int64_t n) { return form(at, n, g.buf[k], g.buf[k] + kd, flag[k]); },
+            [&](int k, int64_t at, int64_t n) {
+                return launchAssembledScatterRows(A->ctx, m, d_nodes, U, R, t.field_inds, at, n, g.buf[k], g.buf[k] + kd, A->row_ptr.ptr,
+                                                  A->col_ind.ptr, A->values.ptr, A->rhs.ptr, A->ldr, 0, d_count, g.second, 0);
+            }))
+        return rc;
+    int64_t   missing = 0;
+    const int rc      = readDegenerateFlags(sa, flag[0], flag[1], d_count, &missing);
+    A->n_missing += missing;
+    return rc;
+}
+// what the term of an l3k_asm_add_* call must share with the system (KernelTerm: both kinds of term)
+int checkTerm(const l3k_asm* A, const KernelTerm& t, const char* what)
+{
+    if (A->state != L3K_ASM_OPEN)
+    {
+        setError("%s: the system is not open (l3k_asm_begin opens it, l3k_asm_end closes it)", what);
+        return -1;
+    }
+    if (t.kp.dimension != A->mesh->dim)
+    {
+        setError("%s: a term of dimension %d on a system of dimension %d%s", what, t.kp.dimension, A->mesh->dim, quadsNote(A->mesh));
+        return -1;
+    }
+    if (t.mesh != A->mesh || t.ctx != A->ctx)
+    {
+        setError("%s: the term lives on another mesh than the system", what);
+        return -1;
+    }
+    for (int u = 0; u < t.kp.n_unknowns; ++u)
+        if (!std::binary_search(A->field_inds.begin(), A->field_inds.end(), t.field_inds[u]))
+        {
+            setError("%s: the term's field_inds[%d] = %d is not among the system's field_inds (not a subset)", what, u, t.field_inds[u]);
+            return -1;
+        }
+    if (t.n_rhs != A->n_rhs)
+    {
+        setError("%s: the term has n_rhs = %d, the system %d", what, t.n_rhs, A->n_rhs);
+        return -1;
+    }
+    return 0;
+}
+} // namespace
+
+extern "C" {
+int l3k_asm_element_systems(l3k_mf* term, int64_t first, int64_t count, double* d_K, double* d_F)
+{
+    if (!term)
+    {
+        setError("l3k_asm_element_systems: null argument");
+        return -1;
+    }
+    const l3k_mesh* m = term->mesh;
+    if (m->dim != 2)
+        return l3k_local_assemble(term, first, count, d_K, d_F, nullptr);
+    if (int rc = checkRange(m, first, count))
+        return rc;
+    if (count == 0 || (!d_K && !d_F))
+        return 0;
+    const auto* inst = quadElementInstance(term, "l3k_asm_element_systems");
+    if (!inst)
+        return -4;
+    l3k::dev::ElemArgs a;
+    if (int rc = assemblyArgs(term, first, count, a))
+        return rc;
+    L3K_HIP(hipSetDevice(term->ctx->device));
+    double* flag = nullptr;
+    if (int rc = assemblyWorkspace(term, inst, count, flag))
+        return rc;
+    a.K         = d_K;
+    a.F         = d_F;
+    a.workspace = flag;
+    if (int rc = inst->assemble(a, term->blobPtr(), term->ctx->stream))
+        return rc;
+    return readDegenerateFlags(term->ctx->stream, flag);
+}
+
+int l3k_asm_side_systems(l3k_bnd* term, int64_t first, int64_t count, double* d_K, double* d_F)
+{
+    if (!term)
+    {
+        setError("l3k_asm_side_systems: null argument");
+        return -1;
+    }
+    if (term->mesh->dim != 2)
+        return l3k_bnd_local_assemble(term, first, count, d_K, d_F);
+    if (int rc = checkSideRange(term, first, count, "l3k_asm_side_systems"))
+        return rc;
+    if (count == 0 || (!d_K && !d_F))
+        return 0;
+    const auto* inst = quadSideInstance(term, "l3k_asm_side_systems");
+    if (!inst)
+        return -4;
+    if (int rc = checkFieldsSet(term, "l3k_asm_side_systems"))
+        return rc;
+    if (int rc = sideListInOrder(term))
+        return rc;
+    L3K_HIP(hipSetDevice(term->ctx->device));
+    l3k::dev::SideAsmArgs a = sideArgsInOrder(term);
+    a.face_begin            = first;
+    a.face_count            = count;
+    a.K                     = d_K;
+    a.F                     = d_F;
+    return inst->assemble(a, term->blobPtr(), term->ctx->stream);
+}
+
+int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out)
+{
+    if (!mesh || !out)
+    {
+        setError("l3k_asm_create: null argument");
+        return -1;
+    }
+    if (n_fields < 0 || (n_fields > 0 && !field_inds) || (n_fields == 0 && field_inds))
+    {
+        setError("l3k_asm_create: n_fields = %d with %s field_inds; it is 1 .. dofs_per_node indices, or 0 and NULL for all dofs", n_fields,
+                 field_inds ? "non-null" : "null");
+        return -1;
+    }
+    if (n_rhs < 1)
+    {
+        setError("l3k_asm_create: n_rhs = %d; it is at least 1", n_rhs);
+        return -1;
+    }
+    if (mesh->n_ghost_nodes > 0)
+    {
+        setError("l3k_asm_create: a partitioned mesh (%lld ghost nodes): the assembled system and its CSR operator are single-rank",
+                 (long long)mesh->n_ghost_nodes);
+        return -1;
+    }
+    l3k_graph* g = nullptr;
+    if (int rc = l3k_graph_create(mesh, n_fields, field_inds, L3K_GRAPH_FULL, &g)) // (the rules of field_inds are the graph's)
+        return rc;
+    const auto     drop_graph = [&](int rc) { (void)l3k_graph_destroy(g); return rc; };
+    l3k_graph_info gi;
+    if (int rc = l3k_graph_info_get(g, &gi))
+        return drop_graph(rc);
+    auto A             = std::make_unique< l3k_asm >();
+    A->ctx             = mesh->ctx;
+    A->mesh            = mesh;
+    A->n_rhs           = n_rhs;
+    A->workspace_bytes = workspace_bytes;
+    A->n               = gi.n;
+    A->nnz             = gi.nnz;
+    A->ldr             = size_t(gi.n);
+    const int U        = n_fields ? n_fields : mesh->dofs_per_node;
+    for (int u = 0; u < U; ++u)
+        A->field_inds.push_back(field_inds ? field_inds[u] : u);
+    if (int rc = A->row_ptr.alloc(size_t(gi.n) + 1))
+        return drop_graph(rc);
+    if (int rc = A->col_ind.alloc(size_t(gi.nnz)))
+        return drop_graph(rc);
+    if (int rc = A->values.alloc(size_t(gi.nnz)))
+        return drop_graph(rc);
+    if (int rc = A->rhs.alloc(size_t(n_rhs) * A->ldr))
+        return drop_graph(rc);
+    if (int rc = l3k_graph_fill(g, A->row_ptr.ptr, A->col_ind.ptr))
+        return drop_graph(rc);
+    // values and rhs <- 0; the graph object's buffers feed the fill: synchronise before it goes
+    hipStream_t s   = A->ctx->stream;
+    hipError_t  err = gi.nnz ? hipMemsetAsync(A->values.ptr, 0, sizeof(double) * size_t(gi.nnz), s) : hipSuccess;
+    if (err == hipSuccess && gi.n)
+        err = hipMemsetAsync(A->rhs.ptr, 0, sizeof(double) * size_t(n_rhs) * A->ldr, s);
+    if (err == hipSuccess)
+        err = hipStreamSynchronize(s);
+    (void)l3k_graph_destroy(g);
+    if (err != hipSuccess)
+    {
+        setError("l3k_asm_create: zeroing the arrays failed: %s", hipGetErrorString(err));
+        return -3;
+    }
+    *out = A.release();
+    return 0;
+}
+
+int l3k_asm_begin(l3k_asm* A)
+{
+    if (!A)
+    {
+        setError("l3k_asm_begin: null argument");
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    hipStream_t s = A->ctx->stream;
+    if (A->nnz)
+        L3K_HIP(hipMemsetAsync(A->values.ptr, 0, sizeof(double) * size_t(A->nnz), s));
+    if (A->n)
+        L3K_HIP(hipMemsetAsync(A->rhs.ptr, 0, sizeof(double) * size_t(A->n_rhs) * A->ldr, s));
+    A->n_missing = 0;
+    A->state     = L3K_ASM_OPEN;
+    return 0;
+}
+
+int l3k_asm_add_domain(l3k_asm* A, l3k_mf* term, int64_t first, int64_t count)
+{
+    const char* const what = "l3k_asm_add_domain";
+    if (!A || !term)
+    {
+        setError("%s: null argument", what);
+        return -1;
+    }
+    if (int rc = checkTerm(A, *term, what))
+        return rc;
+    if (assemblesBoundary(term))
+    {
+        setError("%s: the term has l3k_mf_assemble_boundary on; add its boundary terms with l3k_asm_add_boundary instead", what);
+        return -1;
+    }
+    const l3k_mesh* m = A->mesh;
+    if (int rc = checkRange(m, first, count))
+        return rc;
+    if (count == 0)
+        return 0;
+    int64_t missing = 0;
+    if (m->dim != 2)
+    {
+        const auto* inst = instanceFor(term, term->n_rhs);
+        if (!inst)
+            return -4;
+        if (!inst->assemble)
+        {
+            setError("%s: this kernel shape has no assembly launcher", what);
+            return -1;
+        }
+        const int rc = l3k_assemble_global(term, first, count, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, A->rhs.ptr, A->ldr, 0,
+                                           A->workspace_bytes, &missing);
+        A->n_missing += missing;
+        return rc;
+    }
+    const auto* inst = quadElementInstance(term, what);
+    if (!inst)
+        return -4;
+    return sumQuadSystems(A, *term, m->elem_nodes.ptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double* d_flag) {
+        l3k::dev::ElemArgs a;
+        if (int rc = assemblyArgs(term, at, n, a))
+            return rc;
+        a.K         = d_K;
+        a.F         = d_F;
+        a.workspace = d_flag;
+        return inst->assemble(a, term->blobPtr(), A->ctx->stream);
+    });
+}
+
+int l3k_asm_add_boundary(l3k_asm* A, l3k_bnd* term, int64_t first, int64_t count)
+{
+    const char* const what = "l3k_asm_add_boundary";
+    if (!A || !term)
+    {
+        setError("%s: null argument", what);
+        return -1;
+    }
+    if (int rc = checkTerm(A, *term, what))
+        return rc;
+    if (int rc = checkSideRange(term, first, count, what))
+        return rc;
+    if (count == 0)
+        return 0;
+    const l3k_mesh* m       = A->mesh;
+    int64_t         missing = 0;
+    if (m->dim != 2)
+    {
+        const auto* inst = boundaryInstanceFor(term, term->n_rhs, what);
+        if (!inst)
+            return -4;
+        if (!inst->assemble)
+        {
+            setError("%s: this boundary kernel shape has no assembly launcher", what);
+            return -1;
+        }
+        const int rc = l3k_bnd_assemble_global(term, first, count, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, A->rhs.ptr, A->ldr, 0,
+                                               A->workspace_bytes, &missing);
+        A->n_missing += missing;
+        return rc;
+    }
+    const auto* inst = quadSideInstance(term, what);
+    if (!inst)
+        return -4;
+    if (int rc = checkFieldsSet(term, what))
+        return rc;
+    if (int rc = sideListInOrder(term))
+        return rc;
+    return sumQuadSystems(A, *term, term->in_order.nodes.ptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double*) {
+        l3k::dev::SideAsmArgs a = sideArgsInOrder(term);
+        a.face_begin            = at;
+        a.face_count            = n;
+        a.K                     = d_K;
+        a.F                     = d_F;
+        return inst->assemble(a, term->blobPtr(), A->ctx->stream);
+    });
+}
+
+int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg)
+{
+    if (!A)
+    {
+        setError("l3k_asm_end: null argument");
+        return -1;
+    }
+    if (A->state != L3K_ASM_OPEN)
+    {
+        setError("l3k_asm_end: the system is not open (l3k_asm_begin opens it)");
+        return -1;
+    }
+    if (d_dirichlet_vals && ldg < size_t(A->n))
+    {
+        setError("l3k_asm_end: leading dimension of the prescribed values (%zu) smaller than the number of dofs (%lld)", ldg, (long long)A->n);
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    if (!A->csr) // (the operator keeps the pointers of the object's arrays: created once, valid for every later assembly)
+        if (int rc = l3k_csr_create(A->ctx, A->n, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, 0, &A->csr))
+            return rc;
+    if (A->mesh->dirichlet.ptr && A->n > 0)
+    {
+        const double* g = d_dirichlet_vals;
+        if (!g)
+        {
+            if (!A->zero_vals.ptr)
+            {
+                if (int rc = A->zero_vals.alloc(size_t(A->n_rhs) * size_t(A->n)))
+                    return rc;
+                L3K_HIP(hipMemsetAsync(A->zero_vals.ptr, 0, sizeof(double) * A->zero_vals.n, A->ctx->stream));
+            }
+            g   = A->zero_vals.ptr;
+            ldg = size_t(A->n);
+        }
+        if (int rc = l3k_csr_dirichlet(A->csr, A->values.ptr, A->mesh->dirichlet.ptr, g, ldg, A->rhs.ptr, A->ldr, A->n_rhs))
+            return rc;
+    }
+    A->state = L3K_ASM_CLOSED;
+    return 0;
+}
+
+int l3k_asm_info_get(const l3k_asm* A, l3k_asm_info* out)
+{
+    if (!A || !out)
+    {
+        setError("l3k_asm_info_get: null argument");
+        return -1;
+    }
+    *out = {A->n, A->nnz, A->n_missing, A->ldr, A->n_rhs, A->state, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, A->rhs.ptr,
+            A->state == L3K_ASM_CLOSED ? A->csr : nullptr};
+    return 0;
+}
+
+int l3k_asm_destroy(l3k_asm* A)
+{
+    delete A;
+    return 0;
+}
+} // extern "C"

@@ -494,7 +494,7 @@ int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint
                                const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
                                unsigned long long* d_count, hipStream_t s, int tiled)
 {
-    const int       N1 = m->order + 1, NN = N1 * N1 * N1;
+    const int       N1 = m->order + 1, NN = m->dim == 2 ? N1 * N1 : N1 * N1 * N1; // (p+1)^dim nodes per element
     const int64_t   blocks = count * NN;
     if (blocks > int64_t(0x7fffffff))
     {

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void gatherSideNodesKernel(const uint32_t* __r
 int nodesPerElem(const l3k_mesh* m)
 {
     const int N1 = m->order + 1;
-    return N1 * N1 * N1;
+    return m->dim == 2 ? N1 * N1 : N1 * N1 * N1;
 }
 int uploadSideList(l3k_bnd* b, l3k_bnd::SideList& l, const std::vector< int64_t >& elem, const std::vector< uint8_t >& side,
                    const std::vector< uint8_t >* rank)
@@ -57,13 +57,16 @@ int uploadSideList(l3k_bnd* b, l3k_bnd::SideList& l, const std::vector< int64_t 
     l.built = true;
     return 0;
 }
+} // namespace
 // the list in the caller's order on the device
-int ensureInOrder(l3k_bnd* b)
+int sideListInOrder(l3k_bnd* b)
 {
     if (b->in_order.built)
         return 0;
     return uploadSideList(b, b->in_order, b->list_elem, b->list_side, nullptr);
 }
+namespace
+{
 // ... stably sorted by element, with the rank of each side among the sides of its element (the order of the list)
 int ensureByElem(l3k_bnd* b)
 {
@@ -329,7 +332,7 @@ int l3k_bnd_local_assemble(l3k_bnd* bnd, int64_t first, int64_t count, double* d
         return -4;
     if (int rc = checkFieldsSet(bnd, "l3k_bnd_local_assemble"))
         return rc;
-    if (int rc = ensureInOrder(bnd))
+    if (int rc = sideListInOrder(bnd))
         return rc;
     L3K_HIP(hipSetDevice(bnd->ctx->device));
     for (int64_t done = 0; done < count;)
@@ -383,7 +386,7 @@ int l3k_bnd_assemble_global(l3k_bnd* bnd, int64_t first, int64_t count, const in
         *n_missing = 0;
     if (count == 0)
         return 0;
-    if (int rc = ensureInOrder(bnd))
+    if (int rc = sideListInOrder(bnd))
         return rc;
     return sidesIntoGlobal(bnd, bnd->in_order, first, count, d_row_ptr, d_col_ind, d_values, d_rhs, ldr, skip_dirichlet, workspace_bytes,
                            n_missing, "l3k_bnd_assemble_global");

@@ -17,6 +17,7 @@
 #include "integral.hpp"
 #include "quad.hpp"
 #include "quad_boundary.hpp"
+#include "quad_assemble.hpp"
 
 namespace l3k::dev
 {
@@ -104,28 +105,29 @@ constexpr RouteFn selectRoute()
 
 namespace l3k::dev
 {
-// The registry entry of one (functor, order, nq, columns) shape: quads (dimension 2) take the kernels of quad.hpp and have no
-// LocalAssembly (assemble = nullptr) nor condensation; hexes the sum-factorised hex kernels and the condensation kernels of
-// their (order, unknowns) shape.  `if constexpr` keeps the templates of the other
+// The registry entry of one (functor, order, nq, columns) shape: quads (dimension 2) take the kernels of quad.hpp and the
+// LocalAssembly of quad_assemble.hpp (no coefficient workspace, no tiled layout, no condensation); hexes the sum-factorised hex
+// kernels and the condensation kernels of their (order, unknowns) shape.  `if constexpr` keeps the templates of the other
 // dimension uninstantiated (here and in the boundary / residual entries below).
 template < typename T, int P, int NQ, int R >
 Instance makeInstance()
 {
     if constexpr (T::params.dimension == 2)
-        return {KernelId< T >::value, P, NQ, R, &launchQuadApply< T, P, NQ, R >, &launchQuadDiagRhs< T, P, NQ, R >, nullptr, 0, nullptr,
-                false, &describeQuadApply< T, P, NQ, R >};
+        return {KernelId< T >::value, P, NQ, R, &launchQuadApply< T, P, NQ, R >, &launchQuadDiagRhs< T, P, NQ, R >,
+                selectQuadAssemble< T, P, NQ, R >(), 0, nullptr, false, &describeQuadApply< T, P, NQ, R >};
     else
         return {KernelId< T >::value, P, NQ, R, selectApply< T, P, NQ, R >(), &launchDiagRhs< T, P, NQ, R >, &launchAssemble< T, P, NQ >,
                 assembleWorkspaceDoublesPerElem< T, P, NQ >(), selectApplyCols< T, P, NQ, R >(), SfAsmCfg< P, NQ >::feasible,
                 selectRoute< T, P, NQ, R >(), selectCondense< P, T::params.n_unknowns >()};
 }
-// ... of a boundary equation kernel: the side kernel of quad_boundary.hpp on quads, of boundary.hpp on hexes, which also have
-// the side assembly of boundary_assemble.hpp
+// ... of a boundary equation kernel: the side kernel of quad_boundary.hpp and the side assembly of quad_assemble.hpp on quads, those
+// of boundary.hpp and boundary_assemble.hpp on hexes
 template < typename T, int P, int NQ, int R >
 BoundaryInstance makeBoundaryInstance()
 {
     if constexpr (T::params.dimension == 2)
-        return {KernelId< T >::value, P, NQ, R, &launchQuadSide< T, P, NQ, R, false >, &launchQuadSide< T, P, NQ, R, true >};
+        return {KernelId< T >::value, P, NQ, R, &launchQuadSide< T, P, NQ, R, false >, &launchQuadSide< T, P, NQ, R, true >,
+                selectQuadSideAssemble< T, P, NQ, R >(), 0};
     else
         return {KernelId< T >::value, P, NQ, R, &launchFace< T, P, NQ, R, false >, &launchFace< T, P, NQ, R, true >,
                 &launchSideAssemble< T, P, NQ, R >, sideAssembleWorkspaceDoubles< T, NQ, R >()};

@@ -496,6 +496,16 @@ int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint
                                int64_t first, int64_t count, const double* d_K, const double* d_F, const int64_t* d_row_ptr,
                                const int32_t* d_col_ind, double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet,
                                unsigned long long* d_count, hipStream_t s, int tiled);
+// api.hip: the arguments of a LocalAssembly launch of the elements [first, first + count): all columns, output from slot 0
+int assemblyArgs(l3k_mf* mf, int64_t first, int64_t count, l3k::dev::ElemArgs& a);
+// ... mf->ws grown to the coefficient workspace of `count` elements; flag = its trailing double, which the assembly kernels set on a
+// degenerate element, cleared on the context's stream
+int assemblyWorkspace(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t count, double*& flag);
+// ... and the flag (or the two of a pipeline's halves) and the miss counter read back on s, which is synchronised: -2 if a flag is set
+int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_flag1 = nullptr, const unsigned long long* d_count = nullptr,
+                        int64_t* n_missing = nullptr);
+// api_bnd_assemble.hip: the term's list of sides on the device in the order it was given (l3k_bnd::in_order), built on first use
+int sideListInOrder(l3k_bnd* b);
 // api_bnd_assemble.hip: with l3k_mf_assemble_boundary on and terms attached, the refusals of `what` (0, or -1 with the error set) ...
 int checkAssembleBoundary(const l3k_mf* mf, const char* what);
 inline bool assemblesBoundary(const l3k_mf* mf)

@@ -748,6 +748,19 @@ class BoundaryTerm:
         check(capi.load().l3k_bnd_local_assemble(self._h, first, count, _ptr(K), _ptr(F)))
         return K, F
 
+    def side_systems(self, first=0, count=None, want_K=True, want_F=True):
+        """assembleLocalSystem on the sides [first, first+count) of the list, in the order the term was given
+        (l3k_asm_side_systems; hexes and quads): the local system of the whole element from the side quadrature.  Returns
+        (K [count, Nd, Nd] row-major, bitwise symmetric, F [count, n_rhs, Nd]), Nd = (p+1)^dim U."""
+        import torch
+        count = self.n_faces - first if count is None else count
+        Nd = (self.mesh.part.order + 1) ** self.mesh.part.dim * self.info["n_unknowns"]
+        n = max(count, 0)
+        K = torch.empty((n, Nd, Nd), dtype=torch.float64, device="cuda") if want_K else None
+        F = torch.empty((n, self.n_rhs, Nd), dtype=torch.float64, device="cuda") if want_F else None
+        check(capi.load().l3k_asm_side_systems(self._h, first, count, _ptr(K), _ptr(F)))
+        return K, F
+
     def assemble_global(self, row_ptr, col_ind, values, rhs=None, first=0, count=None, skip_dirichlet=False, workspace_bytes=0):
         """The boundary overload of assembleGlobalSystem for the sides [first, first+count) of the list
         (l3k_bnd_assemble_global; hexes): side systems formed and summed into `values` (over the CSR graph row_ptr int64 /
@@ -1031,6 +1044,18 @@ class MatrixFreeSystem:
         check(capi.load().l3k_local_assemble(self._h, first, count, _ptr(K), _ptr(F), _ptr(cs)))
         return K, F, cs
 
+    def element_systems(self, first=0, count=None, want_K=True, want_F=True):
+        """assembleLocalSystem for the elements [first, first+count) (l3k_asm_element_systems; hexes and quads).  Returns
+        (K [count, Nd, Nd] row-major, bitwise symmetric, F [count, n_rhs, Nd]), Nd = (p+1)^dim U."""
+        import torch
+        count = self.mesh.part.n_elems - first if count is None else count
+        Nd = (self.mesh.part.order + 1) ** self.mesh.part.dim * self.info["n_unknowns"]
+        n = max(count, 0)
+        K = torch.empty((n, Nd, Nd), dtype=torch.float64, device="cuda") if want_K else None
+        F = torch.zeros((n, self.n_rhs, Nd), dtype=torch.float64, device="cuda") if want_F else None
+        check(capi.load().l3k_asm_element_systems(self._h, first, count, _ptr(K), _ptr(F)))
+        return K, F
+
     def local_assemble_into(self, K, first=0, count=None):
         """The element matrices of [first, first + count) into the caller's tensor K [count, Nd, Nd] (row-major, bitwise symmetric)."""
         count = K.shape[0] if count is None else count
@@ -1245,3 +1270,121 @@ class CsrOperator:
             raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
         check(capi.load().l3k_csr_dirichlet(self._h, _ptr(self.values), _ptr(mask), _ptr(g), ldg, _ptr(r), ldr, nc))
         return rhs
+
+
+class _AssembledOperator(CsrOperator):
+    """The CsrOperator of a closed AssembledSystem: the l3k_csr handle belongs to the system (which is kept alive here), the
+    tensors are views of the system's arrays."""
+
+    def __init__(self, system, handle):
+        self.ctx, self.row_ptr, self.col_ind, self.values = system.ctx, system.row_ptr, system.col_ind, system.values
+        self.n = self.n_owned_dofs = system.n
+        self.system = system
+        self._h = C.c_void_p(handle)
+
+    def __del__(self):  # (not the owner of the handle)
+        self._h = None
+
+
+class AssembledSystem:
+    """algsys::AssembledSystem for one rank, on hexes and on quads (l3k_asm_*): begin() / add(term) / end() are beginAssembly /
+    assembleProblem(domain or boundary kernel) / endAssembly.  The object owns the CSR arrays of the full sparsity graph of
+    field_inds (strictly ascending; None = all dofs of the node: the union of the terms' dofs), the right-hand sides
+    [n_rhs, n] and, on quads, the sub-batch workspace (workspace_bytes, 0 = 1 GiB; hexes use the terms' own pipelines with that size);
+    row_ptr, col_ind, values and rhs are torch views of them, not copies, made on access.  end() applies the mesh's Dirichlet mask with the prescribed values and returns a CsrOperator over the
+    same arrays, which solve.pcg and solve.ChebyshevPreconditioner take.  A partitioned mesh is refused."""
+
+    STATES = ("new", "open", "closed")
+
+    def __init__(self, mesh, field_inds=None, n_rhs=1, workspace_bytes=0):
+        self.mesh, self.ctx, self.n_rhs = mesh, mesh.ctx, n_rhs
+        fi = None if field_inds is None else (C.c_int * len(field_inds))(*[int(f) for f in field_inds])
+        self._h = C.c_void_p()
+        check(capi.load().l3k_asm_create(mesh._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes, C.byref(self._h)))
+        i = self._info()
+        self.n, self.nnz = i.n, i.nnz
+
+    def __del__(self):
+        if getattr(self, "_h", None) and capi is not None:
+            capi.load().l3k_asm_destroy(self._h)
+            self._h = None
+
+    def _info(self):
+        i = capi.AsmInfo()
+        check(capi.load().l3k_asm_info_get(self._h, C.byref(i)))
+        return i
+
+    # The four arrays as torch views, built afresh on every access: a view keeps the system alive (its memory is the system's), the
+    # system keeps no view -- torch pins the exporting object from C, where the cycle collector could not see a cycle back to self
+    @property
+    def row_ptr(self):
+        i = self._info()
+        return self._view(i.d_row_ptr, (i.n + 1,), "<i8")
+
+    @property
+    def col_ind(self):
+        i = self._info()
+        return self._view(i.d_col_ind, (i.nnz,), "<i4")
+
+    @property
+    def values(self):
+        i = self._info()
+        return self._view(i.d_values, (i.nnz,), "<f8")
+
+    @property
+    def rhs(self):
+        i = self._info()
+        return self._view(i.d_rhs, (i.n_rhs, i.ldr), "<f8")[:, :i.n]
+
+    def _view(self, ptr, shape, typestr):
+        """A torch tensor over device memory the object owns (no copy; the tensor keeps `self` alive)"""
+        import torch
+        dtype = {"<i8": torch.int64, "<i4": torch.int32, "<f8": torch.float64}[typestr]
+        dev = torch.device("cuda", self.ctx.device)
+        if int(np.prod(shape)) == 0:
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        class _Mem:
+            pass
+        m = _Mem()
+        m.owner = self
+        m.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": typestr, "data": (int(ptr), False),
+                                      "version": 2, "strides": None}
+        return torch.as_tensor(m, device=dev)
+
+    @property
+    def info(self):
+        """n, nnz, n_missing (entries outside the graph: 0 by construction), ldr, n_rhs and state ("new", "open", "closed")"""
+        import types
+        i = self._info()
+        return types.SimpleNamespace(n=i.n, nnz=i.nnz, n_missing=i.n_missing, ldr=i.ldr, n_rhs=i.n_rhs, state=self.STATES[i.state])
+
+    def begin(self):
+        """beginAssembly: values and rhs <- 0, the system is open (allowed in any state)"""
+        check(capi.load().l3k_asm_begin(self._h))
+        return self
+
+    def add(self, term, first=0, count=None):
+        """assembleProblem: the element systems of a MatrixFreeSystem's elements, or the side systems of a BoundaryTerm's sides,
+        [first, first + count) summed into values and rhs"""
+        if isinstance(term, BoundaryTerm):
+            count = term.n_faces - first if count is None else count
+            check(capi.load().l3k_asm_add_boundary(self._h, term._h, first, count))
+        elif isinstance(term, MatrixFreeSystem):
+            count = term.mesh.part.n_elems - first if count is None else count
+            check(capi.load().l3k_asm_add_domain(self._h, term._h, first, count))
+        else:
+            raise L3KError("AssembledSystem.add takes a MatrixFreeSystem or a BoundaryTerm")
+        return self
+
+    def end(self, dirichlet_vals=None):
+        """endAssembly: the mesh's Dirichlet mask applied with the prescribed values dirichlet_vals [n_rhs, >= n] (None:
+        homogeneous); returns the CsrOperator over the object's arrays"""
+        g = dirichlet_vals
+        if g is not None:
+            g = g[None, :] if g.dim() == 1 else g
+            nc, ldg = MatrixFreeSystem._cols(g)
+            if nc != self.n_rhs:
+                raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
+        check(capi.load().l3k_asm_end(self._h, _ptr(g), 0 if g is None else ldg))
+        return _AssembledOperator(self, self._info().csr)
