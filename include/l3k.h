@@ -767,7 +767,8 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
  * l3k_asm_info_get: sizes, state, n_missing, the device pointers of the four arrays (valid as long as the object) and, on a
  *   closed system, the operator: solving is l3k_csr_diag / l3k_csr_pcg_solve* / l3k_csr_cheb_create on that handle, which the
  *   object owns (do not destroy it).
- * Static condensation is not part of this object (hexes: l3k_condense_*; quads: not there yet), nor is partitioned assembly. */
+ * Static condensation on hexes is not part of this object (l3k_condense_*); on quads it is a mode of it (below).  Partitioned
+ * assembly is not part of it. */
 typedef struct l3k_asm l3k_asm;
 enum { L3K_ASM_NEW = 0, L3K_ASM_OPEN = 1, L3K_ASM_CLOSED = 2 };
 typedef struct
@@ -789,6 +790,48 @@ int l3k_asm_add_boundary(l3k_asm* A, l3k_bnd* term, int64_t first, int64_t count
 int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg);
 int l3k_asm_info_get(const l3k_asm* A, l3k_asm_info* out);
 int l3k_asm_destroy(l3k_asm* A);
+
+/* ---- static condensation of the element-internal dofs inside the assembled system (quads) ----------------------------------
+ * StaticCondensationManager< ElementBoundary > of the reference (algsys/StaticCondensationManager.hpp:259-473), and stateful as it
+ * is: the object keeps, per element, the internal rows [K_ii | K_ib | F_i] over the system's Us fields -- Ni Us rows of
+ * Ni Us + Np Us + n_rhs doubles, Np = 4 p primary nodes (ix or iy in {0, p}) and Ni = (p-1)^2 internal ones, both in ascending
+ * element-local index, dofs node-major -- so
+ *     store_bytes = 8 n_elems (Ni Us) (Ni Us + Np Us + n_rhs)          (4.7 KB per element at p = 2, 16 KB at p = 4, 90 KB at p = 6; Us = 3)
+ * allocated at creation.  Any number of domain and boundary terms add to it; recovery needs no second assembly.
+ *
+ * l3k_asm_create_condensed: the arguments and refusals of l3k_asm_create; quads only -- a hex mesh is refused (-1; hexes are
+ *   condensed by l3k_condense_global).  The matrix is n x n over all local dofs in the CONDENSED graph: dof (a, f) couples with
+ *   (b, f') iff some element holds a and b among its primary nodes; the rows of internal dofs are empty.  At order 1 it is the
+ *   full graph.  begin / add_domain / add_boundary / end / info_get / destroy serve the object as they serve any l3k_asm.
+ * l3k_asm_begin also zeroes the store.  l3k_asm_add_*: same checks; every local system is split: its primary x primary block and
+ *   F_b are summed into the CSR arrays, its internal rows into the element's slot of the store (element systems: plain adds, one
+ *   system per element is in flight; side systems: fp64 atomics).
+ * l3k_asm_end: first one elimination pass over all elements: K_ii = L L^T, W = L^-1 K_ib, h = L^-1 F_i; -W^T W and -W^T h are summed
+ *   into values and rhs (bitwise symmetric per element); L^T, W and h stay in the store.  A pivot that is not positive and finite:
+ *   the element contributes no update and is counted (l3k_asm_cond_info::n_failed); -2, "non-positive pivot in the
+ *   element-internal block", the system stays open.  Then l3k_csr_dirichlet and the operator as for any l3k_asm.  A mask flag on
+ *   an element-internal dof is refused by l3k_csr_dirichlet itself (that row has no stored diagonal): -1, the system stays open.
+ *   After an l3k_asm_end that got as far as the elimination, l3k_asm_add_* and l3k_asm_end are refused until l3k_asm_begin.
+ *   Slots of at most 128 KiB per workgroup are factored in the LDS; larger ones (order 6 with 4 fields, order 7 with 3, order 8
+ *   with 2, and above) in place in global memory, by the same code.
+ * l3k_asm_recover: x [n_rhs][ldx] over the local dofs with the solved primary dofs; writes x_i = L^-T (h - W x_b) into the
+ *   internal dofs of every element (plain stores, one writer per dof, a fixed summation order: the same bits on every call).
+ *   -1: a system that is not closed, not condensed, ldx < n.  May be called once per solve of a time loop.
+ * l3k_asm_schur_updates: the element-level observable, from the store of a closed system: W_e = K_bi K_ii^-1 K_ib
+ *   [count][Nb][Nb] row-major, bitwise symmetric, and w_e = K_bi K_ii^-1 F_i [count][n_rhs][Nb], Nb = Np Us; either may be NULL.
+ *   Order 1: zeros.  -1: not closed, not condensed, a range outside the elements.
+ * Both return when the work is complete. */
+typedef struct
+{
+    int     condensed;                         /* 0 for a system made by l3k_asm_create (the other members are 0 then) */
+    int     n_primary_nodes, n_internal_nodes; /* per element: 4p, (p-1)^2 */
+    int64_t n_elems, store_bytes;
+    int64_t n_failed; /* elements whose internal block failed its pivot test in the last l3k_asm_end */
+} l3k_asm_cond_info;
+int l3k_asm_create_condensed(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out);
+int l3k_asm_cond_info_get(const l3k_asm* A, l3k_asm_cond_info* out);
+int l3k_asm_recover(l3k_asm* A, double* d_x, size_t ldx);
+int l3k_asm_schur_updates(l3k_asm* A, int64_t first, int64_t count, double* d_W, double* d_w);
 
 /* ---- static condensation of the element-internal dofs (hexes) -----------------------------------------------------------
  * The reference's CondensationPolicy::ElementBoundary (algsys/StaticCondensationManager.hpp).  Per element, with the primary

@@ -632,13 +632,24 @@ private:
 //   endAssembly            ~ endAssembly + DirichletBCAlgebraic::apply with the mesh's mask; d_dirichlet_vals [n_rhs][ldg] or nullptr
 //   solve                  ~ alg_sys.solve(CG{opts, NativeJacobiOpts{}}): Jacobi PCG on the closed system's CSR operator, column 0
 //   info                   ~ n, nnz, n_missing, ldr, n_rhs, state, the device arrays and (closed) the l3k_csr handle for l3k_csr_*
+// Condensation::ElementBoundary (quads; CondensationPolicy::ElementBoundary, algsys/StaticCondensationManager.hpp:259-473) eliminates
+// the element-internal dofs in endAssembly (l3k_asm_create_condensed): the matrix couples the primary dofs only, and
+//   recover                ~ recoverSolution: the internal dofs of d_x [n_rhs][ldx] from its solved primary dofs
+//   schurUpdates           ~ K_bi K_ii^-1 K_ib [count][Nb][Nb] and K_bi K_ii^-1 F_i [count][n_rhs][Nb] of the elements, either may be null
+//   condInfo               ~ the sizes of the per-element store and the elements that failed the pivot test of the last endAssembly
+enum class Condensation
+{
+    None,
+    ElementBoundary
+};
 class AssembledSystem
 {
 public:
-    AssembledSystem(const DeviceMesh& mesh, std::span< const int > field_inds = {}, int n_rhs = 1, size_t workspace_bytes = 0)
+    AssembledSystem(const DeviceMesh& mesh, std::span< const int > field_inds = {}, int n_rhs = 1, size_t workspace_bytes = 0,
+                    Condensation condensation = Condensation::None)
     {
-        check(l3k_asm_create(mesh.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), n_rhs, workspace_bytes,
-                             &m_asm));
+        check((condensation == Condensation::ElementBoundary ? l3k_asm_create_condensed : l3k_asm_create)(
+            mesh.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), n_rhs, workspace_bytes, &m_asm));
     }
     AssembledSystem(const AssembledSystem&)            = delete;
     AssembledSystem& operator=(const AssembledSystem&) = delete;
@@ -683,6 +694,14 @@ public:
         if (!res.converged)
             throw std::runtime_error{"Solver failed to converge"};
         return res;
+    }
+    void recover(double* d_x, size_t ldx) { check(l3k_asm_recover(m_asm, d_x, ldx)); }
+    void schurUpdates(int64_t first, int64_t count, double* d_W, double* d_w) { check(l3k_asm_schur_updates(m_asm, first, count, d_W, d_w)); }
+    l3k_asm_cond_info condInfo() const
+    {
+        l3k_asm_cond_info i{};
+        check(l3k_asm_cond_info_get(m_asm, &i));
+        return i;
     }
     l3k_asm* get() const { return m_asm; }
 

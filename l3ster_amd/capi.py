@@ -73,6 +73,12 @@ class GraphInfo(C.Structure):
                 ("lds_key_capacity", C.c_int)]
 
 
+class AsmCondInfo(C.Structure):
+    """l3k_asm_cond_info: the per-element store of a condensed assembled system and the pivot failures of its last end"""
+    _fields_ = [("condensed", C.c_int), ("n_primary_nodes", C.c_int), ("n_internal_nodes", C.c_int), ("n_elems", C.c_int64),
+                ("store_bytes", C.c_int64), ("n_failed", C.c_int64)]
+
+
 class AsmInfo(C.Structure):
     """l3k_asm_info: sizes, state, entries outside the graph, the device pointers of the four arrays and the operator"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_missing", C.c_int64), ("ldr", C.c_size_t), ("n_rhs", C.c_int),
@@ -272,6 +278,10 @@ SIGNATURES = {
     "l3k_asm_end": (C.c_int, [_vp, _vp, C.c_size_t]),
     "l3k_asm_info_get": (C.c_int, [_vp, C.POINTER(AsmInfo)]),
     "l3k_asm_destroy": (C.c_int, [_vp]),
+    "l3k_asm_create_condensed": (C.c_int, [_vp, C.c_int, c_int_p, C.c_int, C.c_size_t, C.POINTER(_vp)]),
+    "l3k_asm_cond_info_get": (C.c_int, [_vp, C.POINTER(AsmCondInfo)]),
+    "l3k_asm_recover": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "l3k_asm_schur_updates": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

@@ -6,7 +6,13 @@
 // l3k_bnd_assemble_global: the same launchers, and the sub-batch pipelines of the TERMS, sized by the object's workspace_bytes); quads
 // through the element and side kernels of device/quad_assemble.hpp in front of the row-major scatter kernel of api_assembled.hip, on
 // the object's own sub-batch pipeline (sumQuadSystems below; runSubBatches, objects.hpp).
+//
+// A system made by l3k_asm_create_condensed (quads) eliminates the element-internal dofs: the same pipeline, with the split kernel
+// of device/quad_condense.hpp in the scatter's place, a per-element store of the internal rows that l3k_asm_begin zeroes and
+// l3k_asm_end factors, and l3k_asm_recover / l3k_asm_schur_updates on the factored store.
 #include "objects.hpp"
+
+#include "device/quad_condense.hpp"
 
 #include <algorithm>
 
@@ -23,6 +29,13 @@ struct l3k_asm
     DevBuf< double >   values, rhs, zero_vals;
     SubBatchPipe       pipe;
     l3k_csr*           csr = nullptr;
+    // static condensation: the store [n_elems][Nis][LD] of the internal rows [K_ii | K_ib | F_i], LD = Nis + Nbs + n_rhs
+    bool               condensed = false, eliminated = false;
+    int                Us = 0, Nis = 0, Nbs = 0, LD = 0, team = l3k::dev::cond_threads;
+    int64_t            n_failed = 0;
+    DevBuf< double >   store;
+    DevBuf< int >      d_fields;
+    DevBuf< unsigned > d_nfail;
     ~l3k_asm()
     {
         if (csr)
@@ -90,12 +103,66 @@ int64_t subBatch(size_t workspace_bytes, size_t per_system, int64_t count, int64
     nb         = std::min(nb, std::min(count, cap));
     return nb < 1 ? 1 : nb;
 }
+// the split of a sub-batch of a condensed system: primary block -> CSR arrays, internal rows -> the store (quad_condense.hpp);
+// d_elem_of: the elements of side systems (several of one element may share the launch: atomics), nullptr for element systems
+template < int U >
+int launchQuadSplitU(const l3k::dev::QuadSplitArgs& a, bool atomic, int64_t blocks, hipStream_t s)
+{
+    if (atomic)
+        return l3k::dev::launchKernel("quadSplitKernel", l3k::dev::quadSplitKernel< U, true >, dim3(unsigned(blocks)), dim3(64), 0, s, a);
+    return l3k::dev::launchKernel("quadSplitKernel", l3k::dev::quadSplitKernel< U, false >, dim3(unsigned(blocks)), dim3(64), 0, s, a);
+}
+int launchQuadSplit(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, const int64_t* d_elem_of, int64_t at, int64_t n, const double* d_K,
+                    const double* d_F, unsigned long long* d_count, hipStream_t s)
+{
+    const l3k_mesh*        m = A->mesh;
+    const int              n1d = m->order + 1;
+    l3k::dev::QuadSplitArgs a{};
+    a.nodes     = d_nodes;
+    a.elem_of   = d_elem_of;
+    a.K         = d_K;
+    a.F         = d_F;
+    a.row_ptr   = A->row_ptr.ptr;
+    a.col_ind   = A->col_ind.ptr;
+    a.values    = A->values.ptr;
+    a.rhs       = A->rhs.ptr;
+    a.store     = A->store.ptr;
+    a.ldr       = A->ldr;
+    a.n_missing = d_count;
+    a.first     = at;
+    a.count     = n;
+    a.n1d       = n1d;
+    a.dpn       = m->dofs_per_node;
+    a.n_rhs     = t.n_rhs;
+    a.Us        = A->Us;
+    a.Nis       = A->Nis;
+    a.LD        = A->LD;
+    for (int u = 0; u < t.kp.n_unknowns; ++u)
+    {
+        a.field_inds[u] = t.field_inds[u];
+        a.slot[u] = int(std::lower_bound(A->field_inds.begin(), A->field_inds.end(), t.field_inds[u]) - A->field_inds.begin()); // (checkTerm: present)
+    }
+    const int64_t blocks = n * n1d * n1d; // (subBatch caps n)
+    switch (t.kp.n_unknowns)
+    {
+    case 1: return launchQuadSplitU< 1 >(a, d_elem_of != nullptr, blocks, s);
+    case 2: return launchQuadSplitU< 2 >(a, d_elem_of != nullptr, blocks, s);
+    case 3: return launchQuadSplitU< 3 >(a, d_elem_of != nullptr, blocks, s);
+    case 4: return launchQuadSplitU< 4 >(a, d_elem_of != nullptr, blocks, s);
+    case 5: return launchQuadSplitU< 5 >(a, d_elem_of != nullptr, blocks, s);
+    case 6: return launchQuadSplitU< 6 >(a, d_elem_of != nullptr, blocks, s);
+    case 7: return launchQuadSplitU< 7 >(a, d_elem_of != nullptr, blocks, s);
+    case 8: return launchQuadSplitU< 8 >(a, d_elem_of != nullptr, blocks, s);
+    default: setError("l3k_asm_add: %d unknowns not supported (1..8)", t.kp.n_unknowns); return -1;
+    }
+}
 // The quad route of both l3k_asm_add_* calls: the local systems [first, first + count) of a term -- Nd = NN U dofs each, their node
 // rows d_nodes[first + i] -- formed by form(at, n, d_K, d_F, d_flag) on the context's stream into one half of the object's pipeline
 // while the other half is summed into the object's arrays on the second stream.  Entries outside the graph are added to
-// A->n_missing; -2 if a forming kernel raised a half's degenerate-element flag
+// A->n_missing; -2 if a forming kernel raised a half's degenerate-element flag.  d_elem_of: the elements of side systems (a
+// condensed system files their internal rows under them), nullptr for element systems
 template < typename Form >
-int sumQuadSystems(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, int64_t first, int64_t count, Form&& form)
+int sumQuadSystems(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, const int64_t* d_elem_of, int64_t first, int64_t count, Form&& form)
 {
     const l3k_mesh* m = A->mesh;
     L3K_HIP(hipSetDevice(A->ctx->device));
@@ -115,6 +182,8 @@ int sumQuadSystems(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, int
     if (int rc = runSubBatches(
             g, sa, first, count, nb, [&](int k, int64_t at, int64_t n) { return form(at, n, g.buf[k], g.buf[k] + kd, flag[k]); },
             [&](int k, int64_t at, int64_t n) {
+                if (A->condensed)
+                    return launchQuadSplit(A, t, d_nodes, d_elem_of, at, n, g.buf[k], g.buf[k] + kd, d_count, g.second);
                 return launchAssembledScatterRows(A->ctx, m, d_nodes, U, R, t.field_inds, at, n, g.buf[k], g.buf[k] + kd, A->row_ptr.ptr,
                                                   A->col_ind.ptr, A->values.ptr, A->rhs.ptr, A->ldr, 0, d_count, g.second, 0);
             }))
@@ -123,6 +192,16 @@ int sumQuadSystems(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, int
     const int rc      = readDegenerateFlags(sa, flag[0], flag[1], d_count, &missing);
     A->n_missing += missing;
     return rc;
+}
+// a condensed system whose store l3k_asm_end has factored takes no more terms and no second elimination
+int checkNotEliminated(const l3k_asm* A, const char* what)
+{
+    if (A->condensed && A->eliminated)
+    {
+        setError("%s: the element-internal blocks of this system were eliminated by l3k_asm_end; l3k_asm_begin starts the next assembly", what);
+        return -1;
+    }
+    return 0;
 }
 // what the term of an l3k_asm_add_* call must share with the system (KernelTerm: both kinds of term)
 int checkTerm(const l3k_asm* A, const KernelTerm& t, const char* what)
@@ -152,6 +231,86 @@ int checkTerm(const l3k_asm* A, const KernelTerm& t, const char* what)
     {
         setError("%s: the term has n_rhs = %d, the system %d", what, t.n_rhs, A->n_rhs);
         return -1;
+    }
+    return checkNotEliminated(A, what);
+}
+// l3k_asm_recover / l3k_asm_schur_updates: a closed condensed system
+int checkFactoredStore(const l3k_asm* A, const char* what)
+{
+    if (!A->condensed)
+    {
+        setError("%s: the system is not condensed (l3k_asm_create_condensed makes one that is)", what);
+        return -1;
+    }
+    if (A->state != L3K_ASM_CLOSED)
+    {
+        setError("%s: the system is not closed (l3k_asm_end factors the element-internal blocks and closes it)", what);
+        return -1;
+    }
+    return 0;
+}
+l3k::dev::QuadCondArgs condArgs(const l3k_asm* A, int64_t first, int64_t count)
+{
+    l3k::dev::QuadCondArgs a{};
+    a.store      = A->store.ptr;
+    a.elem_nodes = A->mesh->elem_nodes.ptr;
+    a.fields     = A->d_fields.ptr;
+    a.first      = first;
+    a.count      = count;
+    a.n1d        = A->mesh->order + 1;
+    a.dpn        = A->mesh->dofs_per_node;
+    a.n_rhs      = A->n_rhs;
+    a.Us         = A->Us;
+    a.Nis        = A->Nis;
+    a.Nbs        = A->Nbs;
+    a.LD         = A->LD;
+    a.team       = A->team;
+    return a;
+}
+unsigned condGrid(const l3k_asm* A, int64_t count)
+{
+    const int per_wg = l3k::dev::cond_threads / A->team;
+    return unsigned((count + per_wg - 1) / per_wg);
+}
+// l3k_asm_end on a condensed system: the elimination pass over all elements; -2 where a pivot test failed
+int eliminateStore(l3k_asm* A)
+{
+    A->eliminated = true;
+    A->n_failed   = 0;
+    const int64_t ne = A->mesh->n_elems;
+    if (A->Nis == 0 || ne == 0)
+        return 0;
+    hipStream_t              s = A->ctx->stream;
+    l3k::dev::QuadCondArgs   a = condArgs(A, 0, ne);
+    a.row_ptr                  = A->row_ptr.ptr;
+    a.col_ind                  = A->col_ind.ptr;
+    a.values                   = A->values.ptr;
+    a.rhs                      = A->rhs.ptr;
+    a.ldr                      = A->ldr;
+    a.n_failed                 = A->d_nfail.ptr;
+    a.n_missing                = A->ctx->missCounter();
+    L3K_HIP(hipMemsetAsync(a.n_failed, 0, sizeof(unsigned), s));
+    L3K_HIP(hipMemsetAsync(a.n_missing, 0, sizeof(unsigned long long), s));
+    const size_t lds = sizeof(double) * size_t(l3k::dev::cond_threads / A->team) * A->Nis * A->LD;
+    const int    rc  = lds <= l3k::dev::cond_lds_bytes
+                           ? l3k::dev::launchKernel("quadEliminateKernel", l3k::dev::quadEliminateKernel< true >, dim3(condGrid(A, ne)),
+                                                    dim3(l3k::dev::cond_threads), lds, s, a)
+                           : l3k::dev::launchKernel("quadEliminateKernel", l3k::dev::quadEliminateKernel< false >, dim3(condGrid(A, ne)),
+                                                    dim3(l3k::dev::cond_threads), 0, s, a);
+    if (rc)
+        return rc;
+    unsigned           nfail   = 0;
+    unsigned long long missing = 0;
+    L3K_HIP(hipMemcpyAsync(&nfail, a.n_failed, sizeof nfail, hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipMemcpyAsync(&missing, a.n_missing, sizeof missing, hipMemcpyDeviceToHost, s));
+    L3K_HIP(hipStreamSynchronize(s));
+    A->n_missing += int64_t(missing);
+    A->n_failed = nfail;
+    if (nfail)
+    {
+        setError("l3k_asm_end: non-positive pivot in the element-internal block of %u of %lld elements; the system stays open "
+                 "(l3k_asm_begin starts over)", nfail, (long long)ne);
+        return -2;
     }
     return 0;
 }
@@ -219,32 +378,57 @@ int l3k_asm_side_systems(l3k_bnd* term, int64_t first, int64_t count, double* d_
     return inst->assemble(a, term->blobPtr(), term->ctx->stream);
 }
 
-int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out)
+} // extern "C"
+namespace
+{
+// l3k_asm_create (`condensed` = false: the full graph) and l3k_asm_create_condensed (quads: the graph of the primary nodes and the store)
+int createSystem(const char* what, bool condensed, l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes,
+                 l3k_asm** out)
 {
     if (!mesh || !out)
     {
-        setError("l3k_asm_create: null argument");
+        setError("%s: null argument", what);
         return -1;
     }
     if (n_fields < 0 || (n_fields > 0 && !field_inds) || (n_fields == 0 && field_inds))
     {
-        setError("l3k_asm_create: n_fields = %d with %s field_inds; it is 1 .. dofs_per_node indices, or 0 and NULL for all dofs", n_fields,
+        setError("%s: n_fields = %d with %s field_inds; it is 1 .. dofs_per_node indices, or 0 and NULL for all dofs", what, n_fields,
                  field_inds ? "non-null" : "null");
         return -1;
     }
     if (n_rhs < 1)
     {
-        setError("l3k_asm_create: n_rhs = %d; it is at least 1", n_rhs);
+        setError("%s: n_rhs = %d; it is at least 1", what, n_rhs);
         return -1;
     }
     if (mesh->n_ghost_nodes > 0)
     {
-        setError("l3k_asm_create: a partitioned mesh (%lld ghost nodes): the assembled system and its CSR operator are single-rank",
+        setError("%s: a partitioned mesh (%lld ghost nodes): the assembled system and its CSR operator are single-rank", what,
                  (long long)mesh->n_ghost_nodes);
         return -1;
     }
-    l3k_graph* g = nullptr;
-    if (int rc = l3k_graph_create(mesh, n_fields, field_inds, L3K_GRAPH_FULL, &g)) // (the rules of field_inds are the graph's)
+    if (condensed && mesh->dim != 2)
+    {
+        setError("%s: a hex mesh: the condensed assembled system is for quads; hexes are condensed by l3k_condense_global", what);
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(mesh->ctx->device));
+    const int          n1d = mesh->order + 1, Np = 4 * mesh->order;
+    DevBuf< uint32_t > prim; // the primary node rows: the elements of the condensed graph (alive until the fill has run)
+    l3k_graph*         g = nullptr;
+    if (condensed)
+    {
+        if (int rc = prim.alloc(size_t(mesh->n_elems) * Np))
+            return rc;
+        if (mesh->n_elems > 0)
+            if (int rc = l3k::dev::launchKernel("quadPrimaryNodesKernel", l3k::dev::quadPrimaryNodesKernel, dim3(gridFor(mesh->n_elems * Np)),
+                                                dim3(256), 0, mesh->ctx->stream, static_cast< const uint32_t* >(mesh->elem_nodes.ptr),
+                                                mesh->n_elems, n1d, prim.ptr))
+                return rc;
+        if (int rc = graphCreateOn(mesh, prim.ptr, Np, Np, 0, n_fields, field_inds, &g))
+            return rc;
+    }
+    else if (int rc = l3k_graph_create(mesh, n_fields, field_inds, L3K_GRAPH_FULL, &g)) // (the rules of field_inds are the graph's)
         return rc;
     const auto     drop_graph = [&](int rc) { (void)l3k_graph_destroy(g); return rc; };
     l3k_graph_info gi;
@@ -271,21 +455,49 @@ int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rh
         return drop_graph(rc);
     if (int rc = l3k_graph_fill(g, A->row_ptr.ptr, A->col_ind.ptr))
         return drop_graph(rc);
+    if (condensed)
+    {
+        const int Ni = (mesh->order - 1) * (mesh->order - 1);
+        A->condensed = true;
+        A->Us        = U;
+        A->Nis       = Ni * U;
+        A->Nbs       = Np * U;
+        A->LD        = A->Nis + A->Nbs + n_rhs;
+        A->team      = A->Nis <= 4 ? 16 : (A->Nis <= 32 ? 64 : l3k::dev::cond_threads);
+        if (int rc = A->store.alloc(size_t(mesh->n_elems) * A->Nis * A->LD))
+            return drop_graph(rc);
+        if (int rc = A->d_fields.upload(A->field_inds.data(), A->field_inds.size(), A->ctx->stream))
+            return drop_graph(rc);
+        if (int rc = A->d_nfail.alloc(1))
+            return drop_graph(rc);
+    }
     // values and rhs <- 0; the graph object's buffers feed the fill: synchronise before it goes
     hipStream_t s   = A->ctx->stream;
     hipError_t  err = gi.nnz ? hipMemsetAsync(A->values.ptr, 0, sizeof(double) * size_t(gi.nnz), s) : hipSuccess;
     if (err == hipSuccess && gi.n)
         err = hipMemsetAsync(A->rhs.ptr, 0, sizeof(double) * size_t(n_rhs) * A->ldr, s);
+    if (err == hipSuccess && A->store.n)
+        err = hipMemsetAsync(A->store.ptr, 0, sizeof(double) * A->store.n, s);
     if (err == hipSuccess)
         err = hipStreamSynchronize(s);
     (void)l3k_graph_destroy(g);
     if (err != hipSuccess)
     {
-        setError("l3k_asm_create: zeroing the arrays failed: %s", hipGetErrorString(err));
+        setError("%s: zeroing the arrays failed: %s", what, hipGetErrorString(err));
         return -3;
     }
     *out = A.release();
     return 0;
+}
+} // namespace
+extern "C" {
+int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out)
+{
+    return createSystem("l3k_asm_create", false, mesh, n_fields, field_inds, n_rhs, workspace_bytes, out);
+}
+int l3k_asm_create_condensed(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out)
+{
+    return createSystem("l3k_asm_create_condensed", true, mesh, n_fields, field_inds, n_rhs, workspace_bytes, out);
 }
 
 int l3k_asm_begin(l3k_asm* A)
@@ -301,6 +513,10 @@ int l3k_asm_begin(l3k_asm* A)
         L3K_HIP(hipMemsetAsync(A->values.ptr, 0, sizeof(double) * size_t(A->nnz), s));
     if (A->n)
         L3K_HIP(hipMemsetAsync(A->rhs.ptr, 0, sizeof(double) * size_t(A->n_rhs) * A->ldr, s));
+    if (A->store.n)
+        L3K_HIP(hipMemsetAsync(A->store.ptr, 0, sizeof(double) * A->store.n, s));
+    A->eliminated = false;
+    A->n_failed   = 0;
     A->n_missing = 0;
     A->state     = L3K_ASM_OPEN;
     return 0;
@@ -345,7 +561,7 @@ int l3k_asm_add_domain(l3k_asm* A, l3k_mf* term, int64_t first, int64_t count)
     const auto* inst = quadElementInstance(term, what);
     if (!inst)
         return -4;
-    return sumQuadSystems(A, *term, m->elem_nodes.ptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double* d_flag) {
+    return sumQuadSystems(A, *term, m->elem_nodes.ptr, nullptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double* d_flag) {
         l3k::dev::ElemArgs a;
         if (int rc = assemblyArgs(term, at, n, a))
             return rc;
@@ -394,7 +610,7 @@ int l3k_asm_add_boundary(l3k_asm* A, l3k_bnd* term, int64_t first, int64_t count
         return rc;
     if (int rc = sideListInOrder(term))
         return rc;
-    return sumQuadSystems(A, *term, term->in_order.nodes.ptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double*) {
+    return sumQuadSystems(A, *term, term->in_order.nodes.ptr, term->in_order.elem.ptr, first, count, [&](int64_t at, int64_t n, double* d_K, double* d_F, double*) {
         l3k::dev::SideAsmArgs a = sideArgsInOrder(term);
         a.face_begin            = at;
         a.face_count            = n;
@@ -422,6 +638,11 @@ int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg)
         return -1;
     }
     L3K_HIP(hipSetDevice(A->ctx->device));
+    if (int rc = checkNotEliminated(A, "l3k_asm_end"))
+        return rc;
+    if (A->condensed)
+        if (int rc = eliminateStore(A))
+            return rc;
     if (!A->csr) // (the operator keeps the pointers of the object's arrays: created once, valid for every later assembly)
         if (int rc = l3k_csr_create(A->ctx, A->n, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, 0, &A->csr))
             return rc;
@@ -455,6 +676,86 @@ int l3k_asm_info_get(const l3k_asm* A, l3k_asm_info* out)
     }
     *out = {A->n, A->nnz, A->n_missing, A->ldr, A->n_rhs, A->state, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, A->rhs.ptr,
             A->state == L3K_ASM_CLOSED ? A->csr : nullptr};
+    return 0;
+}
+
+int l3k_asm_cond_info_get(const l3k_asm* A, l3k_asm_cond_info* out)
+{
+    if (!A || !out)
+    {
+        setError("l3k_asm_cond_info_get: null argument");
+        return -1;
+    }
+    *out = {};
+    if (A->condensed)
+        *out = {1, 4 * A->mesh->order, (A->mesh->order - 1) * (A->mesh->order - 1), A->mesh->n_elems, int64_t(A->store.n * sizeof(double)),
+                A->n_failed};
+    return 0;
+}
+
+int l3k_asm_recover(l3k_asm* A, double* d_x, size_t ldx)
+{
+    const char* const what = "l3k_asm_recover";
+    if (!A || !d_x)
+    {
+        setError("%s: null argument", what);
+        return -1;
+    }
+    if (int rc = checkFactoredStore(A, what))
+        return rc;
+    if (ldx < size_t(A->n))
+    {
+        setError("%s: leading dimension of x (%zu) smaller than the number of dofs (%lld)", what, ldx, (long long)A->n);
+        return -1;
+    }
+    const int64_t ne = A->mesh->n_elems;
+    if (A->Nis == 0 || ne == 0)
+        return 0;
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    l3k::dev::QuadCondArgs a = condArgs(A, 0, ne);
+    a.x                      = d_x;
+    a.ldx                    = ldx;
+    const size_t lds = sizeof(double) * size_t(l3k::dev::cond_threads / A->team) * (A->Nbs + 2 * A->Nis);
+    if (int rc = l3k::dev::launchKernel("quadRecoverKernel", l3k::dev::quadRecoverKernel, dim3(condGrid(A, ne)), dim3(l3k::dev::cond_threads), lds,
+                                        A->ctx->stream, a))
+        return rc;
+    L3K_HIP(hipStreamSynchronize(A->ctx->stream));
+    return 0;
+}
+
+int l3k_asm_schur_updates(l3k_asm* A, int64_t first, int64_t count, double* d_W, double* d_w)
+{
+    const char* const what = "l3k_asm_schur_updates";
+    if (!A)
+    {
+        setError("%s: null argument", what);
+        return -1;
+    }
+    if (int rc = checkFactoredStore(A, what))
+        return rc;
+    if (int rc = checkRange(A->mesh, first, count))
+        return rc;
+    if (count == 0 || (!d_W && !d_w))
+        return 0;
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    hipStream_t s = A->ctx->stream;
+    if (A->Nis == 0) // order 1: nothing to eliminate
+    {
+        if (d_W)
+            L3K_HIP(hipMemsetAsync(d_W, 0, sizeof(double) * size_t(count) * A->Nbs * A->Nbs, s));
+        if (d_w)
+            L3K_HIP(hipMemsetAsync(d_w, 0, sizeof(double) * size_t(count) * A->n_rhs * A->Nbs, s));
+    }
+    else
+    {
+        l3k::dev::QuadCondArgs a = condArgs(A, first, count);
+        a.outW                   = d_W;
+        a.outw                   = d_w;
+        if (int rc = l3k::dev::launchKernel("quadSchurOutKernel", l3k::dev::quadSchurOutKernel, dim3(condGrid(A, count)),
+                                            dim3(l3k::dev::cond_threads), 0, s, a))
+            return rc;
+    }
+    L3K_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -64,23 +64,12 @@ int degreesToOffsets(l3k_graph* g, unsigned long long (&h)[stat_words], int64_t&
 }
 } // namespace
 
-extern "C" {
-
-int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int kind, l3k_graph** out)
+// The graph of the node rows d_elem_nodes [n_elems][N] of `mesh`, of which the Ns selected ones couple (all of them, or with
+// `condensed` the primary nodes of a hex): l3k_graph_create on the mesh's own rows, and the condensed graph of a quad mesh on the
+// rows of its primary nodes (api_asm.hip), which must outlive the fill
+int graphCreateOn(l3k_mesh* mesh, const uint32_t* d_elem_nodes, int N, int Ns, int condensed, int n_fields, const int* field_inds,
+                  l3k_graph** out)
 {
-    if (!mesh || !out)
-    {
-        setError("l3k_graph_create: null argument");
-        return -1;
-    }
-    if (kind != L3K_GRAPH_FULL && kind != L3K_GRAPH_CONDENSED)
-    {
-        setError("l3k_graph_create: kind = %d; it is L3K_GRAPH_FULL (0) or L3K_GRAPH_CONDENSED (1)", kind);
-        return -1;
-    }
-    if (kind == L3K_GRAPH_CONDENSED)
-        if (int rc = refuseQuads(mesh, "l3k_graph_create(L3K_GRAPH_CONDENSED)"))
-            return rc;
     const int dpn = mesh->dofs_per_node;
     if (n_fields < 0 || n_fields > dpn || (n_fields > 0 && !field_inds) || (n_fields == 0 && field_inds))
     {
@@ -106,8 +95,7 @@ int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int ki
         setError("l3k_graph_create: n = %lld does not fit the 32-bit column indices", static_cast< long long >(n));
         return -1;
     }
-    const int n1d = mesh->order + 1, N = mesh->dim == 2 ? n1d * n1d : n1d * n1d * n1d;
-    const int inner = mesh->order - 1, Ns = kind == L3K_GRAPH_CONDENSED ? N - inner * inner * inner : N;
+    const int n1d = mesh->order + 1;
     if (mesh->n_elems > int64_t(UINT32_MAX))
     {
         setError("l3k_graph_create: %lld elements do not fit the 32-bit node -> element table", static_cast< long long >(mesh->n_elems));
@@ -132,13 +120,13 @@ int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int ki
     if (int rc = g->stats.alloc(stat_words + 1)) // + the cursor of the scratch list
         return rc;
     GraphArgs& a = g->args;
-    a.elem_nodes = mesh->elem_nodes.ptr;
+    a.elem_nodes = d_elem_nodes;
     a.n_elems    = mesh->n_elems;
     a.n_nodes    = n_nodes;
     a.N          = N;
     a.Ns         = Ns;
     a.n1d        = n1d;
-    a.condensed  = kind == L3K_GRAPH_CONDENSED;
+    a.condensed  = condensed;
     a.U          = U;
     a.dpn        = dpn;
     a.field_inds = g->field_inds.ptr;
@@ -215,6 +203,28 @@ int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int ki
                                lds_key_capacity};
     *out = g.release();
     return 0;
+}
+
+extern "C" {
+
+int l3k_graph_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int kind, l3k_graph** out)
+{
+    if (!mesh || !out)
+    {
+        setError("l3k_graph_create: null argument");
+        return -1;
+    }
+    if (kind != L3K_GRAPH_FULL && kind != L3K_GRAPH_CONDENSED)
+    {
+        setError("l3k_graph_create: kind = %d; it is L3K_GRAPH_FULL (0) or L3K_GRAPH_CONDENSED (1)", kind);
+        return -1;
+    }
+    if (kind == L3K_GRAPH_CONDENSED)
+        if (int rc = refuseQuads(mesh, "l3k_graph_create(L3K_GRAPH_CONDENSED)"))
+            return rc;
+    const int n1d = mesh->order + 1, N = mesh->dim == 2 ? n1d * n1d : n1d * n1d * n1d;
+    const int inner = mesh->order - 1, Ns = kind == L3K_GRAPH_CONDENSED ? N - inner * inner * inner : N;
+    return graphCreateOn(mesh, mesh->elem_nodes.ptr, N, Ns, kind == L3K_GRAPH_CONDENSED, n_fields, field_inds, out);
 }
 int l3k_graph_info_get(const l3k_graph* g, l3k_graph_info* out)
 {

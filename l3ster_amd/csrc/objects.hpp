@@ -504,6 +504,10 @@ int assemblyWorkspace(l3k_mf* mf, const l3k::dev::Instance* inst, int64_t count,
 // ... and the flag (or the two of a pipeline's halves) and the miss counter read back on s, which is synchronised: -2 if a flag is set
 int readDegenerateFlags(hipStream_t s, const double* d_flag0, const double* d_flag1 = nullptr, const unsigned long long* d_count = nullptr,
                         int64_t* n_missing = nullptr);
+// api_graph.hip: l3k_graph_create's builder on any table of node rows of the mesh (the argument checks of field_inds are its own)
+struct l3k_graph;
+int graphCreateOn(l3k_mesh* mesh, const uint32_t* d_elem_nodes, int N, int Ns, int condensed, int n_fields, const int* field_inds,
+                  l3k_graph** out);
 // api_bnd_assemble.hip: the term's list of sides on the device in the order it was given (l3k_bnd::in_order), built on first use
 int sideListInOrder(l3k_bnd* b);
 // api_bnd_assemble.hip: with l3k_mf_assemble_boundary on and terms attached, the refusals of `what` (0, or -1 with the error set) ...

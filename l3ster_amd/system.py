@@ -855,13 +855,18 @@ def norm_l2(mesh, residual_id, fields=None, kernel_params=None, asm_opts=(1, 0, 
     return np.sqrt(sq)
 
 
-def element_node_split(order):
-    """(primary, internal) element-local node indices of a hex of `order` (ix + n iy + n^2 iz, n = order + 1), each ascending:
-    the internal nodes have all of ix, iy, iz in 1 .. order-1 (mesh/ElementTraits.hpp:37-59)."""
+def element_node_split(order, dim=3):
+    """(primary, internal) element-local node indices of a hex (dim = 3: ix + n iy + n^2 iz, n = order + 1) or a quad (dim = 2:
+    ix + n iy) of `order`, each ascending: the internal nodes have all of their indices in 1 .. order-1
+    (mesh/ElementTraits.hpp:37-59)."""
+    if dim not in (2, 3):
+        raise L3KError(f"element_node_split: dim = {dim}; it is 2 (quads) or 3 (hexes)")
     n = order + 1
-    idx = np.arange(n ** 3)
-    ix, iy, iz = idx % n, (idx // n) % n, idx // (n * n)
-    inner = (ix >= 1) & (ix <= order - 1) & (iy >= 1) & (iy <= order - 1) & (iz >= 1) & (iz <= order - 1)
+    idx = np.arange(n ** dim)
+    inner = np.ones(idx.shape, dtype=bool)
+    for d in range(dim):
+        i = (idx // n ** d) % n
+        inner &= (i >= 1) & (i <= order - 1)
     return idx[~inner], idx[inner]
 
 
@@ -1292,17 +1297,26 @@ class AssembledSystem:
     field_inds (strictly ascending; None = all dofs of the node: the union of the terms' dofs), the right-hand sides
     [n_rhs, n] and, on quads, the sub-batch workspace (workspace_bytes, 0 = 1 GiB; hexes use the terms' own pipelines with that size);
     row_ptr, col_ind, values and rhs are torch views of them, not copies, made on access.  end() applies the mesh's Dirichlet mask with the prescribed values and returns a CsrOperator over the
-    same arrays, which solve.pcg and solve.ChebyshevPreconditioner take.  A partitioned mesh is refused."""
+    same arrays, which solve.pcg and solve.ChebyshevPreconditioner take.  A partitioned mesh is refused.
+
+    condensation="element_boundary" (quads; CondensationPolicy::ElementBoundary of the reference, l3k_asm_create_condensed): the
+    matrix lives on the condensed graph (the primary dofs of every element coupled, the rows of internal dofs empty), the object
+    keeps the internal rows of every element, end() eliminates them, and recover(x) fills the internal dofs of a solution."""
 
     STATES = ("new", "open", "closed")
+    CONDENSATION = ("none", "element_boundary")
 
-    def __init__(self, mesh, field_inds=None, n_rhs=1, workspace_bytes=0):
-        self.mesh, self.ctx, self.n_rhs = mesh, mesh.ctx, n_rhs
+    def __init__(self, mesh, field_inds=None, n_rhs=1, workspace_bytes=0, condensation="none"):
+        if condensation not in self.CONDENSATION:
+            raise L3KError(f"AssembledSystem: condensation = {condensation!r}; it is one of {self.CONDENSATION}")
+        self.mesh, self.ctx, self.n_rhs, self.condensation = mesh, mesh.ctx, n_rhs, condensation
         fi = None if field_inds is None else (C.c_int * len(field_inds))(*[int(f) for f in field_inds])
         self._h = C.c_void_p()
-        check(capi.load().l3k_asm_create(mesh._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes, C.byref(self._h)))
+        create = capi.load().l3k_asm_create if condensation == "none" else capi.load().l3k_asm_create_condensed
+        check(create(mesh._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes, C.byref(self._h)))
         i = self._info()
         self.n, self.nnz = i.n, i.nnz
+        self.n_fields = mesh.dofs_per_node if field_inds is None else len(field_inds)
 
     def __del__(self):
         if getattr(self, "_h", None) and capi is not None:
@@ -1388,3 +1402,35 @@ class AssembledSystem:
                 raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
         check(capi.load().l3k_asm_end(self._h, _ptr(g), 0 if g is None else ldg))
         return _AssembledOperator(self, self._info().csr)
+
+    @property
+    def cond_info(self):
+        """condensed, n_primary_nodes and n_internal_nodes per element, n_elems, store_bytes and n_failed (the elements whose
+        internal block failed the pivot test of the last end()); all 0 on a system without condensation"""
+        import types
+        i = capi.AsmCondInfo()
+        check(capi.load().l3k_asm_cond_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.AsmCondInfo._fields_})
+
+    def recover(self, x):
+        """recoverSolution: the internal dofs of x [n] or [n_rhs, >= n] (float64, on the device, contiguous rows) from its solved
+        primary dofs, in place; a closed condensed system"""
+        X = x[None, :] if x.dim() == 1 else x
+        nc, ldx = MatrixFreeSystem._cols(X)
+        if nc != self.n_rhs:
+            raise L3KError(f"AssembledSystem.recover: x has {nc} columns, the system n_rhs = {self.n_rhs}")
+        check(capi.load().l3k_asm_recover(self._h, _ptr(X), ldx))
+        return x
+
+    def schur_updates(self, first=0, count=None):
+        """(W, w): K_bi K_ii^-1 K_ib [count, Nb, Nb] and K_bi K_ii^-1 F_i [count, n_rhs, Nb] of the elements [first, first + count),
+        Nb = n_primary_nodes * fields, from the store of a closed condensed system"""
+        import torch
+        ci = self.cond_info
+        count = ci.n_elems - first if count is None else count
+        nb = ci.n_primary_nodes * self.n_fields
+        dev = torch.device("cuda", self.ctx.device)
+        W = torch.empty((max(count, 0), nb, nb), dtype=torch.float64, device=dev)
+        w = torch.empty((max(count, 0), self.n_rhs, nb), dtype=torch.float64, device=dev)
+        check(capi.load().l3k_asm_schur_updates(self._h, first, count, _ptr(W), _ptr(w)))
+        return W, w
