@@ -767,8 +767,8 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
  * l3k_asm_info_get: sizes, state, n_missing, the device pointers of the four arrays (valid as long as the object) and, on a
  *   closed system, the operator: solving is l3k_csr_diag / l3k_csr_pcg_solve* / l3k_csr_cheb_create on that handle, which the
  *   object owns (do not destroy it).
- * Static condensation on hexes is not part of this object (l3k_condense_*); on quads it is a mode of it (below).  Partitioned
- * assembly is not part of it. */
+ * Static condensation on hexes is not part of this object (l3k_condense_*); on quads it is a mode of it (below).  On a
+ * partitioned mesh the object is made by l3k_asm_create_dist (behind the halo section: the distributed CSR operator). */
 typedef struct l3k_asm l3k_asm;
 enum { L3K_ASM_NEW = 0, L3K_ASM_OPEN = 1, L3K_ASM_CLOSED = 2 };
 typedef struct
@@ -923,6 +923,82 @@ int     l3k_halo_timing_begin(l3k_halo* halo, int n_applies);
 int     l3k_halo_timing_get(l3k_halo* halo, int apply, double ms[3]);
 int     l3k_mf_apply_dist(l3k_mf* mf, l3k_halo* halo, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols,
                           double alpha, double beta);
+
+/* ---- the assembled and the condensed system on a partitioned mesh: the distributed CSR operator -------------------------------
+ * algsys::AssembledSystem in an MPI run of the reference (algsys/AssembledSystem.hpp: beginAssembly / assembleProblem /
+ * endAssembly on every rank, then Belos on the Tpetra matrix, solve/BelosSolvers.hpp:116-122).  SUB-ASSEMBLED FORM: every rank
+ * keeps the LOCAL matrix A_r of its own elements and sides over its local dofs [owned | ghost]; the global matrix
+ *     A = sum_r R_r^T A_r R_r             (R_r: global dofs -> the local dofs of rank r)
+ * is never formed and no matrix entry travels between ranks.  Tpetra exports the ghost rows of the matrix once, at endAssembly
+ * (fillComplete); here the ghost rows of y are export-added at every apply, exactly as l3k_mf_apply_dist does it
+ * (comm/ImportExport.hpp:295-372 import, :402-470 export; the schedule of algsys/MatrixFreeSystem.hpp:1020-1140).  Vectors of
+ * the operator hold OWNED rows only.
+ *
+ * l3k_csr_dist_create: the operator over a local l3k_csr `A` (n = n_owned + ghost dofs of the halo) -- any l3k_csr: the one of a
+ *   partitioned l3k_asm, or one over arrays the caller filled through l3k_assemble_global / l3k_condense_global on a partitioned
+ *   hex mesh.  Sorts the local rows once into three ascending int32 lists: INTERIOR (owned, every column < n_owned; an empty owned
+ *   row is interior), BORDER (owned, at least one ghost column), GHOST (row >= n_owned); an ordered compaction: the lists do not
+ *   depend on the order in which anything lands.  The lists depend on the graph only; values may be rewritten.  Owns the lists,
+ *   copies nothing else; A and the halo must outlive it.  -1, *out untouched: a null argument, a halo on another context than
+ *   the operator, A->n != n_owned + l3k_halo_n_ghost_dofs(halo).
+ * l3k_csr_dist_info_get: sizes, the three row counts, the device pointers of the lists and the local operator.
+ * l3k_csr_dist_apply: y <- alpha A x + beta y on the owned rows, x and y [ncols][ld] over the owned rows (collective):
+ *   pack and post the import || first half of the interior list; wait; border and ghost rows (ghost rows write the halo's export
+ *   buffer, every entry of it: no zeroing); post the export || second half of the interior list; wait; unpack-add into y.
+ *   Per row it is l3k_csr_apply's kernel on a vector split into its owned and ghost part: one writer per row, no floating-point
+ *   atomics, beta == 0: y is not read; more than four columns go in passes of four, two and one behind ONE exchange.  In a world of
+ *   one rank the result equals l3k_csr_apply's bit for bit.  A rank without neighbours has no exchange to hide and runs its interior
+ *   list in one launch; a rank that owns nothing (no row, no neighbour) returns 0.
+ *   l3k_halo_timing_begin / _get time its three groups of launches as they time those of l3k_mf_apply_dist.
+ * l3k_csr_dist_diag: the local diagonal over [owned | ghost], the ghost part export-added to the owners (collective), then
+ *   l3k_csr_diag's formula on the owned rows: d_diag [n_owned] the diagonal of A, d_minv [n_owned] = sign damping / max(|a_ii|,
+ *   threshold) and 0 on an EMPTY owned row (the frozen-row rule: the internal dofs of a condensed graph).  Either may be NULL, not
+ *   both.
+ * l3k_csr_dirichlet_dist: the rank-local step of DirichletBCAlgebraic::apply (bcs/DirichletBC.hpp:82-150) with an OWNER RULE, on
+ *   a local operator: d_mask [n] and d_bc_vals_local [ncols][ldg] are over the LOCAL dofs (the caller, or l3k_asm_end, imports the
+ *   ghost values), d_rhs [ncols][ldr] likewise.  A flagged owned row becomes the identity row with rhs = g; a flagged ghost row
+ *   becomes an all-zero row with rhs = 0 (the owner holds the 1); every other row, owned or ghost, gives rhs_i -= a_ij g_j over its
+ *   flagged columns in l3k_csr_dirichlet's fixed order and zeroes those entries.  Summed over the ranks this is the reference's
+ *   step on the global matrix.  -1, nothing written: a flagged OWNED row without a stored diagonal, n_owned outside [0, n],
+ *   l3k_csr_dirichlet's other refusals.  PRECONDITION, as on the matrix-free path: the flags of a ghost dof equal its owner's.
+ *
+ * l3k_asm_create_dist: l3k_asm_create (condensed == 0) or l3k_asm_create_condensed (!= 0) with their arguments and refusals,
+ *   except that ghost nodes are accepted; also refused (-1): a null halo, a halo on another context, a halo whose dofs_per_node
+ *   or ghost range differs from the mesh's, `condensed` on hexes.  l3k_asm_begin / _add_domain / _add_boundary serve it
+ *   unchanged: they are rank-local.  l3k_asm_create and l3k_asm_create_condensed keep refusing a partitioned mesh.
+ * l3k_asm_end on such a system is COLLECTIVE: d_dirichlet_vals [n_rhs][ldg] is over the OWNED dofs (ldg >= n_owned; NULL:
+ *   homogeneous, on every rank) and is imported to the ghost rows inside the call; the element elimination of a condensed system
+ *   is rank-local and unchanged; then l3k_csr_dirichlet_dist with the mesh's mask (same precondition; a mask on every rank or on
+ *   none), then the ghost rows of rhs are export-added into their owners' rows and set to 0, then the local l3k_csr and the
+ *   l3k_csr_dist are created (once; the object owns both).  l3k_asm_info keeps its layout; rhs [n_rhs][ldr]: the first n_owned
+ *   entries of a row are the owned right-hand side.
+ * l3k_asm_dist_info_get: n_owned, n_ghost and the distributed operator (NULL unless the system is closed).  -1 on a system
+ *   that is not partitioned.
+ * l3k_asm_recover on a partitioned condensed system (collective): x [n_rhs][ldx] over the LOCAL dofs, ldx >= n, with the owned
+ *   part filled; the call imports the ghost part itself, then writes the internal dofs (always owned). */
+typedef struct l3k_csr_dist l3k_csr_dist;
+typedef struct
+{
+    int64_t        n_owned, n_ghost;
+    int64_t        n_interior_rows, n_border_rows, n_ghost_rows;
+    const int32_t *d_interior_rows, *d_border_rows, *d_ghost_rows;
+    l3k_csr*       local;
+} l3k_csr_dist_info;
+typedef struct
+{
+    int64_t       n_owned, n_ghost;
+    l3k_csr_dist* dist; /* NULL unless state == L3K_ASM_CLOSED */
+} l3k_asm_dist_info;
+int l3k_csr_dist_create(l3k_csr* A, l3k_halo* halo, int64_t n_owned, l3k_csr_dist** out);
+int l3k_csr_dist_info_get(const l3k_csr_dist* D, l3k_csr_dist_info* out);
+int l3k_csr_dist_apply(l3k_csr_dist* D, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha, double beta);
+int l3k_csr_dist_diag(l3k_csr_dist* D, double* d_diag, double damping, double threshold, double* d_minv);
+int l3k_csr_dist_destroy(l3k_csr_dist* D);
+int l3k_csr_dirichlet_dist(l3k_csr* A, double* d_values, const uint8_t* d_mask, const double* d_bc_vals_local, size_t ldg,
+                           double* d_rhs, size_t ldr, int ncols, int64_t n_owned);
+int l3k_asm_create_dist(l3k_mesh* mesh, l3k_halo* halo, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes,
+                        int condensed, l3k_asm** out);
+int l3k_asm_dist_info_get(const l3k_asm* A, l3k_asm_dist_info* out);
 
 /* ---- host-side synthetic mesh + block partition --------------------------------------------------------------------
  * Stand-in for makeCubeMesh + convertMeshToOrder + partitionMesh + the ownership / import-export context

@@ -15,6 +15,8 @@
 //   l3k::SquareMesh              ~ makeSquareMesh(...) at an order, one rank              mesh/primitives/SquareMesh.hpp
 //   l3k::AssembledSystem         ~ algsys::AssembledSystem: beginAssembly / assembleProblem / endAssembly, hexes and quads
 //   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
+//   l3k::DistributedCsr          ~ ... of an MPI run: the ranks' local matrices applied as one (sub-assembled form)
+//       AssembledSystem(mesh, halo, ...) ~ algsys::AssembledSystem on one rank of a partitioned mesh
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
 //   l3k::computeIntegral / computeNormL2 ~ post/Integral.hpp:113-128, post/NormL2.hpp:31-62 (one rank)
 // Errors: the reference throws std::runtime_error from util::throwingAssert (util/Assertion.hpp:88-95); so does this
@@ -238,8 +240,9 @@ public:
                               v.send_nodes, v.ghost_offsets, &m_halo));
     }
     // With a transport table instead of RCCL: the host's own (e.g. MPI on device pointers), or the library's in-process
-    // transport for the threads of one process (InprocGroup below).  Not collective.
-    Halo(Context& ctx, const CubeMesh& mesh, int dofs_per_node, const l3k_halo_transport& transport, int rank, int world)
+    // transport for the threads of one process (InprocGroup above).  Not collective.  Mesh: CubeMesh, or SquareMesh (one part)
+    template < typename Mesh >
+    Halo(Context& ctx, const Mesh& mesh, int dofs_per_node, const l3k_halo_transport& transport, int rank, int world)
     {
         const auto& v = mesh.view();
         check(l3k_halo_create_transport(ctx.get(), &transport, rank, world, dofs_per_node, v.n_nbrs, v.nbr_rank, v.send_offsets,
@@ -588,11 +591,67 @@ public:
                 throw std::runtime_error{"Solver failed to converge"};
         return res;
     }
+    // the rank-local Dirichlet step with the owner rule on the local matrix of a partitioned system (l3k_csr_dirichlet_dist): mask,
+    // values and rhs over the LOCAL dofs [owned | ghost], ghost values imported by the caller; a flagged owned row becomes the
+    // identity row with rhs = g, a flagged ghost row an all-zero row with rhs = 0
+    void applyDirichletLocal(const uint8_t* d_mask, const double* d_bc_vals_local, size_t ldg, double* d_rhs, size_t ldr, int64_t n_owned,
+                             int ncols = 1) const
+    {
+        check(l3k_csr_dirichlet_dist(m_csr, m_values, d_mask, d_bc_vals_local, ldg, d_rhs, ldr, ncols, n_owned));
+    }
     l3k_csr* get() const { return m_csr; }
 
 private:
     l3k_csr* m_csr{};
     double*  m_values{};
+};
+
+// The assembled or condensed matrix of a partitioned mesh in front of the solver (l3k_csr_dist_*), in the SUB-ASSEMBLED form: every
+// rank keeps the matrix of its own elements over its local dofs [owned | ghost] (a CsrOperator, or the l3k_csr of a partitioned
+// AssembledSystem), the global matrix -- their sum -- is never formed, and the halo's exchanges run inside every apply: the Tpetra
+// matrix of an MPI run of the reference in front of Belos (solve/BelosSolvers.hpp:116-122).  Vectors hold the owned rows only.
+//   apply   ~ tpetra_crsmatrix_t::apply: import || interior rows, border and ghost rows, export || interior rows, unpack-add
+//   diag    ~ getLocalDiagCopy of the global matrix on the owned rows + NativeJacobiImpl::init; collective
+//   info    ~ n_owned, n_ghost, the three row counts and lists, the local l3k_csr
+// The local operator and the halo must outlive the object.
+class DistributedCsr
+{
+public:
+    DistributedCsr(const CsrOperator& local, const Halo& halo, int64_t n_owned) : m_owner{true}
+    {
+        check(l3k_csr_dist_create(local.get(), halo.get(), n_owned, &m_dist));
+    }
+    // a handle that belongs to somebody else (AssembledSystem::distributed)
+    explicit DistributedCsr(l3k_csr_dist* handle) : m_dist{handle}, m_owner{false} {}
+    DistributedCsr(const DistributedCsr&)            = delete;
+    DistributedCsr& operator=(const DistributedCsr&) = delete;
+    DistributedCsr(DistributedCsr&& o) noexcept : m_dist{o.m_dist}, m_owner{o.m_owner} { o.m_dist = nullptr; }
+    ~DistributedCsr()
+    {
+        if (m_owner)
+            l3k_csr_dist_destroy(m_dist);
+    }
+    l3k_csr_dist_info info() const
+    {
+        l3k_csr_dist_info i{};
+        check(l3k_csr_dist_info_get(m_dist, &i));
+        return i;
+    }
+    // Y <- alpha*A*X + beta*Y on the owned rows; beta == 0: Y is not read
+    void apply(const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols = 1, double alpha = 1., double beta = 0.) const
+    {
+        check(l3k_csr_dist_apply(m_dist, d_x, ldx, d_y, ldy, ncols, alpha, beta));
+    }
+    // the global diagonal on the owned rows and / or minv = sign(d) damping / max(|d|, threshold), 0 on an empty owned row
+    void diag(double* d_diag, double* d_minv, double damping = 1., double threshold = 0.) const
+    {
+        check(l3k_csr_dist_diag(m_dist, d_diag, damping, threshold, d_minv));
+    }
+    l3k_csr_dist* get() const { return m_dist; }
+
+private:
+    l3k_csr_dist* m_dist{};
+    bool          m_owner{};
 };
 
 // The CSR sparsity graph of a mesh over its local dofs, built on the device: computeLocalGraph in front of makeSparsityGraph
@@ -651,6 +710,16 @@ public:
         check((condensation == Condensation::ElementBoundary ? l3k_asm_create_condensed : l3k_asm_create)(
             mesh.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), n_rhs, workspace_bytes, &m_asm));
     }
+    // One rank of a partitioned mesh (l3k_asm_create_dist): the arrays hold the local matrix over the local dofs [owned | ghost];
+    // beginAssembly and assembleProblem are rank-local, endAssembly is collective and takes d_dirichlet_vals over the OWNED dofs
+    // (ldg >= n_owned), distributed() is then the operator for the solver and the first n_owned entries of a row of info().d_rhs
+    // the owned right-hand side; recover is collective and takes d_x over the local dofs with the owned part filled
+    AssembledSystem(const DeviceMesh& mesh, const Halo& halo, std::span< const int > field_inds = {}, int n_rhs = 1,
+                    size_t workspace_bytes = 0, Condensation condensation = Condensation::None)
+    {
+        check(l3k_asm_create_dist(mesh.get(), halo.get(), int(field_inds.size()), field_inds.empty() ? nullptr : field_inds.data(), n_rhs,
+                                  workspace_bytes, condensation == Condensation::ElementBoundary ? 1 : 0, &m_asm));
+    }
     AssembledSystem(const AssembledSystem&)            = delete;
     AssembledSystem& operator=(const AssembledSystem&) = delete;
     AssembledSystem(AssembledSystem&& o) noexcept : m_asm{o.m_asm} { o.m_asm = nullptr; }
@@ -702,6 +771,21 @@ public:
         l3k_asm_cond_info i{};
         check(l3k_asm_cond_info_get(m_asm, &i));
         return i;
+    }
+    // a partitioned system: n_owned, n_ghost and (closed) the l3k_csr_dist handle
+    l3k_asm_dist_info distInfo() const
+    {
+        l3k_asm_dist_info i{};
+        check(l3k_asm_dist_info_get(m_asm, &i));
+        return i;
+    }
+    // the operator of a closed partitioned system (the system owns the handle and must outlive the result)
+    DistributedCsr distributed() const
+    {
+        const l3k_asm_dist_info i = distInfo();
+        if (!i.dist)
+            throw std::runtime_error{"AssembledSystem::distributed: the system is not closed (endAssembly)"};
+        return DistributedCsr{i.dist};
     }
     l3k_asm* get() const { return m_asm; }
 

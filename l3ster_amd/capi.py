@@ -86,6 +86,18 @@ class AsmInfo(C.Structure):
                 ("d_rhs", C.c_void_p), ("csr", C.c_void_p)]
 
 
+class CsrDistInfo(C.Structure):
+    """l3k_csr_dist_info: the sizes of a distributed CSR operator, its three row lists and its local operator"""
+    _fields_ = [("n_owned", C.c_int64), ("n_ghost", C.c_int64), ("n_interior_rows", C.c_int64), ("n_border_rows", C.c_int64),
+                ("n_ghost_rows", C.c_int64), ("d_interior_rows", C.c_void_p), ("d_border_rows", C.c_void_p),
+                ("d_ghost_rows", C.c_void_p), ("local", C.c_void_p)]
+
+
+class AsmDistInfo(C.Structure):
+    """l3k_asm_dist_info: the sizes of a partitioned assembled system and, once it is closed, its distributed operator"""
+    _fields_ = [("n_owned", C.c_int64), ("n_ghost", C.c_int64), ("dist", C.c_void_p)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -282,6 +294,14 @@ SIGNATURES = {
     "l3k_asm_cond_info_get": (C.c_int, [_vp, C.POINTER(AsmCondInfo)]),
     "l3k_asm_recover": (C.c_int, [_vp, _vp, C.c_size_t]),
     "l3k_asm_schur_updates": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "l3k_csr_dist_create": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(_vp)]),
+    "l3k_csr_dist_info_get": (C.c_int, [_vp, C.POINTER(CsrDistInfo)]),
+    "l3k_csr_dist_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),
+    "l3k_csr_dist_diag": (C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
+    "l3k_csr_dist_destroy": (C.c_int, [_vp]),
+    "l3k_csr_dirichlet_dist": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int64]),
+    "l3k_asm_create_dist": (C.c_int, [_vp, _vp, C.c_int, c_int_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(_vp)]),
+    "l3k_asm_dist_info_get": (C.c_int, [_vp, C.POINTER(AsmDistInfo)]),
     "l3k_cube_partition_create": (C.c_int, [c_int_p, C.c_int, c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_square_mesh_create": (C.c_int, [c_int_p, C.c_int, C.c_double, C.POINTER(_vp)]),
     "l3k_hostmesh_destroy": (C.c_int, [_vp]),

@@ -10,6 +10,10 @@
 // A system made by l3k_asm_create_condensed (quads) eliminates the element-internal dofs: the same pipeline, with the split kernel
 // of device/quad_condense.hpp in the scatter's place, a per-element store of the internal rows that l3k_asm_begin zeroes and
 // l3k_asm_end factors, and l3k_asm_recover / l3k_asm_schur_updates on the factored store.
+//
+// A system made by l3k_asm_create_dist lives on one rank's part of a partitioned mesh: the same arrays over the local dofs
+// [owned | ghost], filled by the same rank-local calls; l3k_asm_end is then collective and hands out a distributed operator
+// (api_csr_dist.hip; DESIGN.md 4.20: the sub-assembled form).
 #include "objects.hpp"
 
 #include "device/quad_condense.hpp"
@@ -29,6 +33,11 @@ struct l3k_asm
     DevBuf< double >   values, rhs, zero_vals;
     SubBatchPipe       pipe;
     l3k_csr*           csr = nullptr;
+    // a partitioned system (l3k_asm_create_dist): the exchange, the operator over [owned | ghost], the prescribed values over the local dofs
+    l3k_halo*          halo    = nullptr;
+    l3k_csr_dist*      dist    = nullptr;
+    int64_t            n_owned = 0;
+    DevBuf< double >   g_local;
     // static condensation: the store [n_elems][Nis][LD] of the internal rows [K_ii | K_ib | F_i], LD = Nis + Nbs + n_rhs
     bool               condensed = false, eliminated = false;
     int                Us = 0, Nis = 0, Nbs = 0, LD = 0, team = l3k::dev::cond_threads;
@@ -38,6 +47,8 @@ struct l3k_asm
     DevBuf< unsigned > d_nfail;
     ~l3k_asm()
     {
+        if (dist)
+            (void)l3k_csr_dist_destroy(dist);
         if (csr)
             (void)l3k_csr_destroy(csr);
     }
@@ -314,6 +325,44 @@ int eliminateStore(l3k_asm* A)
     }
     return 0;
 }
+// The collective tail of l3k_asm_end on a partitioned system, behind the rank-local elimination and the local operator: the
+// prescribed values imported to the ghost rows, the Dirichlet step with the owner rule, the ghost rows of rhs export-added into
+// their owners' rows and zeroed, the distributed operator (created once: its row lists depend on the graph only)
+int endDistributed(l3k_asm* A, const double* d_vals_owned, size_t ldg)
+{
+    hipStream_t   s = A->ctx->stream;
+    const int64_t n = A->n, no = A->n_owned, ng = n - no;
+    if (A->mesh->dirichlet.ptr && n > 0)
+    {
+        if (!A->g_local.ptr)
+            if (int rc = A->g_local.alloc(size_t(A->n_rhs) * size_t(n)))
+                return rc;
+        L3K_HIP(hipMemsetAsync(A->g_local.ptr, 0, sizeof(double) * A->g_local.n, s));
+        if (d_vals_owned) // (NULL: homogeneous on every rank -- nothing to import)
+        {
+            if (no > 0)
+                L3K_HIP(hipMemcpy2DAsync(A->g_local.ptr, sizeof(double) * size_t(n), d_vals_owned, sizeof(double) * ldg, sizeof(double) * size_t(no),
+                                         size_t(A->n_rhs), hipMemcpyDeviceToDevice, s));
+            if (int rc = l3k_halo_import(A->halo, A->g_local.ptr, size_t(n), A->n_rhs, A->g_local.ptr + no, size_t(n)))
+                return rc;
+        }
+        if (int rc = l3k_csr_dirichlet_dist(A->csr, A->values.ptr, A->mesh->dirichlet.ptr, A->g_local.ptr, size_t(n), A->rhs.ptr, A->ldr,
+                                            A->n_rhs, no))
+            return rc;
+    }
+    if (n > 0)
+    {
+        if (int rc = l3k_halo_export_add(A->halo, A->rhs.ptr + no, A->ldr, A->n_rhs, A->rhs.ptr, A->ldr))
+            return rc;
+        if (ng > 0)
+            L3K_HIP(hipMemset2DAsync(A->rhs.ptr + no, sizeof(double) * A->ldr, 0, sizeof(double) * size_t(ng), size_t(A->n_rhs), s));
+    }
+    if (!A->dist)
+        if (int rc = l3k_csr_dist_create(A->csr, A->halo, no, &A->dist))
+            return rc;
+    A->state = L3K_ASM_CLOSED;
+    return 0;
+}
 } // namespace
 
 extern "C" {
@@ -382,10 +431,11 @@ int l3k_asm_side_systems(l3k_bnd* term, int64_t first, int64_t count, double* d_
 namespace
 {
 // l3k_asm_create (`condensed` = false: the full graph) and l3k_asm_create_condensed (quads: the graph of the primary nodes and the store)
+// and l3k_asm_create_dist (`dist`: with the halo of a partitioned mesh, whose ghost nodes are then accepted)
 int createSystem(const char* what, bool condensed, l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes,
-                 l3k_asm** out)
+                 l3k_asm** out, bool dist = false, l3k_halo* halo = nullptr)
 {
-    if (!mesh || !out)
+    if (!mesh || !out || (dist && !halo))
     {
         setError("%s: null argument", what);
         return -1;
@@ -401,7 +451,22 @@ int createSystem(const char* what, bool condensed, l3k_mesh* mesh, int n_fields,
         setError("%s: n_rhs = %d; it is at least 1", what, n_rhs);
         return -1;
     }
-    if (mesh->n_ghost_nodes > 0)
+    if (dist)
+    {
+        if (l3k::halo::context(halo) != mesh->ctx)
+        {
+            setError("%s: the halo and the mesh belong to different contexts", what);
+            return -1;
+        }
+        if (l3k::halo::dofsPerNode(halo) != mesh->dofs_per_node || l3k_halo_n_ghost_dofs(halo) != mesh->n_ghost_nodes * mesh->dofs_per_node)
+        {
+            setError("%s: the halo (%d dofs per node, %lld ghost dofs) does not match the mesh (%d dofs per node, %lld ghost dofs)", what,
+                     l3k::halo::dofsPerNode(halo), (long long)l3k_halo_n_ghost_dofs(halo), mesh->dofs_per_node,
+                     (long long)(mesh->n_ghost_nodes * mesh->dofs_per_node));
+            return -1;
+        }
+    }
+    else if (mesh->n_ghost_nodes > 0)
     {
         setError("%s: a partitioned mesh (%lld ghost nodes): the assembled system and its CSR operator are single-rank", what,
                  (long long)mesh->n_ghost_nodes);
@@ -413,6 +478,26 @@ int createSystem(const char* what, bool condensed, l3k_mesh* mesh, int n_fields,
         return -1;
     }
     L3K_HIP(hipSetDevice(mesh->ctx->device));
+    if (dist && mesh->n_elems == 0 && mesh->nLocalDofs() == 0)
+    {
+        // a rank that owns nothing: the system of no rows (row_ptr = {0}), so that the rank takes part in every call and returns
+        auto A             = std::make_unique< l3k_asm >();
+        A->ctx             = mesh->ctx;
+        A->mesh            = mesh;
+        A->n_rhs           = n_rhs;
+        A->halo            = halo;
+        A->workspace_bytes = workspace_bytes;
+        A->condensed       = condensed;
+        const int U        = n_fields ? n_fields : mesh->dofs_per_node;
+        for (int u = 0; u < U; ++u)
+            A->field_inds.push_back(field_inds ? field_inds[u] : u);
+        if (int rc = A->row_ptr.alloc(1))
+            return rc;
+        L3K_HIP(hipMemsetAsync(A->row_ptr.ptr, 0, sizeof(int64_t), mesh->ctx->stream));
+        L3K_HIP(hipStreamSynchronize(mesh->ctx->stream));
+        *out = A.release();
+        return 0;
+    }
     const int          n1d = mesh->order + 1, Np = 4 * mesh->order;
     DevBuf< uint32_t > prim; // the primary node rows: the elements of the condensed graph (alive until the fill has run)
     l3k_graph*         g = nullptr;
@@ -438,6 +523,8 @@ int createSystem(const char* what, bool condensed, l3k_mesh* mesh, int n_fields,
     A->ctx             = mesh->ctx;
     A->mesh            = mesh;
     A->n_rhs           = n_rhs;
+    A->halo            = dist ? halo : nullptr;
+    A->n_owned         = mesh->nOwnedDofs();
     A->workspace_bytes = workspace_bytes;
     A->n               = gi.n;
     A->nnz             = gi.nnz;
@@ -498,6 +585,11 @@ int l3k_asm_create(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rh
 int l3k_asm_create_condensed(l3k_mesh* mesh, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, l3k_asm** out)
 {
     return createSystem("l3k_asm_create_condensed", true, mesh, n_fields, field_inds, n_rhs, workspace_bytes, out);
+}
+int l3k_asm_create_dist(l3k_mesh* mesh, l3k_halo* halo, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes, int condensed,
+                        l3k_asm** out)
+{
+    return createSystem("l3k_asm_create_dist", condensed != 0, mesh, n_fields, field_inds, n_rhs, workspace_bytes, out, true, halo);
 }
 
 int l3k_asm_begin(l3k_asm* A)
@@ -632,7 +724,13 @@ int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg)
         setError("l3k_asm_end: the system is not open (l3k_asm_begin opens it)");
         return -1;
     }
-    if (d_dirichlet_vals && ldg < size_t(A->n))
+    if (A->halo && d_dirichlet_vals && ldg < size_t(A->n_owned))
+    {
+        setError("l3k_asm_end: leading dimension of the prescribed values (%zu) smaller than the number of owned dofs (%lld)", ldg,
+                 (long long)A->n_owned);
+        return -1;
+    }
+    if (!A->halo && d_dirichlet_vals && ldg < size_t(A->n))
     {
         setError("l3k_asm_end: leading dimension of the prescribed values (%zu) smaller than the number of dofs (%lld)", ldg, (long long)A->n);
         return -1;
@@ -646,6 +744,8 @@ int l3k_asm_end(l3k_asm* A, const double* d_dirichlet_vals, size_t ldg)
     if (!A->csr) // (the operator keeps the pointers of the object's arrays: created once, valid for every later assembly)
         if (int rc = l3k_csr_create(A->ctx, A->n, A->row_ptr.ptr, A->col_ind.ptr, A->values.ptr, 0, &A->csr))
             return rc;
+    if (A->halo)
+        return endDistributed(A, d_dirichlet_vals, ldg);
     if (A->mesh->dirichlet.ptr && A->n > 0)
     {
         const double* g = d_dirichlet_vals;
@@ -679,6 +779,22 @@ int l3k_asm_info_get(const l3k_asm* A, l3k_asm_info* out)
     return 0;
 }
 
+int l3k_asm_dist_info_get(const l3k_asm* A, l3k_asm_dist_info* out)
+{
+    if (!A || !out)
+    {
+        setError("l3k_asm_dist_info_get: null argument");
+        return -1;
+    }
+    if (!A->halo)
+    {
+        setError("l3k_asm_dist_info_get: the system is not partitioned (l3k_asm_create_dist makes one that is)");
+        return -1;
+    }
+    *out = {A->n_owned, A->n - A->n_owned, A->state == L3K_ASM_CLOSED ? A->dist : nullptr};
+    return 0;
+}
+
 int l3k_asm_cond_info_get(const l3k_asm* A, l3k_asm_cond_info* out)
 {
     if (!A || !out)
@@ -696,22 +812,27 @@ int l3k_asm_cond_info_get(const l3k_asm* A, l3k_asm_cond_info* out)
 int l3k_asm_recover(l3k_asm* A, double* d_x, size_t ldx)
 {
     const char* const what = "l3k_asm_recover";
-    if (!A || !d_x)
+    if (!A || (!d_x && !(A->halo && A->n == 0)))
     {
         setError("%s: null argument", what);
         return -1;
     }
     if (int rc = checkFactoredStore(A, what))
         return rc;
+    if (A->halo && A->n == 0) // (a rank that owns nothing)
+        return 0;
     if (ldx < size_t(A->n))
     {
         setError("%s: leading dimension of x (%zu) smaller than the number of dofs (%lld)", what, ldx, (long long)A->n);
         return -1;
     }
     const int64_t ne = A->mesh->n_elems;
+    L3K_HIP(hipSetDevice(A->ctx->device));
+    if (A->halo) // (collective: the primary dofs of ghost nodes come from their owners; internal dofs are always owned)
+        if (int rc = l3k_halo_import(A->halo, d_x, ldx, A->n_rhs, d_x + A->n_owned, ldx))
+            return rc;
     if (A->Nis == 0 || ne == 0)
         return 0;
-    L3K_HIP(hipSetDevice(A->ctx->device));
     l3k::dev::QuadCondArgs a = condArgs(A, 0, ne);
     a.x                      = d_x;
     a.ldx                    = ldx;

@@ -1,41 +1,12 @@
 // api_csr.hip -- the device CSR operator of libl3k.so (include/l3k.h: l3k_csr_*): what the assembled and the condensed system hand to
 // the solver layer.  The kernels are in device/csr.hpp; the solves on such an operator are in api_solver.hip.
-#include "device/csr.hpp"
+#include "csr_launch.hpp"
 
 namespace
 {
 using namespace l3k::csr;
 using l3k::red::cg_blocks;
 
-// blocks of a launch in which groups of `lanes` lanes walk n rows: at most cg_blocks, so that the partials of a reducing kernel
-// fit the context's workspace
-int csrGrid(int64_t n, int lanes)
-{
-    const int64_t g = (n * lanes + cg_threads - 1) / cg_threads;
-    return int(g < 1 ? 1 : (g > cg_blocks ? cg_blocks : g));
-}
-// f(std::integral_constant< int, L >) for the operator's lanes per row
-template < typename F >
-int withLanes(int lanes, F&& f)
-{
-    switch (lanes)
-    {
-    case 4: return f(std::integral_constant< int, 4 >{});
-    case 16: return f(std::integral_constant< int, 16 >{});
-    default: return f(std::integral_constant< int, 64 >{});
-    }
-}
-// The automatic choice from the mean length of the non-empty rows.  The cut points 8 and 64 are the starting values, NOT measured:
-// DESIGN.md 4.12 says what tools/bench_csr.py has to show before they move
-int chooseLanes(double mean_row_len)
-{
-    return mean_row_len <= 8. ? 4 : mean_row_len <= 64. ? 16 : 64;
-}
-// do the vectors [p, p + span) and [q, q + span2) share memory?
-bool overlap(const double* p, size_t span, const double* q, size_t span2)
-{
-    return p < q + span2 && q < p + span;
-}
 // NC columns of an apply
 template < int L, int NC >
 void launchApply(const l3k_csr* A, const double* d_x, size_t ldx, double* d_y, size_t ldy, double alpha, double beta)

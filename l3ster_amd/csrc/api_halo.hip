@@ -269,6 +269,61 @@ int unpackAll(l3k_halo* h, double* d_owned, size_t ld, int ncols)
 }
 } // namespace
 
+namespace l3k::halo
+{
+l3k_ctx* context(const l3k_halo* h)
+{
+    return h->ctx;
+}
+int dofsPerNode(const l3k_halo* h)
+{
+    return h->dpn;
+}
+bool hasNeighbours(const l3k_halo* h)
+{
+    return !h->nbrs.empty();
+}
+int buffers(l3k_halo* h, int ncols, double** xg, double** yg, size_t* ldg)
+{
+    if (int rc = ensureBuffers(h, ncols))
+        return rc;
+    *xg  = h->xg.ptr;
+    *yg  = h->yg.ptr;
+    *ldg = size_t(std::max< int64_t >(h->n_ghost_dofs, 1));
+    return 0;
+}
+int beginImport(l3k_halo* h, const double* d_owned, size_t ld, int ncols, double* d_ghost, size_t ldg)
+{
+    if (int rc = ensureBuffers(h, ncols))
+        return rc;
+    if (int rc = packAll(h, d_owned, ld, ncols))
+        return rc;
+    L3K_HIP(hipEventRecord(h->ev_main, h->ctx->stream));
+    return postImport(h, ncols, d_ghost, ldg, h->ev_main, h->ev_import);
+}
+int waitImport(l3k_halo* h)
+{
+    L3K_HIP(hipStreamWaitEvent(h->ctx->stream, h->ev_import, 0));
+    return 0;
+}
+int beginExport(l3k_halo* h, int ncols, const double* d_ghost, size_t ldg)
+{
+    if (int rc = ensureBuffers(h, ncols))
+        return rc;
+    L3K_HIP(hipEventRecord(h->ev_main, h->ctx->stream));
+    return postExport(h, ncols, d_ghost, ldg, h->ev_main, h->ev_export);
+}
+int endExport(l3k_halo* h, double* d_owned, size_t ld, int ncols)
+{
+    L3K_HIP(hipStreamWaitEvent(h->ctx->stream, h->ev_export, 0));
+    return unpackAll(h, d_owned, ld, ncols);
+}
+hipEvent_t* timingSlot(l3k_halo* h)
+{
+    return h->timing_n < h->timing_cap ? &h->timing[size_t(6) * h->timing_n++] : nullptr;
+}
+} // namespace l3k::halo
+
 extern "C" {
 int l3k_halo_unique_id(char* id128)
 {

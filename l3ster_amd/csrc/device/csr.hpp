@@ -31,8 +31,8 @@ __device__ __forceinline__ void report(unsigned long long* flag, int64_t row, un
 constexpr int flag_words = 4;
 
 // first pass of the validation: row_ptr alone (nothing is read through it), and the row statistics of l3k_csr_info
-__global__ __launch_bounds__(cg_threads) void csrCheckRowsKernel(const int64_t* __restrict__ row_ptr, int64_t n,
-                                                                 unsigned long long* __restrict__ flag)
+static __global__ __launch_bounds__(cg_threads) void csrCheckRowsKernel(const int64_t* __restrict__ row_ptr, int64_t n,
+                                                                        unsigned long long* __restrict__ flag)
 {
     const int64_t t = int64_t(blockIdx.x) * cg_threads + threadIdx.x;
     if (t == 0)
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(cg_threads) void csrCheckRowsKernel(const int64_t* 
 }
 // second pass, on the same stream: does nothing unless row_ptr passed -- only then is every k in [row_ptr[i], row_ptr[i + 1]) an
 // index into col_ind.  16 lanes walk a row
-__global__ __launch_bounds__(cg_threads) void csrCheckColsKernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col_ind,
-                                                                 int64_t n, unsigned long long* __restrict__ flag)
+static __global__ __launch_bounds__(cg_threads) void csrCheckColsKernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col_ind,
+                                                                        int64_t n, unsigned long long* __restrict__ flag)
 {
     constexpr int L = 16;
     if (*static_cast< volatile unsigned long long* >(flag) != no_offence)
@@ -172,9 +172,9 @@ __device__ __forceinline__ int64_t findColumn(const int32_t* __restrict__ col_in
 }
 // diag[i] = a_ii (0 where none is stored); minv[i] = sign(a_ii) damping / max(|a_ii|, threshold) as jacobiInverseKernel has it on
 // every non-empty row and 0 on an empty one: the PCG freezes such a row.  Either output may be nullptr
-__global__ __launch_bounds__(cg_threads) void csrDiagKernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col_ind,
-                                                            const double* __restrict__ values, int64_t n, double damping,
-                                                            double threshold, double* __restrict__ diag, double* __restrict__ minv)
+static __global__ __launch_bounds__(cg_threads) void csrDiagKernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col_ind,
+                                                                   const double* __restrict__ values, int64_t n, double damping,
+                                                                   double threshold, double* __restrict__ diag, double* __restrict__ minv)
 {
     for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
     {
@@ -190,10 +190,10 @@ __global__ __launch_bounds__(cg_threads) void csrDiagKernel(const int64_t* __res
 
 // l3k_csr_dirichlet, first kernel: the smallest masked row without a stored diagonal, if any (nothing is written before the
 // host has seen the answer)
-__global__ __launch_bounds__(cg_threads) void csrDirichletCheckKernel(const int64_t* __restrict__ row_ptr,
-                                                                      const int32_t* __restrict__ col_ind, int64_t n,
-                                                                      const uint8_t* __restrict__ mask,
-                                                                      unsigned long long* __restrict__ flag)
+static __global__ __launch_bounds__(cg_threads) void csrDirichletCheckKernel(const int64_t* __restrict__ row_ptr,
+                                                                             const int32_t* __restrict__ col_ind, int64_t n,
+                                                                             const uint8_t* __restrict__ mask,
+                                                                             unsigned long long* __restrict__ flag)
 {
     for (int64_t i = int64_t(blockIdx.x) * cg_threads + threadIdx.x; i < n; i += int64_t(gridDim.x) * cg_threads)
         if (mask[i] && findColumn(col_ind, row_ptr[i], row_ptr[i + 1], i) < 0)

@@ -446,6 +446,27 @@ struct l3k_csr
     DevBuf< unsigned long long > flag; // the word the checking kernels report through (validation, l3k_csr_dirichlet)
 };
 
+// api_halo.hip: the steps of an overlapped exchange, for the operators that live outside that file (api_csr_dist.hip: the
+// schedule of l3k_mf_apply_dist around row launches).  All of them queue work and return; 0 or the error code with the message set
+namespace l3k::halo
+{
+l3k_ctx* context(const l3k_halo* h);
+int      dofsPerNode(const l3k_halo* h);
+bool     hasNeighbours(const l3k_halo* h);
+// the halo's own ghost buffers for `ncols` columns: xg (import target) and yg (export source), [ncols][ldg], ldg >= 1
+int buffers(l3k_halo* h, int ncols, double** xg, double** yg, size_t* ldg);
+// pack the owned rows the neighbours read and post the import into ghost [ncols][ldg] behind the work queued so far
+int beginImport(l3k_halo* h, const double* d_owned, size_t ld, int ncols, double* d_ghost, size_t ldg);
+// the context's stream waits for the posted import
+int waitImport(l3k_halo* h);
+// post the export of ghost [ncols][ldg] behind the work queued so far
+int beginExport(l3k_halo* h, int ncols, const double* d_ghost, size_t ldg);
+// the context's stream waits for the posted export, then the received rows are added into d_owned (neighbour list order)
+int endExport(l3k_halo* h, double* d_owned, size_t ld, int ncols);
+// the six events of the next timed apply (l3k_halo_timing_begin), or nullptr when none is left
+hipEvent_t* timingSlot(l3k_halo* h);
+} // namespace l3k::halo
+
 // a boundary equation kernel on a list of element sides (assembleProblem(kernel, boundary_ids) of the reference)
 struct l3k_bnd : KernelTerm
 {

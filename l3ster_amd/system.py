@@ -1276,6 +1276,23 @@ class CsrOperator:
         check(capi.load().l3k_csr_dirichlet(self._h, _ptr(self.values), _ptr(mask), _ptr(g), ldg, _ptr(r), ldr, nc))
         return rhs
 
+    def dirichlet_local(self, mask, bc_vals_local, rhs, n_owned):
+        """The rank-local Dirichlet step with the owner rule on the local matrix of a partitioned system, in place
+        (l3k_csr_dirichlet_dist): the operator is over the local dofs [owned | ghost], the first n_owned rows are owned; mask uint8
+        [n], bc_vals_local and rhs (ncols, ld) or 1-D over the LOCAL dofs (ghost values imported by the caller).  A flagged owned row
+        becomes the identity row with rhs = g, a flagged ghost row an all-zero row with rhs = 0.  DistributedCsrOperator(self, halo)
+        then applies the ranks' matrices as one; the ghost rows of rhs still have to be export-added into their owners' rows."""
+        import torch
+        if mask.dtype != torch.uint8 or mask.numel() != self.n or not mask.is_contiguous():
+            raise L3KError("mask must be a contiguous uint8 tensor over the n rows")
+        g, r = (bc_vals_local[None, :], rhs[None, :]) if rhs.dim() == 1 else (bc_vals_local, rhs)
+        nc, ldg = MatrixFreeSystem._cols(g)
+        nc2, ldr = MatrixFreeSystem._cols(r)
+        if nc != nc2 or g.shape[1] < self.n or r.shape[1] < self.n:
+            raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
+        check(capi.load().l3k_csr_dirichlet_dist(self._h, _ptr(self.values), _ptr(mask), _ptr(g), ldg, _ptr(r), ldr, nc, int(n_owned)))
+        return rhs
+
 
 class _AssembledOperator(CsrOperator):
     """The CsrOperator of a closed AssembledSystem: the l3k_csr handle belongs to the system (which is kept alive here), the
@@ -1291,31 +1308,143 @@ class _AssembledOperator(CsrOperator):
         self._h = None
 
 
+class DistributedCsrOperator:
+    """The assembled or condensed matrix of a partitioned mesh in front of the solver (l3k_csr_dist_*), in the sub-assembled form:
+    `local` is this rank's CsrOperator over its local dofs [owned | ghost] -- the matrix of its own elements -- and the global
+    matrix, the sum of the ranks' local ones, is never formed; vectors hold the owned rows only and the exchanges of `halo` (a
+    distributed.NativeHalo) run inside every apply.  AssembledSystem(..., halo=...).end() returns one; it can also be built from any
+    CsrOperator over local dofs (arrays filled by assemble_global / condense_global on a partitioned hex mesh, after
+    dirichlet_local) plus the halo.  n = n_owned_dofs: the owned dofs.  solve.pcg_distributed takes it as its `op` (with minv from
+    jacobi_inverse, and with precond=dict(...) for Chebyshev); it offers no energy= keyword, so the loop takes <p, A p> from
+    l3k_cg_dot_pap.  apply, diag and jacobi_inverse are collective.  Applies are bitwise reproducible."""
+
+    def __init__(self, local, halo, n_owned=None, _handle=None):
+        lib = capi.load()
+        self.local, self.halo, self.ctx = local, halo, local.ctx
+        self.n_ghost = int(lib.l3k_halo_n_ghost_dofs(halo._h))
+        self.n = self.n_owned_dofs = local.n - self.n_ghost if n_owned is None else int(n_owned)
+        self._own = _handle is None
+        self._h = C.c_void_p(_handle)
+        if self._own:
+            check(lib.l3k_csr_dist_create(local._h, halo._h, self.n, C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and capi is not None:
+            if self._own:
+                capi.load().l3k_csr_dist_destroy(self._h)
+            self._h = None
+
+    def _rows(self, ptr, count):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if count == 0:
+            return torch.empty(0, dtype=torch.int32, device=dev)
+
+        class _Mem:
+            pass
+        m = _Mem()
+        m.owner = self
+        m.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(ptr), False), "version": 2, "strides": None}
+        return torch.as_tensor(m, device=dev)
+
+    @property
+    def info(self):
+        """n_owned, n_ghost, n_interior_rows, n_border_rows, n_ghost_rows and the three ascending row lists interior_rows,
+        border_rows, ghost_rows as int32 device tensors (views of the operator's lists: l3k_csr_dist_info)"""
+        import types
+        i = capi.CsrDistInfo()
+        check(capi.load().l3k_csr_dist_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(n_owned=i.n_owned, n_ghost=i.n_ghost, n_interior_rows=i.n_interior_rows,
+                                     n_border_rows=i.n_border_rows, n_ghost_rows=i.n_ghost_rows,
+                                     interior_rows=self._rows(i.d_interior_rows, i.n_interior_rows),
+                                     border_rows=self._rows(i.d_border_rows, i.n_border_rows),
+                                     ghost_rows=self._rows(i.d_ghost_rows, i.n_ghost_rows))
+
+    def apply(self, X, Y, alpha=1.0, beta=0.0):
+        """Y <- alpha A X + beta Y on the owned rows; X, Y: (ncols, ld) multivectors or 1-D vectors over the owned rows
+        (l3k_csr_dist_apply; collective)"""
+        if X.dim() == 1 and Y.dim() == 1:
+            X, Y2 = X[None, :], Y[None, :]
+        else:
+            Y2 = Y
+        nc, ldx = MatrixFreeSystem._cols(X)
+        nc2, ldy = MatrixFreeSystem._cols(Y2)
+        if nc != nc2 or X.shape[1] < self.n or Y2.shape[1] < self.n:
+            raise L3KError("X and Y must have the same number of columns and at least n_owned rows")
+        check(capi.load().l3k_csr_dist_apply(self._h, _ptr(X), ldx, _ptr(Y2), ldy, nc, alpha, beta))
+        return Y
+
+    def _diag(self, want_diag, want_minv, damping, threshold):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        out = [torch.empty(self.n, dtype=torch.float64, device=dev) if w else None for w in (want_diag, want_minv)]
+        check(capi.load().l3k_csr_dist_diag(self._h, _ptr(out[0]), float(damping), float(threshold), _ptr(out[1])))
+        return out
+
+    def diag(self):
+        """The diagonal of the global matrix on the owned rows (l3k_csr_dist_diag; collective)"""
+        return self._diag(True, False, 1.0, 0.0)[0]
+
+    def jacobi_inverse(self, damping=1.0, threshold=0.0):
+        """sign(a_ii) damping / max(|a_ii|, threshold) of the global diagonal on the owned rows, 0 on the empty ones, which the PCG
+        then leaves alone (l3k_csr_dist_diag; collective)"""
+        return self._diag(False, True, damping, threshold)[1]
+
+    def import_ghosts(self, V):
+        """comm::Import of a multivector (ncols, n_owned): its (ncols, max(n_ghost, 1)) ghost rows (l3k_halo_import)"""
+        import torch
+        ng = max(self.n_ghost, 1)
+        ghost = torch.zeros((V.shape[0], ng), dtype=torch.float64, device=V.device)
+        check(capi.load().l3k_halo_import(self.halo._h, _ptr(V), V.stride(0), V.shape[0], _ptr(ghost), ng))
+        return ghost
+
+    def export_add(self, ghost, owned):
+        """comm::Export: every ghost row added into its owner's row of `owned` (l3k_halo_export_add)"""
+        if ghost.numel() == 0:  # (a rank without ghosts still takes part; the halo takes no NULL vector)
+            import torch
+            ghost = torch.zeros((owned.shape[0], 1), dtype=torch.float64, device=owned.device)
+        check(capi.load().l3k_halo_export_add(self.halo._h, _ptr(ghost), ghost.stride(0), owned.shape[0], _ptr(owned), owned.stride(0)))
+        return owned
+
+
 class AssembledSystem:
     """algsys::AssembledSystem for one rank, on hexes and on quads (l3k_asm_*): begin() / add(term) / end() are beginAssembly /
     assembleProblem(domain or boundary kernel) / endAssembly.  The object owns the CSR arrays of the full sparsity graph of
     field_inds (strictly ascending; None = all dofs of the node: the union of the terms' dofs), the right-hand sides
     [n_rhs, n] and, on quads, the sub-batch workspace (workspace_bytes, 0 = 1 GiB; hexes use the terms' own pipelines with that size);
     row_ptr, col_ind, values and rhs are torch views of them, not copies, made on access.  end() applies the mesh's Dirichlet mask with the prescribed values and returns a CsrOperator over the
-    same arrays, which solve.pcg and solve.ChebyshevPreconditioner take.  A partitioned mesh is refused.
+    same arrays, which solve.pcg and solve.ChebyshevPreconditioner take.  Without a halo a partitioned mesh is refused.
 
     condensation="element_boundary" (quads; CondensationPolicy::ElementBoundary of the reference, l3k_asm_create_condensed): the
     matrix lives on the condensed graph (the primary dofs of every element coupled, the rows of internal dofs empty), the object
-    keeps the internal rows of every element, end() eliminates them, and recover(x) fills the internal dofs of a solution."""
+    keeps the internal rows of every element, end() eliminates them, and recover(x) fills the internal dofs of a solution.
+
+    halo (a distributed.NativeHalo of this rank's part, l3k_asm_create_dist): the system of one rank of a partitioned mesh, in the
+    sub-assembled form -- the arrays hold the local matrix over the local dofs [owned | ghost] and travel nowhere.  begin() and add()
+    are rank-local; end(g_owned) is collective, takes the prescribed values over the OWNED dofs and returns a
+    DistributedCsrOperator, which solve.pcg_distributed takes; rhs[:, :n_owned] is then the owned right-hand side (the ghost part
+    has been added to its owners and is 0); recover(x_owned) is collective and returns the owned dofs.  The flags of a ghost dof
+    in the mesh's Dirichlet mask must equal its owner's, as on the matrix-free path."""
 
     STATES = ("new", "open", "closed")
     CONDENSATION = ("none", "element_boundary")
 
-    def __init__(self, mesh, field_inds=None, n_rhs=1, workspace_bytes=0, condensation="none"):
+    def __init__(self, mesh, field_inds=None, n_rhs=1, workspace_bytes=0, condensation="none", halo=None):
+        condensation = "none" if condensation is None else condensation
         if condensation not in self.CONDENSATION:
             raise L3KError(f"AssembledSystem: condensation = {condensation!r}; it is one of {self.CONDENSATION}")
-        self.mesh, self.ctx, self.n_rhs, self.condensation = mesh, mesh.ctx, n_rhs, condensation
+        self.mesh, self.ctx, self.n_rhs, self.condensation, self.halo = mesh, mesh.ctx, n_rhs, condensation, halo
         fi = None if field_inds is None else (C.c_int * len(field_inds))(*[int(f) for f in field_inds])
         self._h = C.c_void_p()
-        create = capi.load().l3k_asm_create if condensation == "none" else capi.load().l3k_asm_create_condensed
-        check(create(mesh._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes, C.byref(self._h)))
+        if halo is not None:
+            check(capi.load().l3k_asm_create_dist(mesh._h, halo._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes,
+                                                  int(condensation != "none"), C.byref(self._h)))
+        else:
+            create = capi.load().l3k_asm_create if condensation == "none" else capi.load().l3k_asm_create_condensed
+            check(create(mesh._h, 0 if fi is None else len(fi), fi, n_rhs, workspace_bytes, C.byref(self._h)))
         i = self._info()
         self.n, self.nnz = i.n, i.nnz
+        self.n_owned = mesh.n_owned_dofs if halo is not None else i.n
         self.n_fields = mesh.dofs_per_node if field_inds is None else len(field_inds)
 
     def __del__(self):
@@ -1401,7 +1530,14 @@ class AssembledSystem:
             if nc != self.n_rhs:
                 raise L3KError("Number of RHSs must be equal to the number of prescribed values")  # bcs/DirichletBC.hpp:86
         check(capi.load().l3k_asm_end(self._h, _ptr(g), 0 if g is None else ldg))
+        if self.halo is not None:
+            return DistributedCsrOperator(_AssembledOperator(self, self._info().csr), self.halo, _handle=self._dist_info().dist)
         return _AssembledOperator(self, self._info().csr)
+
+    def _dist_info(self):
+        i = capi.AsmDistInfo()
+        check(capi.load().l3k_asm_dist_info_get(self._h, C.byref(i)))
+        return i
 
     @property
     def cond_info(self):
@@ -1414,7 +1550,18 @@ class AssembledSystem:
 
     def recover(self, x):
         """recoverSolution: the internal dofs of x [n] or [n_rhs, >= n] (float64, on the device, contiguous rows) from its solved
-        primary dofs, in place; a closed condensed system"""
+        primary dofs, in place; a closed condensed system.  With a halo (collective): x holds the owned dofs, [n_owned] or
+        [n_rhs, n_owned]; the ghost dofs are imported, and the owned dofs with the internal ones filled come back as a new tensor"""
+        if self.halo is not None:
+            import torch
+            xo = x[None, :] if x.dim() == 1 else x
+            if xo.shape != (self.n_rhs, self.n_owned):
+                raise L3KError(f"AssembledSystem.recover: x is over the {self.n_owned} owned dofs of {self.n_rhs} right-hand sides")
+            X = torch.zeros((self.n_rhs, max(self.n, 1)), dtype=torch.float64, device=x.device)
+            X[:, :self.n_owned] = xo
+            check(capi.load().l3k_asm_recover(self._h, _ptr(X), X.shape[1]))
+            out = X[:, :self.n_owned].contiguous()
+            return out[0] if x.dim() == 1 else out
         X = x[None, :] if x.dim() == 1 else x
         nc, ldx = MatrixFreeSystem._cols(X)
         if nc != self.n_rhs:
