@@ -917,6 +917,17 @@ int     l3k_halo_destroy(l3k_halo* halo);
 int64_t l3k_halo_n_ghost_dofs(const l3k_halo* halo);
 int     l3k_halo_import(l3k_halo* halo, const double* d_owned, size_t ld, int ncols, double* d_ghost, size_t ldg);
 int     l3k_halo_export_add(l3k_halo* halo, const double* d_ghost, size_t ldg, int ncols, double* d_owned, size_t ld);
+/* Sum all-reduce of d_vals[0 .. count), 1 <= count <= 8, in place on device memory, collective over ALL `world` ranks of the halo
+ * (a rank without neighbours and a rank that owns nothing take part): what MPI_Allreduce is to Belos' dot products in an MPI run
+ * of the reference (solve/BelosSolvers.hpp:116-122).  Built from the transport table alone, so every transport has it: in one
+ * group every rank sends its values to every other rank and receives theirs into a [world][8] device block; a one-workgroup
+ * kernel then adds the rows IN ASCENDING RANK ORDER, the rank's own row at its own position.  Every rank therefore ends with the
+ * same bits, and so does every run -- the collective solves below rely on it: all ranks take the same branch at a convergence
+ * check.  Queued on the context's stream and ordered against the communication stream by events, as import and export are;
+ * consecutive calls need no host synchronisation between them.  world == 1: nothing is done, no group call.  2 (world - 1)
+ * messages of at most 64 bytes per rank: O(world^2) in all, meant for the ranks of one node.  -1, d_vals untouched: a null
+ * argument, count outside [1, 8]. */
+int     l3k_halo_allreduce_sum(l3k_halo* halo, double* d_vals, int count);
 /* HIP events around the three element launches (first interior half, border elements, second interior half) of the next
  * n_applies calls of l3k_mf_apply_dist, on the stream they run on; _get waits for that apply and returns the durations. */
 int     l3k_halo_timing_begin(l3k_halo* halo, int n_applies);
@@ -999,6 +1010,41 @@ int l3k_csr_dirichlet_dist(l3k_csr* A, double* d_values, const uint8_t* d_mask, 
 int l3k_asm_create_dist(l3k_mesh* mesh, l3k_halo* halo, int n_fields, const int* field_inds, int n_rhs, size_t workspace_bytes,
                         int condensed, l3k_asm** out);
 int l3k_asm_dist_info_get(const l3k_asm* A, l3k_asm_dist_info* out);
+
+/* ---- the collective solve of a partitioned system -------------------------------------------------------------------------------
+ * l3k_csr_dist_apply_energy: y <- A x on the schedule of l3k_csr_dist_apply for one column (alpha = 1, beta = 0; y comes out bit
+ *   for bit as that call writes it) and s[1] <- THIS RANK'S share of <x, A x> over its owned rows; no other slot of s is written.
+ *   The interior rows accumulate x_i y_i inside the row kernel; the border rows, whose y is complete only behind the unpack-add,
+ *   in a pass over the border list behind it (x and y at border rows only).  An interior row that a neighbour holds as a ghost
+ *   row is completed by the unpack-add too: a third pass, over each neighbour's message, adds x_i times what the message added
+ *   to such a row (the border rows of the message are the border pass's).  Block sums in a fixed order and one finishing block:
+ *   no floating-point atomics, two calls give the same bits.  The sum over the ranks is l3k_halo_allreduce_sum's.
+ *
+ * The solves: what alg_sys.solve(CG{...}) is on every MPI rank of a run of the reference (solve/BelosSolvers.hpp:116-122).  The
+ * loops are those of l3k_pcg_solve (cheb == NULL: Jacobi), l3k_pcg_solve_cheb, l3k_cheb_create and l3k_cheb_apply -- the same
+ * code, run with the partitioned applies (l3k_mf_apply_dist; l3k_csr_dist_apply / _apply_energy) and with l3k_halo_allreduce_sum
+ * on the scalar block wherever a dot product ends: s[2:4] after the initial residual and after the z pass, s[1] after the energy
+ * apply, s[3] after the r pass, s[2] after a preconditioner application, <b, b> once, both dot products of every power step.
+ * Vectors hold the OWNED rows; x holds the initial guess and the result; options, residual scalings, check_every, frozen rows and
+ * the result are those of l3k_pcg_solve.  All four calls are COLLECTIVE and every rank passes the same options.  The reduced scalars
+ * are bit-identical on all ranks, so every rank stops at the same iteration and returns the same iterations, achieved_tol and
+ * converged; a call returns when the solve is complete.  Matrix-free <p, A p>: from the element kernels (l3k_mf_energy_begin /
+ * _end around the launches of the distributed apply) only if every rank's launches can; otherwise l3k_cg_dot_pap on every rank --
+ * decided once, at the first iteration, by all-reducing a flag.
+ * l3k_cheb_create_dist / l3k_csr_dist_cheb_create: l3k_cheb_create on the partitioned operator, the power method started from
+ *   the hash of THIS RANK'S row index; l3k_cheb_info_get, l3k_cheb_apply (collective on such an object) and l3k_cheb_destroy serve
+ *   the object unchanged.
+ * A solve with cheb != NULL takes d_minv == NULL (the object's own minv) or that very array.
+ * -1, with no collective call made before the refusal: a null argument (a rank that owns no row may pass null vectors), a cheb
+ * created on another operator or halo, a halo on another context than the system or whose dofs per node or ghost range do not match
+ * the mesh, the option errors of l3k_cheb_create. */
+int l3k_csr_dist_apply_energy(l3k_csr_dist* D, const double* d_x, double* d_y, double* d_s);
+int l3k_pcg_solve_dist(l3k_mf* mf, l3k_halo* halo, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb /* NULL: Jacobi */,
+                       const l3k_cg_opts* opts, l3k_cg_result* result);
+int l3k_csr_dist_pcg_solve(l3k_csr_dist* D, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb /* NULL: Jacobi */,
+                           const l3k_cg_opts* opts, l3k_cg_result* result);
+int l3k_cheb_create_dist(l3k_mf* mf, l3k_halo* halo, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
+int l3k_csr_dist_cheb_create(l3k_csr_dist* D, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
 
 /* ---- host-side synthetic mesh + block partition --------------------------------------------------------------------
  * Stand-in for makeCubeMesh + convertMeshToOrder + partitionMesh + the ownership / import-export context

@@ -261,6 +261,8 @@ public:
     {
         check(l3k_halo_export_add(m_halo, d_ghost, ldg, ncols, d_owned, ld));
     }
+    // sum of d_vals[0 .. count), count <= 8, over all ranks in ascending rank order, in place: the same bits on every rank
+    void allreduceSum(double* d_vals, int count) const { check(l3k_halo_allreduce_sum(m_halo, d_vals, count)); }
     l3k_halo* get() const { return m_halo; }
 
 private:
@@ -420,6 +422,31 @@ inline void updateSolution(const DeviceMesh& mesh, const double* d_x, size_t ldx
                               sol_man_inds.data(), d_fields, ldf, n_fields));
 }
 
+// The Chebyshev-Jacobi preconditioner of a partitioned operator (Ifpack2ChebyshevPreconditioner in an MPI run,
+// solve/Ifpack2Preconditioners.hpp:26-36,107-131): made by MatrixFreeSystem::chebyshev(halo, ...) or DistributedCsr::chebyshev(...)
+// (collective), handed to their pcgSolve.  The operator, the halo and d_minv must outlive it.  RAII, move-only.
+class Chebyshev
+{
+public:
+    explicit Chebyshev(l3k_cheb* handle) : m_cheb{handle} {}
+    Chebyshev(const Chebyshev&)            = delete;
+    Chebyshev& operator=(const Chebyshev&) = delete;
+    Chebyshev(Chebyshev&& o) noexcept : m_cheb{o.m_cheb} { o.m_cheb = nullptr; }
+    ~Chebyshev() { l3k_cheb_destroy(m_cheb); }
+    l3k_cheb_info info() const
+    {
+        l3k_cheb_info i{};
+        check(l3k_cheb_info_get(m_cheb, &i));
+        return i;
+    }
+    // z <- p(D^-1 A) D^-1 r over the owned rows; collective on a partitioned operator
+    void      apply(const double* d_r, double* d_z) const { check(l3k_cheb_apply(m_cheb, d_r, d_z)); }
+    l3k_cheb* get() const { return m_cheb; }
+
+private:
+    l3k_cheb* m_cheb{};
+};
+
 class MatrixFreeSystem
 {
 public:
@@ -512,6 +539,25 @@ public:
             if (!r.converged)
                 throw std::runtime_error{"Solver failed to converge"};
         return res;
+    }
+    // alg_sys.solve(CG{...}) on every rank of an MPI run (solve/BelosSolvers.hpp:116-122): the collective solve of the partitioned
+    // system over the owned rows, the reductions through `halo`; cheb == nullptr: Jacobi with d_minv, else the preconditioner of
+    // chebyshev(halo, ...) (d_minv may then be nullptr).  Every rank returns the same result; throws if not converged
+    l3k_cg_result pcgSolve(const Halo& halo, const double* d_b, double* d_x, const double* d_minv, l3k_cg_opts opts = {1e-6, 10000, 0, 1},
+                           const Chebyshev* cheb = nullptr) const
+    {
+        l3k_cg_result res{};
+        check(l3k_pcg_solve_dist(m_mf, halo.get(), d_b, d_x, d_minv, cheb ? cheb->get() : nullptr, &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    // collective; lambda_max == 0: estimated by the power method on D^-1 A across the ranks
+    Chebyshev chebyshev(const Halo& halo, const double* d_minv, l3k_cheb_opts opts = {1, 30., 10, 1.1, 0.}) const
+    {
+        l3k_cheb* c = nullptr;
+        check(l3k_cheb_create_dist(m_mf, halo.get(), d_minv, &opts, &c));
+        return Chebyshev{c};
     }
     // the kernel a launch of this system takes (which: 0 all / 1 interior / 2 border elements), as text
     std::string route(int which = 0, int ncols = 1, bool with_energy = false) const
@@ -646,6 +692,27 @@ public:
     void diag(double* d_diag, double* d_minv, double damping = 1., double threshold = 0.) const
     {
         check(l3k_csr_dist_diag(m_dist, d_diag, damping, threshold, d_minv));
+    }
+    // Y <- A X on the owned rows and d_s[1] <- this rank's share of <X, A X> (d_s: 8 device doubles; collective)
+    void applyEnergy(const double* d_x, double* d_y, double* d_s) const { check(l3k_csr_dist_apply_energy(m_dist, d_x, d_y, d_s)); }
+    // alg_sys.solve(CG{...}) on every rank of an MPI run of the reference (solve/BelosSolvers.hpp:116-122): the collective solve over
+    // the owned rows, the reductions through the operator's halo; cheb == nullptr: Jacobi with d_minv from diag(), else the
+    // preconditioner of chebyshev(...) (d_minv may then be nullptr).  Every rank returns the same result; throws if not converged
+    l3k_cg_result pcgSolve(const double* d_b, double* d_x, const double* d_minv, l3k_cg_opts opts = {1e-6, 10000, 0, 1},
+                           const Chebyshev* cheb = nullptr) const
+    {
+        l3k_cg_result res{};
+        check(l3k_csr_dist_pcg_solve(m_dist, d_b, d_x, d_minv, cheb ? cheb->get() : nullptr, &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    // collective; lambda_max == 0: estimated by the power method on D^-1 A across the ranks
+    Chebyshev chebyshev(const double* d_minv, l3k_cheb_opts opts = {1, 30., 10, 1.1, 0.}) const
+    {
+        l3k_cheb* c = nullptr;
+        check(l3k_csr_dist_cheb_create(m_dist, d_minv, &opts, &c));
+        return Chebyshev{c};
     }
     l3k_csr_dist* get() const { return m_dist; }
 

@@ -299,6 +299,12 @@ SIGNATURES = {
     "l3k_csr_dist_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),
     "l3k_csr_dist_diag": (C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
     "l3k_csr_dist_destroy": (C.c_int, [_vp]),
+    "l3k_halo_allreduce_sum": (C.c_int, [_vp, _vp, C.c_int]),
+    "l3k_csr_dist_apply_energy": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "l3k_pcg_solve_dist": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_csr_dist_pcg_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_cheb_create_dist": (C.c_int, [_vp, _vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
+    "l3k_csr_dist_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
     "l3k_csr_dirichlet_dist": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int64]),
     "l3k_asm_create_dist": (C.c_int, [_vp, _vp, C.c_int, c_int_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(_vp)]),
     "l3k_asm_dist_info_get": (C.c_int, [_vp, C.POINTER(AsmDistInfo)]),

@@ -17,6 +17,7 @@ struct l3k_csr_dist
     int64_t           n_rows[l3k::csr::n_row_classes] = {0, 0, 0};
     DevBuf< int32_t > rows[l3k::csr::n_row_classes]; // ascending row lists: interior, border, ghost
     DevBuf< double >  diag_ws;                       // [n_owned + n_ghost]: the local diagonal of l3k_csr_dist_diag
+    DevBuf< double >  energy_ws;                     // block sums of l3k_csr_dist_apply_energy (allocated by its first call)
 };
 
 namespace
@@ -98,7 +99,157 @@ void applyRows(const l3k_csr_dist* D, const int32_t* rows, int64_t n_rows, int n
         c += nc;
     }
 }
+// l3k_csr_dist_apply_energy: the launches that leave block sums of x_i y_i write a workspace of the operator's own, one segment
+// behind the other -- the two slices of the interior list (each with the grid the plain apply gives it), the border pass, the
+// neighbours' messages
+constexpr int energy_interior_blocks = l3k::red::cg_blocks, energy_border_blocks = 3 * l3k::red::cg_blocks / 8,
+              energy_received_blocks = 3 * l3k::red::cg_blocks / 8;
+constexpr size_t energy_ws_doubles   = 2 * energy_interior_blocks + energy_border_blocks + energy_received_blocks;
+// one column of a slice of the interior list with the block sums of x_i y_i into partial[0 .. returned blocks)
+int applyInteriorDot(const l3k_csr_dist* D, const int32_t* rows, int64_t n_rows, const double* x, double* y, double* partial)
+{
+    if (n_rows == 0)
+        return 0;
+    const l3k_csr* A = D->A;
+    return withLanes(A->lanes, [&](auto L) {
+        const int g = std::min(csrGrid(n_rows, L()), energy_interior_blocks);
+        hipLaunchKernelGGL((csrDistApplyKernel< L(), 1, false, true >), dim3(g), dim3(cg_threads), 0, A->ctx->stream, A->row_ptr, A->col_ind,
+                           A->values, rows, n_rows, D->n_owned, x, size_t(0), static_cast< const double* >(nullptr), size_t(0), y, size_t(0),
+                           static_cast< double* >(nullptr), size_t(0), 1., 0., partial);
+        return g;
+    });
+}
+// y <- alpha A x + beta y on the owned rows (l3k_csr_dist_apply).  d_s != nullptr (one column, alpha = 1, beta = 0:
+// l3k_csr_dist_apply_energy): the same launches in the same order, the interior ones in their WITH_DOT instance, and behind the
+// unpack-add the border pass and the finishing block: s[1] <- this rank's <x, y>
+int distApply(l3k_csr_dist* D, const char* who, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha, double beta,
+              double* d_s)
+{
+    l3k_halo* h   = D->halo;
+    l3k_ctx*  ctx = D->A->ctx;
+    // a rank that owns nothing (no row, no neighbour) takes part and returns; its timing slot is filled like everybody's
+    if (D->A->n == 0 && !halo::hasNeighbours(h))
+    {
+        L3K_HIP(hipSetDevice(ctx->device));
+        if (hipEvent_t* tev = halo::timingSlot(h))
+            for (int k = 0; k < 6; ++k)
+                L3K_HIP(hipEventRecord(tev[k], ctx->stream));
+        if (d_s)
+        {
+            l3k::red::launchFinish(ctx, 0, d_s, {1}); // (its share of <x, A x> is 0)
+            L3K_HIP(hipGetLastError());
+        }
+        return 0;
+    }
+    const size_t no = size_t(D->n_owned);
+    if (no > 0 && (!d_x || !d_y))
+    {
+        setError("%s: null vector", who);
+        return -1;
+    }
+    if (ncols > 1 && (ldx < no || ldy < no))
+    {
+        setError("%s: leading dimension smaller than the number of owned rows", who);
+        return -1;
+    }
+    if (no > 0 && overlap(d_x, size_t(ncols - 1) * ldx + no, d_y, size_t(ncols - 1) * ldy + no))
+    {
+        setError("%s: x and y overlap", who);
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(ctx->device));
+    hipStream_t s  = ctx->stream;
+    double *    xg = nullptr, *yg = nullptr;
+    size_t      ldg = 1;
+    if (int rc = halo::buffers(h, ncols, &xg, &yg, &ldg))
+        return rc;
+    hipEvent_t* tev   = halo::timingSlot(h);
+    const auto  stamp = [&](int k) { return tev ? hipEventRecord(tev[k], s) : hipSuccess; };
+    const int32_t* interior = D->rows[row_interior].ptr;
+    // (a rank without neighbours has no exchange to hide: its interior list goes in one launch -- the split costs a launch's ramp
+    // and drain, DESIGN.md 4.20)
+    const int64_t ni = D->n_rows[row_interior], half = halo::hasNeighbours(h) ? ni / 2 : ni;
+    if (d_s && !D->energy_ws.ptr)
+        if (int rc = D->energy_ws.alloc(energy_ws_doubles))
+            return rc;
+    double* const partial = D->energy_ws.ptr;
+    int           blocks  = 0; // of partial sums left so far (d_s != nullptr)
+    // ---- import: pack, post; the first half of the interior rows runs meanwhile
+    if (int rc = halo::beginImport(h, d_x, ldx, ncols, xg, ldg))
+        return rc;
+    L3K_HIP(stamp(0));
+    if (d_s)
+        blocks += applyInteriorDot(D, interior, half, d_x, d_y, partial);
+    else
+        applyRows< false >(D, interior, half, ncols, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0, alpha, beta);
+    L3K_HIP(stamp(1));
+    // ---- border rows read the imported ghosts; ghost rows write the export buffer (every entry of it: no zeroing)
+    if (int rc = halo::waitImport(h))
+        return rc;
+    L3K_HIP(stamp(2));
+    applyRows< true >(D, D->rows[row_border].ptr, D->n_rows[row_border], ncols, d_x, ldx, xg, ldg, d_y, ldy, yg, ldg, alpha, beta);
+    applyRows< true >(D, D->rows[row_ghost].ptr, D->n_rows[row_ghost], ncols, d_x, ldx, xg, ldg, d_y, ldy, yg, ldg, alpha, beta);
+    L3K_HIP(stamp(3));
+    // ---- export: post; the second half of the interior rows runs meanwhile
+    if (int rc = halo::beginExport(h, ncols, yg, ldg))
+        return rc;
+    L3K_HIP(stamp(4));
+    if (d_s)
+        blocks += applyInteriorDot(D, interior + half, ni - half, d_x, d_y, partial + blocks);
+    else
+        applyRows< false >(D, interior + half, ni - half, ncols, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0, alpha, beta);
+    L3K_HIP(stamp(5));
+    L3K_HIP(hipGetLastError());
+    if (int rc = halo::endExport(h, d_y, ldy, ncols))
+        return rc;
+    if (d_s)
+    {
+        // the border rows are complete now: their share; the interior rows that a neighbour's message added into: what it added;
+        // then the sum of all block sums in the order they were laid out
+        if (const int64_t nb = D->n_rows[row_border]; nb > 0)
+        {
+            const int g = int(std::min< int64_t >((nb + cg_threads - 1) / cg_threads, energy_border_blocks));
+            hipLaunchKernelGGL(csrDistBorderDotKernel, dim3(g), dim3(cg_threads), 0, s, D->rows[row_border].ptr, nb, d_x, d_y, partial + blocks);
+            blocks += g;
+        }
+        const int n_nbrs = halo::nNeighbours(h);
+        if (n_nbrs > energy_received_blocks)
+        {
+            setError("%s: %d neighbours, more than the %d block sums kept for their messages", who, n_nbrs, energy_received_blocks);
+            return -3;
+        }
+        for (int k = 0; k < n_nbrs; ++k)
+        {
+            const int32_t* rows = nullptr;
+            const double*  vals = nullptr;
+            int64_t        n    = 0;
+            halo::received(h, k, &rows, &vals, &n);
+            if (n == 0)
+                continue;
+            const int g = int(std::min< int64_t >((n + cg_threads - 1) / cg_threads, energy_received_blocks / n_nbrs));
+            hipLaunchKernelGGL(csrDistReceivedDotKernel, dim3(g), dim3(cg_threads), 0, s, D->A->row_ptr, D->A->col_ind, D->n_owned, rows, vals,
+                               n, d_x, partial + blocks);
+            blocks += g;
+        }
+        hipLaunchKernelGGL(l3k::red::cgFinishKernel, dim3(1), dim3(cg_threads), 0, s, partial, blocks, d_s, 1, -1);
+        L3K_HIP(hipGetLastError());
+    }
+    return 0;
+}
 } // namespace
+
+l3k_halo* l3k::csr::haloOf(const l3k_csr_dist* D)
+{
+    return D->halo;
+}
+l3k_ctx* l3k::csr::contextOf(const l3k_csr_dist* D)
+{
+    return D->A->ctx;
+}
+int64_t l3k::csr::ownedRows(const l3k_csr_dist* D)
+{
+    return D->n_owned;
+}
 
 extern "C" {
 int l3k_csr_dist_create(l3k_csr* A, l3k_halo* h, int64_t n_owned, l3k_csr_dist** out)
@@ -151,64 +302,19 @@ int l3k_csr_dist_apply(l3k_csr_dist* D, const double* d_x, size_t ldx, double* d
         setError("l3k_csr_dist_apply: null argument or ncols < 1");
         return -1;
     }
-    l3k_halo* h = D->halo;
-    // a rank that owns nothing (no row, no neighbour) takes part and returns; its timing slot is filled like everybody's
-    if (D->A->n == 0 && !halo::hasNeighbours(h))
+    return distApply(D, "l3k_csr_dist_apply", d_x, ldx, d_y, ldy, ncols, alpha, beta, nullptr);
+}
+int l3k_csr_dist_apply_energy(l3k_csr_dist* D, const double* d_x, double* d_y, double* d_s)
+{
+    if (!D || !d_s)
     {
-        if (hipEvent_t* tev = halo::timingSlot(h))
-            for (int k = 0; k < 6; ++k)
-                L3K_HIP(hipEventRecord(tev[k], D->A->ctx->stream));
-        return 0;
-    }
-    const size_t no = size_t(D->n_owned);
-    if (no > 0 && (!d_x || !d_y))
-    {
-        setError("l3k_csr_dist_apply: null vector");
+        setError("l3k_csr_dist_apply_energy: null argument");
         return -1;
     }
-    if (ncols > 1 && (ldx < no || ldy < no))
-    {
-        setError("l3k_csr_dist_apply: leading dimension smaller than the number of owned rows");
-        return -1;
-    }
-    if (no > 0 && overlap(d_x, size_t(ncols - 1) * ldx + no, d_y, size_t(ncols - 1) * ldy + no))
-    {
-        setError("l3k_csr_dist_apply: x and y overlap");
-        return -1;
-    }
-    L3K_HIP(hipSetDevice(D->A->ctx->device));
-    hipStream_t s  = D->A->ctx->stream;
-    double *    xg = nullptr, *yg = nullptr;
-    size_t      ldg = 1;
-    if (int rc = halo::buffers(h, ncols, &xg, &yg, &ldg))
+    if (int rc = l3k::red::cgWorkspace(D->A->ctx))
         return rc;
-    hipEvent_t* tev   = halo::timingSlot(h);
-    const auto  stamp = [&](int k) { return tev ? hipEventRecord(tev[k], s) : hipSuccess; };
-    const int32_t* interior = D->rows[row_interior].ptr;
-    // (a rank without neighbours has no exchange to hide: its interior list goes in one launch -- the split costs a launch's ramp
-    // and drain, DESIGN.md 4.20)
-    const int64_t ni = D->n_rows[row_interior], half = halo::hasNeighbours(h) ? ni / 2 : ni;
-    // ---- import: pack, post; the first half of the interior rows runs meanwhile
-    if (int rc = halo::beginImport(h, d_x, ldx, ncols, xg, ldg))
-        return rc;
-    L3K_HIP(stamp(0));
-    applyRows< false >(D, interior, half, ncols, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0, alpha, beta);
-    L3K_HIP(stamp(1));
-    // ---- border rows read the imported ghosts; ghost rows write the export buffer (every entry of it: no zeroing)
-    if (int rc = halo::waitImport(h))
-        return rc;
-    L3K_HIP(stamp(2));
-    applyRows< true >(D, D->rows[row_border].ptr, D->n_rows[row_border], ncols, d_x, ldx, xg, ldg, d_y, ldy, yg, ldg, alpha, beta);
-    applyRows< true >(D, D->rows[row_ghost].ptr, D->n_rows[row_ghost], ncols, d_x, ldx, xg, ldg, d_y, ldy, yg, ldg, alpha, beta);
-    L3K_HIP(stamp(3));
-    // ---- export: post; the second half of the interior rows runs meanwhile
-    if (int rc = halo::beginExport(h, ncols, yg, ldg))
-        return rc;
-    L3K_HIP(stamp(4));
-    applyRows< false >(D, interior + half, ni - half, ncols, d_x, ldx, nullptr, 0, d_y, ldy, nullptr, 0, alpha, beta);
-    L3K_HIP(stamp(5));
-    L3K_HIP(hipGetLastError());
-    return halo::endExport(h, d_y, ldy, ncols);
+    const size_t ld = size_t(D->n_owned > 0 ? D->n_owned : 1);
+    return distApply(D, "l3k_csr_dist_apply_energy", d_x, ld, d_y, ld, 1, 1., 0., d_s);
 }
 int l3k_csr_dist_diag(l3k_csr_dist* D, double* d_diag, double damping, double threshold, double* d_minv)
 {

@@ -11,6 +11,8 @@
 // that also runs torch.distributed shares torch's copy (same SONAME).
 #include "objects.hpp"
 
+#include "device/allreduce.hpp"
+
 #include <algorithm>
 
 #include <dlfcn.h>
@@ -145,6 +147,10 @@ struct l3k_halo
     int64_t            n_ghost_dofs = 0, n_send_total = 0;
     DevBuf< double >   xg, yg, sendbuf, recvbuf; // [cols][n_ghost_dofs], [cols][...] per neighbour block
     int                cols = 0;
+    // l3k_halo_allreduce_sum: the gathered values [world][allreduce_max_count] -- row `rank` is what the peers read, the others
+    // what they sent -- and the event behind a reduction's group (world > 1 only)
+    DevBuf< double > reduce_rows;
+    hipEvent_t       ev_reduce = nullptr;
     // optional timing of the three element launches of the next applies (bench.py's roofline at N > 1): 6 events per apply
     std::vector< hipEvent_t > timing;
     int                       timing_cap = 0, timing_n = 0;
@@ -158,6 +164,8 @@ struct l3k_halo
             (void)hipEventDestroy(ev_import);
         if (ev_export)
             (void)hipEventDestroy(ev_export);
+        if (ev_reduce)
+            (void)hipEventDestroy(ev_reduce);
         if (comm_stream)
             (void)hipStreamDestroy(comm_stream);
         for (hipEvent_t e : timing)
@@ -322,6 +330,17 @@ hipEvent_t* timingSlot(l3k_halo* h)
 {
     return h->timing_n < h->timing_cap ? &h->timing[size_t(6) * h->timing_n++] : nullptr;
 }
+int nNeighbours(const l3k_halo* h)
+{
+    return int(h->nbrs.size());
+}
+void received(const l3k_halo* h, int k, const int32_t** d_rows, const double** d_vals, int64_t* n)
+{
+    const auto& nb = h->nbrs[size_t(k)];
+    *d_rows        = nb.send_rows.ptr;
+    *d_vals        = h->recvbuf.ptr + nb.send_off; // (one column: the neighbour's block starts at its offset in rows)
+    *n             = nb.n_send;
+}
 } // namespace l3k::halo
 
 extern "C" {
@@ -393,6 +412,12 @@ int createHalo(l3k_ctx* ctx, const l3k_halo_transport& tp, int rank, int world, 
     L3K_HIP(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
     L3K_HIP(hipEventCreateWithFlags(&h->ev_import, hipEventDisableTiming));
     L3K_HIP(hipEventCreateWithFlags(&h->ev_export, hipEventDisableTiming));
+    if (world > 1)
+    {
+        if (int rc = h->reduce_rows.alloc(size_t(world) * l3k::halo::allreduce_max_count))
+            return rc;
+        L3K_HIP(hipEventCreateWithFlags(&h->ev_reduce, hipEventDisableTiming));
+    }
     h->owns_tp = true;
     *out       = h.release();
     return 0;
@@ -702,6 +727,62 @@ int l3k_halo_export_add(l3k_halo* h, const double* d_ghost, size_t ldg, int ncol
         return rc;
     L3K_HIP(hipStreamWaitEvent(h->ctx->stream, h->ev_export, 0));
     return unpackAll(h, d_owned, ld, ncols);
+}
+
+// MPI_Allreduce(SUM) of at most 8 doubles from the transport's point-to-point messages: every rank's values gathered on every
+// rank, added in ascending rank order (device/allreduce.hpp).
+//
+// One block serves every reduction, with no host synchronisation between them.  Reduction k + 1 overwrites
+//  - row `rank` (read by the peers in reduction k) with a copy on the context's stream, which has waited for ev_reduce of
+//    reduction k -- recorded behind the group, and a send is complete in stream order behind its group's end (the transport's
+//    contract: RCCL's, and the in-process transport's, whose group end makes the stream wait for every receiver's copy);
+//  - the other rows (read by the adding kernel of reduction k on the context's stream) inside a group that the communication
+//    stream starts behind ev_main, recorded behind that kernel.
+// The in-process transport takes its events from two pools that it reuses by group: they hold one group's messages, however
+// many reductions run.
+int l3k_halo_allreduce_sum(l3k_halo* h, double* d_vals, int count)
+{
+    using l3k::halo::allreduce_max_count;
+    if (!h || !d_vals || count < 1 || count > allreduce_max_count)
+    {
+        setError("l3k_halo_allreduce_sum: null argument or count outside [1, %d]", allreduce_max_count);
+        return -1;
+    }
+    if (h->world == 1)
+        return 0;
+    L3K_HIP(hipSetDevice(h->ctx->device));
+    hipStream_t   s    = h->ctx->stream;
+    double* const rows = h->reduce_rows.ptr;
+    double* const mine = rows + size_t(h->rank) * allreduce_max_count;
+    L3K_HIP(hipMemcpyAsync(mine, d_vals, sizeof(double) * count, hipMemcpyDeviceToDevice, s));
+    L3K_HIP(hipEventRecord(h->ev_main, s));
+    L3K_HIP(hipStreamWaitEvent(h->comm_stream, h->ev_main, 0));
+    const auto& tp = h->tp;
+    if (int rc = tp.group_begin(tp.user))
+        return rc;
+    int posted = 0; // (as in postImport: the group is closed before an error is reported)
+    for (int peer = 0; peer < h->world && posted == 0; ++peer)
+    {
+        if (peer == h->rank)
+            continue;
+        posted = tp.send(tp.user, mine, size_t(count), peer, h->comm_stream);
+        if (posted == 0)
+            posted = tp.recv(tp.user, rows + size_t(peer) * allreduce_max_count, size_t(count), peer, h->comm_stream);
+    }
+    if (posted != 0)
+    {
+        const std::string first = l3k::dev::lastError();
+        (void)tp.group_end(tp.user, h->comm_stream);
+        setError("%s", first.c_str());
+        return posted;
+    }
+    if (int rc = tp.group_end(tp.user, h->comm_stream))
+        return rc;
+    L3K_HIP(hipEventRecord(h->ev_reduce, h->comm_stream));
+    L3K_HIP(hipStreamWaitEvent(s, h->ev_reduce, 0));
+    hipLaunchKernelGGL(l3k::halo::allreduceSumRowsKernel, dim3(1), dim3(64), 0, s, rows, h->world, count, d_vals);
+    L3K_HIP(hipGetLastError());
+    return 0;
 }
 
 // HIP events around the three element launches (first interior half, border, second interior half) of the next `n_applies`

@@ -1,5 +1,6 @@
-// api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the single-rank drivers, written
-// once over the matrix-free operator and the device CSR operator (LinOp below).
+// api_solver.hip -- Jacobi-preconditioned conjugate gradients of libl3k.so: fused vector kernels and the drivers, written once over
+// the matrix-free operator and the device CSR operator, of one rank or of a partitioned system (LinOp, solver.hpp: the partitioned
+// makers bring the all-reduce of the scalar block as a hook, and the same loops are then the collective solves at the end of the file).
 #include "reduce.hpp"
 #include "solver.hpp"
 
@@ -268,11 +269,12 @@ int launchShift(l3k_ctx* ctx, double* d_s)
 // What l3k_pcg_solve and l3k_pcg_solve_cheb share around their loop bodies
 constexpr l3k_cg_opts cg_default_opts{1e-6, 10000, 0, 1}; // (opts == NULL, include/l3k.h)
 const char* const     pcg_single_rank =
-    "%s is the single-rank solver; partitioned systems iterate with the l3k_cg_* pieces and an all-reduce of the scalar block "
-    "between them (l3ster_amd/solve.py)";
+    "%s is the single-rank solver; partitioned systems call l3k_pcg_solve_dist, or iterate with the l3k_cg_* pieces and an "
+    "all-reduce of the scalar block between them (l3ster_amd/solve.py)";
 const char* const cheb_single_rank =
     "%s serves single-rank systems; this mesh has ghost nodes: partitioned systems iterate with l3k_cheb_first / l3k_cheb_step / "
-    "l3k_cg_update_rx / l3k_cg_update_p and their own applies and all-reduces (pcg_distributed in l3ster_amd/solve.py)";
+    "l3k_cg_update_rx / l3k_cg_update_p and their own applies and all-reduces (pcg_distributed in l3ster_amd/solve.py), or call "
+    "l3k_cheb_create_dist and l3k_pcg_solve_dist";
 int singleRankOnly(const l3k_mf* mf, const char* message, const char* who)
 {
     if (mf->mesh->n_ghost_nodes != 0)
@@ -296,12 +298,16 @@ struct CgDriver
         L3K_HIP(hipStreamSynchronize(ctx->stream));
         return 0;
     }
-    // with s[3] = <r, r> of the initial residual on the stream: the residual scale and the first scaled residual
-    int start(const double* d_b, int64_t n)
+    // with s[3] = <r, r> of the initial residual (reduced) on the stream: the residual scale and the first scaled residual
+    int start(const l3k::solver::LinOp& A, const double* d_b, int64_t n)
     {
         if (o.residual_scaling == 2)
+        {
             if (int rc = l3k_cg_dot_pap(ctx, d_b, d_b, n, s)) // s[1] = <b, b> (scratch use of the slot)
                 return rc;
+            if (int rc = A.reduce(s, 1, 1))
+                return rc;
+        }
         if (int rc = readScalars())
             return rc;
         const double rr0 = std::sqrt(h[3]);
@@ -337,15 +343,94 @@ using l3k::solver::Precond;
 LinOp csrOp(l3k_csr* A)
 {
     return {A->ctx, A->n, A,
-            [](void* o, const double* x, double* y, size_t n) { return l3k_csr_apply(static_cast< l3k_csr* >(o), x, n, y, n, 1, 1., 0.); },
-            [](void* o, const double* x, double* y, double* s) { return l3k_csr_apply_energy(static_cast< l3k_csr* >(o), x, y, s); }};
+            [](const LinOp& op, const double* x, double* y) {
+                return l3k_csr_apply(static_cast< l3k_csr* >(op.object), x, size_t(op.n), y, size_t(op.n), 1, 1., 0.);
+            },
+            [](const LinOp& op, const double* x, double* y, double* s) {
+                return l3k_csr_apply_energy(static_cast< l3k_csr* >(op.object), x, y, s);
+            }};
+}
+int haloReduce(void* halo, double* d_vals, int count)
+{
+    return l3k_halo_allreduce_sum(static_cast< l3k_halo* >(halo), d_vals, count);
+}
+// <x, A x> of the partitioned matrix-free operator (LinOp::energy_route): the element kernels accumulate their elements' shares,
+// l3k_cg_dot_pap the owned rows' -- the two do not add up across ranks, so all ranks take one route, agreed at the first call by
+// all-reducing "my launches did not fuse" (it depends on the launch sizes only) in s[4], a slot the iteration does not use
+int mfDistEnergy(const LinOp& op, const double* x, double* y, double* s)
+{
+    l3k_mf* const mf = static_cast< l3k_mf* >(op.object);
+    const size_t  ld = size_t(op.n > 0 ? op.n : 1);
+    if (op.energy_route == 2)
+    {
+        if (int rc = l3k_mf_apply_dist(mf, op.halo, x, ld, y, ld, 1, 1., 0.))
+            return rc;
+        return l3k_cg_dot_pap(op.ctx, x, y, op.n, s);
+    }
+    if (int rc = l3k_mf_energy_begin(mf, s))
+        return rc;
+    const int rc    = l3k_mf_apply_dist(mf, op.halo, x, ld, y, ld, 1, 1., 0.);
+    int       fused = 0;
+    if (int rc2 = l3k_mf_energy_end(mf, x, &fused))
+        return rc2;
+    if (rc)
+        return rc;
+    if (op.energy_route == 0)
+    {
+        double not_fused = fused ? 0. : 1.;
+        L3K_HIP(hipMemcpyAsync(s + 4, &not_fused, sizeof not_fused, hipMemcpyHostToDevice, op.ctx->stream));
+        L3K_HIP(hipStreamSynchronize(op.ctx->stream)); // (not_fused is a local)
+        if (int rc3 = op.reduce(s, 4, 1))
+            return rc3;
+        L3K_HIP(hipMemcpyAsync(&not_fused, s + 4, sizeof not_fused, hipMemcpyDeviceToHost, op.ctx->stream));
+        L3K_HIP(hipStreamSynchronize(op.ctx->stream));
+        op.energy_route = not_fused == 0. ? 1 : 2;
+    }
+    else if (!fused)
+    {
+        setError("l3k_pcg_solve_dist: the element kernels stopped accumulating <p, A p>");
+        return -3;
+    }
+    return op.energy_route == 1 ? 0 : l3k_cg_dot_pap(op.ctx, x, y, op.n, s); // (the dot product overwrites s[1])
 }
 } // namespace
 LinOp l3k::solver::mfOp(l3k_mf* mf)
 {
     return {mf->ctx, mf->mesh->nOwnedDofs(), mf,
-            [](void* o, const double* x, double* y, size_t n) { return l3k_mf_apply(static_cast< l3k_mf* >(o), x, n, y, n, 1, 1., 0.); },
-            [](void* o, const double* x, double* y, double* s) { return l3k_mf_apply_energy(static_cast< l3k_mf* >(o), x, y, s); }};
+            [](const LinOp& op, const double* x, double* y) {
+                return l3k_mf_apply(static_cast< l3k_mf* >(op.object), x, size_t(op.n), y, size_t(op.n), 1, 1., 0.);
+            },
+            [](const LinOp& op, const double* x, double* y, double* s) {
+                return l3k_mf_apply_energy(static_cast< l3k_mf* >(op.object), x, y, s);
+            }};
+}
+LinOp l3k::solver::mfDistOp(l3k_mf* mf, l3k_halo* halo)
+{
+    return {mf->ctx,
+            mf->mesh->nOwnedDofs(),
+            mf,
+            [](const LinOp& op, const double* x, double* y) {
+                const size_t ld = size_t(op.n > 0 ? op.n : 1);
+                return l3k_mf_apply_dist(static_cast< l3k_mf* >(op.object), op.halo, x, ld, y, ld, 1, 1., 0.);
+            },
+            &mfDistEnergy,
+            &haloReduce,
+            halo};
+}
+LinOp l3k::solver::csrDistOp(l3k_csr_dist* D)
+{
+    return {l3k::csr::contextOf(D),
+            l3k::csr::ownedRows(D),
+            D,
+            [](const LinOp& op, const double* x, double* y) {
+                const size_t ld = size_t(op.n > 0 ? op.n : 1);
+                return l3k_csr_dist_apply(static_cast< l3k_csr_dist* >(op.object), x, ld, y, ld, 1, 1., 0.);
+            },
+            [](const LinOp& op, const double* x, double* y, double* s) {
+                return l3k_csr_dist_apply_energy(static_cast< l3k_csr_dist* >(op.object), x, y, s);
+            },
+            &haloReduce,
+            l3k::csr::haloOf(D)};
 }
 using l3k::solver::mfOp;
 int l3k::solver::dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, double* d_s, int slot)
@@ -419,19 +504,32 @@ int pcgSolve(const LinOp& A, const double* d_b, double* d_x, const double* d_min
     if (int rc = work.alloc(size_t(3 * n + 8)))
         return rc;
     double *r = work.ptr, *p = r + n, *ap = p + n, *s = ap + n;
+    if (n == 0) // (a rank of a partitioned system that owns no row may bring null vectors: the kernels touch none of them)
+        d_b = d_x = work.ptr;
     CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // z = M^-1 (b - A x0), p = z
     if (int rc = A.apply(d_x, r))
         return rc;
     if (int rc = l3k_cg_init(ctx, r, d_b, p, d_minv, n, s))
         return rc;
-    if (int rc = cg.start(d_b, n))
+    if (A.reduce_fn) // (l3k_cg_init shifted this rank's <r, z>: the reduced one is shifted again)
+    {
+        if (int rc = A.reduce(s, 2, 2))
+            return rc;
+        if (int rc = launchShift(ctx, s))
+            return rc;
+    }
+    if (int rc = cg.start(A, d_b, n))
         return rc;
     while (cg.running())
     {
         if (int rc = A.applyEnergy(p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
+        if (int rc = A.reduce(s, 1, 1))
+            return rc;
         if (int rc = l3k_cg_update_z(ctx, r, ap, d_minv, n, s)) // (r holds z = M^-1 r)
+            return rc;
+        if (int rc = A.reduce(s, 2, 2))
             return rc;
         if (int rc = l3k_cg_update_px(ctx, p, d_x, r, n, s))
             return rc;
@@ -521,7 +619,7 @@ int l3k::solver::chebApply(l3k_cheb* c, const double* r, double* z, double* w, d
         if (int rc = l3k_cheb_step(ctx, r, az, c->minv, c->coef.a[k - 1], c->coef.b[k - 1], w, z, c->n, k == d - 1 ? d_s : nullptr))
             return rc;
     }
-    return 0;
+    return d_s ? c->op.reduce(d_s, 2, 1) : 0; // (the inner applies need no reduction; <r, z> is summed over the ranks)
 }
 using l3k::solver::chebApply;
 extern "C" {
@@ -596,6 +694,8 @@ int chebCreate(const LinOp& A, const char* who, const double* d_minv, const l3k_
     {
         if (int rc = launchReduce(ctx, powerStartKernel, n, s, {1}, y, d_minv))
             return rc;
+        if (int rc = A.reduce(s, 1, 1))
+            return rc;
         for (; steps < o.max_power_iters; ++steps)
         {
             hipLaunchKernelGGL(powerScaleKernel, dim3(cgGrid(n)), dim3(cg_threads), 0, st, x, y, n, s);
@@ -603,6 +703,8 @@ int chebCreate(const LinOp& A, const char* who, const double* d_minv, const l3k_
             if (int rc = A.apply(x, y))
                 return rc;
             if (int rc = launchReduce(ctx, powerStepKernel, n, s, {0, 1}, y, d_minv, x))
+                return rc;
+            if (int rc = A.reduce(s, 0, 2))
                 return rc;
         }
         L3K_HIP(hipMemcpyAsync(&est, s, sizeof est, hipMemcpyDeviceToHost, st)); // (the one readback of the creation)
@@ -692,13 +794,17 @@ int l3k::solver::pcgSolvePrecond(const LinOp& A, const char* who, const double* 
     if (int rc = work.alloc(size_t(5 * ld + 8)))
         return rc;
     double *r = work.ptr, *z = r + ld, *p = z + ld, *ap = p + ld, *w = ap + ld, *s = w + ld;
+    if (n == 0) // (a rank of a partitioned system that owns no row may bring null vectors: the kernels touch none of them)
+        d_b = d_x = work.ptr;
     CgDriver cg{opts ? *opts : cg_default_opts, ctx, s};
     // r = b - A x0 (0 on the frozen rows), s[3] = <r, r>
     if (int rc = A.apply(d_x, r))
         return rc;
     if (int rc = launchReduce(ctx, cgInitRKernel, n, s, {3}, r, d_b, M.mask))
         return rc;
-    if (int rc = cg.start(d_b, n))
+    if (int rc = A.reduce(s, 3, 1))
+        return rc;
+    if (int rc = cg.start(A, d_b, n))
         return rc;
     if (cg.running())
     {
@@ -713,7 +819,11 @@ int l3k::solver::pcgSolvePrecond(const LinOp& A, const char* who, const double* 
     {
         if (int rc = A.applyEnergy(p, ap, s)) // ap = A p, s[1] = <p, A p>
             return rc;
+        if (int rc = A.reduce(s, 1, 1))
+            return rc;
         if (int rc = l3k_cg_update_rx(ctx, d_x, r, p, ap, M.mask, n, s))
+            return rc;
+        if (int rc = A.reduce(s, 3, 1))
             return rc;
         if (int rc = cg.afterIteration())
             return rc;
@@ -756,5 +866,95 @@ int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb*
         return -1;
     }
     return l3k::solver::pcgSolvePrecond(csrOp(A), "l3k_csr_pcg_solve_cheb", d_b, d_x, chebPrecond(c), opts, result);
+}
+} // extern "C"
+// ------------------------------------------------------------------------------------------------ collective solves
+// The same loops on a partitioned operator (include/l3k.h; solve/BelosSolvers.hpp:116-122 in an MPI run).  Every refusal comes
+// before the first collective call: a rank that returns -1 here has left no peer waiting inside an exchange
+namespace
+{
+int haloFitsSystem(const char* who, const l3k_mf* mf, const l3k_halo* h)
+{
+    if (l3k::halo::context(h) != mf->ctx)
+    {
+        setError("%s: the halo and the system belong to different contexts", who);
+        return -1;
+    }
+    const int dpn = mf->mesh->dofs_per_node;
+    if (l3k::halo::dofsPerNode(h) != dpn || l3k_halo_n_ghost_dofs(h) != mf->mesh->n_ghost_nodes * dpn)
+    {
+        setError("%s: the halo (%d dofs per node, %lld ghost dofs) does not match the mesh (%d, %lld)", who, l3k::halo::dofsPerNode(h),
+                 (long long)l3k_halo_n_ghost_dofs(h), dpn, (long long)(mf->mesh->n_ghost_nodes * dpn));
+        return -1;
+    }
+    return 0;
+}
+int distSolve(const LinOp& A, const char* who, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* c, const l3k_cg_opts* opts,
+              l3k_cg_result* result)
+{
+    if (A.n > 0 && (!d_b || !d_x))
+    {
+        setError("%s: null vector", who);
+        return -1;
+    }
+    if (int rc = cgWorkspace(A.ctx))
+        return rc;
+    if (!c)
+        return pcgSolve(A, d_b, d_x, d_minv, opts, result);
+    if (c->op.object != A.object || c->op.halo != A.halo)
+    {
+        setError("%s: the preconditioner was created for another system", who);
+        return -1;
+    }
+    if (d_minv && d_minv != c->minv)
+    {
+        setError("%s: d_minv is not the array the preconditioner was created on (pass that one, or NULL)", who);
+        return -1;
+    }
+    return l3k::solver::pcgSolvePrecond(A, who, d_b, d_x, chebPrecond(c), opts, result);
+}
+} // namespace
+extern "C" {
+int l3k_pcg_solve_dist(l3k_mf* mf, l3k_halo* halo, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb,
+                       const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!mf || !halo || !result)
+    {
+        setError("l3k_pcg_solve_dist: null argument");
+        return -1;
+    }
+    if (int rc = haloFitsSystem("l3k_pcg_solve_dist", mf, halo))
+        return rc;
+    return distSolve(l3k::solver::mfDistOp(mf, halo), "l3k_pcg_solve_dist", d_b, d_x, d_minv, cheb, opts, result);
+}
+int l3k_csr_dist_pcg_solve(l3k_csr_dist* D, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb, const l3k_cg_opts* opts,
+                           l3k_cg_result* result)
+{
+    if (!D || !result)
+    {
+        setError("l3k_csr_dist_pcg_solve: null argument");
+        return -1;
+    }
+    return distSolve(l3k::solver::csrDistOp(D), "l3k_csr_dist_pcg_solve", d_b, d_x, d_minv, cheb, opts, result);
+}
+int l3k_cheb_create_dist(l3k_mf* mf, l3k_halo* halo, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!mf || !halo || !out || (!d_minv && mf->mesh->nOwnedDofs() > 0))
+    {
+        setError("l3k_cheb_create_dist: null argument");
+        return -1;
+    }
+    if (int rc = haloFitsSystem("l3k_cheb_create_dist", mf, halo))
+        return rc;
+    return chebCreate(l3k::solver::mfDistOp(mf, halo), "l3k_cheb_create_dist", d_minv, opts, out);
+}
+int l3k_csr_dist_cheb_create(l3k_csr_dist* D, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!D || !out || (!d_minv && l3k::csr::ownedRows(D) > 0))
+    {
+        setError("l3k_csr_dist_cheb_create: null argument");
+        return -1;
+    }
+    return chebCreate(l3k::solver::csrDistOp(D), "l3k_csr_dist_cheb_create", d_minv, opts, out);
 }
 } // extern "C"

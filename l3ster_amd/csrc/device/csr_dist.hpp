@@ -118,24 +118,31 @@ static __global__ __launch_bounds__(cg_threads) void csrRowClassFillKernel(const
 // read) and yg[i - n_owned] <- alpha (A x)_i otherwise -- a ghost row is this rank's share of its owner's row: it goes into the
 // export buffer, which therefore needs no zeroing, an empty ghost row stores alpha 0.  SPLIT = false: the rows of the interior
 // list, whose columns and rows are all owned -- xg and yg are not touched.  Same lanes, loads, accumulators and butterfly as
-// csrApplyKernel: the same bits per row
-template < int L, int NC, bool SPLIT >
+// csrApplyKernel: the same bits per row.
+// WITH_DOT (the interior list, NC = 1, n_rows > 0; l3k_csr_dist_apply_energy): the block sums of x_i y_i over the launch's rows go
+// to partial[blockIdx.x], for cgFinishKernel -- csrApplyKernel's WITH_DOT on a row list; y is stored as without it
+template < int L, int NC, bool SPLIT, bool WITH_DOT = false >
 __global__ __launch_bounds__(cg_threads) void csrDistApplyKernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col_ind,
                                                                  const double* __restrict__ values, const int32_t* __restrict__ rows,
                                                                  int64_t n_rows, int64_t n_owned, const double* __restrict__ x, size_t ldx,
                                                                  const double* __restrict__ xg, size_t ldxg, double* __restrict__ y,
-                                                                 size_t ldy, double* __restrict__ yg, size_t ldyg, double alpha, double beta)
+                                                                 size_t ldy, double* __restrict__ yg, size_t ldyg, double alpha, double beta,
+                                                                 double* __restrict__ partial = nullptr)
 {
+    static_assert(!WITH_DOT || (NC == 1 && !SPLIT));
     const int     lane   = threadIdx.x % L;
     const int64_t groups = int64_t(gridDim.x) * (cg_threads / L);
     int64_t       r      = (int64_t(blockIdx.x) * cg_threads + threadIdx.x) / L;
+    double        dot[1] = {0.};
     // The list entry of the group's NEXT row is fetched while the current row is walked, by an unconditional load (the last row
     // names itself again), and is turned into the next row's address BEFORE the current row's store: the top of the loop then
     // issues the row_ptr load at once and one wait covers it and the store, as in csrApplyKernel.  (The wait counter of loads and
     // stores is one in-order counter here: a value consumed behind the store costs the store's round trip on every row.)
-    if (r >= n_rows)
-        return;
-    int32_t i_first = rows[r];
+    const bool idle = r >= n_rows;
+    if constexpr (!WITH_DOT)
+        if (idle)
+            return;
+    int32_t i_first = rows[idle ? 0 : r]; // (WITH_DOT: a group without a row stays for the barriers of the block sum)
     asm volatile("" : "+v"(i_first)); // (awaited ahead of the loop, so that the loop's head waits for nothing)
     const int64_t* rp = row_ptr + i_first;
     for (; r < n_rows; r += groups)
@@ -143,7 +150,10 @@ __global__ __launch_bounds__(cg_threads) void csrDistApplyKernel(const int64_t* 
         const int64_t i      = rp - row_ptr;
         int32_t       i_next = rows[r + groups < n_rows ? r + groups : r];
         const int64_t e      = rp[1];
-        double        acc[NC];
+        double        xi     = 0.; // (WITH_DOT: x_i is fetched with the row, ahead of the store -- a load behind it would wait for it)
+        if constexpr (WITH_DOT)
+            xi = x[i];
+        double acc[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             acc[c] = 0.;
@@ -171,6 +181,8 @@ __global__ __launch_bounds__(cg_threads) void csrDistApplyKernel(const int64_t* 
         rp = row_ptr + i_next;
         if (lane == 0)
         {
+            if constexpr (WITH_DOT)
+                dot[0] += xi * (alpha * acc[0]); // (alpha = 1, beta = 0: x_i times the value stored below)
             if (SPLIT && i >= n_owned)
             {
 #pragma unroll
@@ -191,6 +203,46 @@ __global__ __launch_bounds__(cg_threads) void csrDistApplyKernel(const int64_t* 
             }
         }
     }
+    if constexpr (WITH_DOT)
+    {
+        __shared__ double sh[cg_threads];
+        red::storePartials(dot, sh, partial);
+    }
+}
+// An INTERIOR row that a neighbour holds as a ghost row is completed by the unpack-add as well -- after its x_i y_i went into the
+// row kernel's sum.  What it still lacks is x_i times what one neighbour's message added: block sums over that message (rows: the
+// neighbour's send list, vals: the received values, n of each) into partial[blockIdx.x].  A border row of the list is left out:
+// the border pass reads its final y
+static __global__ __launch_bounds__(cg_threads) void csrDistReceivedDotKernel(const int64_t* __restrict__ row_ptr,
+                                                                              const int32_t* __restrict__ col_ind, int64_t n_owned,
+                                                                              const int32_t* __restrict__ rows, const double* __restrict__ vals,
+                                                                              int64_t n, const double* __restrict__ x,
+                                                                              double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            dot[1] = {0.};
+    for (int64_t k = int64_t(blockIdx.x) * cg_threads + threadIdx.x; k < n; k += int64_t(gridDim.x) * cg_threads)
+    {
+        const int64_t i = rows[k];
+        if (rowClass(row_ptr, col_ind, i, n_owned) == row_interior)
+            dot[0] += x[i] * vals[k];
+    }
+    red::storePartials(dot, sh, partial);
+}
+// the border rows' share of <x, y> once y is complete there (behind the unpack-add): block sums of x_i y_i over the border list
+// into partial[blockIdx.x].  Reads x and y at border rows only
+static __global__ __launch_bounds__(cg_threads) void csrDistBorderDotKernel(const int32_t* __restrict__ rows, int64_t n_rows,
+                                                                            const double* __restrict__ x, const double* __restrict__ y,
+                                                                            double* __restrict__ partial)
+{
+    __shared__ double sh[cg_threads];
+    double            dot[1] = {0.};
+    for (int64_t r = int64_t(blockIdx.x) * cg_threads + threadIdx.x; r < n_rows; r += int64_t(gridDim.x) * cg_threads)
+    {
+        const int64_t i = rows[r];
+        dot[0] += x[i] * y[i];
+    }
+    red::storePartials(dot, sh, partial);
 }
 
 // the local diagonal over [owned | ghost]: csrDiagKernel's a_ii (0 where none is stored), the owned rows into diag, the ghost rows

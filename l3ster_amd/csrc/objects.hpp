@@ -465,7 +465,18 @@ int beginExport(l3k_halo* h, int ncols, const double* d_ghost, size_t ldg);
 int endExport(l3k_halo* h, double* d_owned, size_t ld, int ncols);
 // the six events of the next timed apply (l3k_halo_timing_begin), or nullptr when none is left
 hipEvent_t* timingSlot(l3k_halo* h);
+// what the last export of ONE column brought from neighbour k < nNeighbours(h): the owned rows it added into (the neighbour's send
+// list) and the values it added, n of each; valid behind endExport until the next export
+int  nNeighbours(const l3k_halo* h);
+void received(const l3k_halo* h, int k, const int32_t** d_rows, const double** d_vals, int64_t* n);
 } // namespace l3k::halo
+// api_csr_dist.hip: what the collective solves (api_solver.hip) need of a distributed CSR operator
+namespace l3k::csr
+{
+l3k_halo* haloOf(const l3k_csr_dist* D);
+l3k_ctx*  contextOf(const l3k_csr_dist* D);
+int64_t   ownedRows(const l3k_csr_dist* D);
+} // namespace l3k::csr
 
 // a boundary equation kernel on a list of element sides (assembleProblem(kernel, boundary_ids) of the reference)
 struct l3k_bnd : KernelTerm

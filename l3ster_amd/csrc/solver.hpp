@@ -9,19 +9,31 @@
 
 namespace l3k::solver
 {
-// The operator of a single-rank solve: n rows, y <- A x, and y <- A x with s[1] <- <x, A x>, on the context's stream.  The PCG
-// loops, the power method and the Chebyshev recurrence are written ONCE over this value; mfOp and csrOp make it
+// The operator of a solve: n rows (of a partitioned system: this rank's owned rows), y <- A x, and y <- A x with s[1] <- this rank's
+// <x, A x>, on the context's stream.  The PCG loops, the power method and the Chebyshev recurrence are written ONCE over this
+// value; mfOp and csrOp make it for one rank, mfDistOp and csrDistOp for a partitioned system.  reduce_fn and its object `halo` are the reduction hook:
+// the loops call reduce(s, first, count) wherever a dot product has landed in s[first .. first + count); the partitioned makers
+// set l3k_halo_allreduce_sum over the halo's ranks, the single-rank makers leave it null and nothing is enqueued
 struct LinOp
 {
     l3k_ctx* ctx;
     int64_t  n;
-    void*    object; // the l3k_mf or l3k_csr behind it
-    int (*apply_fn)(void*, const double*, double*, size_t);
-    int (*energy_fn)(void*, const double*, double*, double*);
-    int apply(const double* d_x, double* d_y) const { return apply_fn(object, d_x, d_y, size_t(n)); }
-    int applyEnergy(const double* d_x, double* d_y, double* d_s) const { return energy_fn(object, d_x, d_y, d_s); }
+    void*    object; // the l3k_mf, l3k_csr or l3k_csr_dist behind it
+    int (*apply_fn)(const LinOp&, const double*, double*);
+    int (*energy_fn)(const LinOp&, const double*, double*, double*);
+    int (*reduce_fn)(void* halo, double* d_vals, int count) = nullptr;
+    l3k_halo* halo                                           = nullptr;
+    // partitioned matrix-free operator: where <x, A x> comes from -- 0 not agreed yet, 1 the element kernels on every rank, 2
+    // l3k_cg_dot_pap on every rank (element-wise and row-wise shares do not add up across ranks)
+    mutable int energy_route = 0;
+    int apply(const double* d_x, double* d_y) const { return apply_fn(*this, d_x, d_y); }
+    int applyEnergy(const double* d_x, double* d_y, double* d_s) const { return energy_fn(*this, d_x, d_y, d_s); }
+    int reduce(double* d_s, int first, int count) const { return reduce_fn ? reduce_fn(halo, d_s + first, count) : 0; }
 };
 LinOp mfOp(l3k_mf* mf);
+// the partitioned operators: (l3k_mf, l3k_halo) through l3k_mf_apply_dist, l3k_csr_dist through l3k_csr_dist_apply / _apply_energy
+LinOp mfDistOp(l3k_mf* mf, l3k_halo* halo);
+LinOp csrDistOp(l3k_csr_dist* D);
 // The preconditioner of the PCG that keeps r (pcgSolvePrecond): z <- M^-1 r with s[2] <- <r, z> behind it on the stream, the
 // frozen-row mask (rows with mask == 0 keep x and carry r = 0) and the sizes.  w and az are two vectors of the loop's workspace
 // that are free during the application
@@ -45,7 +57,7 @@ int dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, doubl
 // method during creation, w and A z of l3k_cheb_apply afterwards
 struct l3k_cheb
 {
-    l3k::solver::LinOp    op; // the operator it was created on (mfOp or csrOp)
+    l3k::solver::LinOp    op; // the operator it was created on (mfOp, csrOp, mfDistOp or csrDistOp: its applies are collective then)
     const double*         minv;
     l3k_cheb_info         info;
     l3k::host::ChebCoeffs coef;

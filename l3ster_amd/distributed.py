@@ -300,6 +300,17 @@ class NativeHalo:
             capi.check(lib.l3k_halo_create_transport(ctx._h, C.byref(table), rank, world, dofs_per_node, *lists))
         self.ctx = ctx
 
+    def allreduce(self, t):
+        """Sum of the 1 to 8 doubles of the contiguous device tensor t over ALL ranks the halo was created with, in place
+        (l3k_halo_allreduce_sum; collective, queued on the context's stream).  The rows are added in ascending rank order: every rank
+        ends with the same bits."""
+        import ctypes as C
+        from . import capi
+        if t.dtype != torch.float64 or not t.is_contiguous() or not 1 <= t.numel() <= 8:
+            raise capi.L3KError("NativeHalo.allreduce: a contiguous float64 tensor of 1 to 8 entries")
+        capi.check(capi.load().l3k_halo_allreduce_sum(self._h, C.c_void_p(t.data_ptr()), t.numel()))
+        return t
+
     def __del__(self):
         try:
             from . import capi

@@ -437,7 +437,7 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
 
 
 def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None,
-                    throw_on_fail=True, allreduce=None, check_every=1, precond=None):
+                    throw_on_fail=True, allreduce=None, check_every=1, precond=None, native=False):
     """The same iteration for a partitioned system: `op.apply(X, Y)` is a DistributedOperator over this rank's owned
     rows; the fused l3k_cg_* kernels keep the scalars in a device block that is all-reduced between them (two small
     all-reduces per iteration, as Belos does).
@@ -449,8 +449,24 @@ def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residu
     iteration is then that of l3k_pcg_solve_cheb with the exported pieces (l3k_cheb_first / _step, l3k_cg_update_rx /
     _update_p): the inner applies go through op.apply and need no reduction, the outer scalars and -- without
     lambda_max -- <x, y> and <y, y> of the power method go through the same reduction hook.  The power method starts
-    from power_start_vector over this rank's rows."""
+    from power_start_vector over this rank's rows.
+
+    native=True: the whole iteration inside the library (l3k_csr_dist_pcg_solve / l3k_pcg_solve_dist): `op` is a
+    system.DistributedCsrOperator or a distributed.NativeDistributedOperator, the reductions are l3k_halo_allreduce_sum over the
+    ranks of its halo -- `group` and `allreduce` must be None -- and the host reads 32 bytes per convergence check.  `precond`:
+    None, a dict of Chebyshev options (the power method then runs inside the library too), a DistributedChebyshev of `op`, or an
+    object whose .info has lambda_max, lambda_min and degree.  A DistributedPMultigrid stays on the host loop (native=False).
+    Every rank returns the same IterSolveResult."""
     from . import capi
+    if native:
+        if group is not None or allreduce is not None:
+            raise capi.L3KError("pcg_distributed(native=True) reduces over the ranks of the operator's halo inside the library: "
+                                "group and allreduce must be None")
+        if isinstance(precond, DistributedPMultigrid):
+            raise capi.L3KError("pcg_distributed(native=True) has no p-multigrid: a DistributedPMultigrid runs on the host loop "
+                                "(native=False)")
+        opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
+        return _pcg_distributed_native(op, b, x, minv, opts, precond, throw_on_fail)
     pmg = precond if isinstance(precond, DistributedPMultigrid) else None
     if pmg is not None:
         if pmg.op is not op:
@@ -561,6 +577,15 @@ def _distributed_chebyshev(precond, op, minv, reduce):
     info = getattr(precond, "info", None)
     if info is not None:
         return chebyshev_coefficients(info.lambda_max, info.lambda_min, info.degree)
+    o = _chebyshev_options(precond)
+    lam = o["lambda_max"]
+    if lam is None:
+        lam = o["boost_factor"] * _distributed_lambda_est(op, minv, reduce, o["max_power_iters"])
+    return chebyshev_coefficients(lam, lam / o["cond_est"], o["degree"])
+
+
+def _chebyshev_options(precond):
+    """a dict of ChebyshevPreconditioner's options completed with their defaults and checked"""
     o = dict(degree=1, cond_est=30.0, max_power_iters=10, boost_factor=1.1, lambda_max=None)
     unknown = set(precond) - set(o)
     if unknown:
@@ -568,24 +593,100 @@ def _distributed_chebyshev(precond, op, minv, reduce):
     o.update(precond)
     if o["degree"] < 1 or not o["cond_est"] > 1 or not o["boost_factor"] >= 1:
         raise ValueError("Chebyshev options: degree >= 1, cond_est > 1, boost_factor >= 1")
-    lam = o["lambda_max"]
-    if lam is None:
-        if o["max_power_iters"] < 1:
-            raise ValueError("max_power_iters < 1 and no lambda_max given")
-        live = minv != 0
-        y = torch.where(live, power_start_vector(minv.numel(), minv.device), torch.zeros_like(minv))
-        t = torch.zeros(2, dtype=torch.float64, device=minv.device)
-        t[1] = torch.dot(y, y)
-        reduce(t[1:2])
-        ax = torch.empty_like(minv)
-        for _ in range(o["max_power_iters"]):
-            xv = y * (1.0 / torch.sqrt(t[1]))
-            op.apply(xv[None, :], ax[None, :])
-            y = torch.where(live, minv * ax, torch.zeros_like(minv))
-            t[0], t[1] = torch.dot(xv, y), torch.dot(y, y)
-            reduce(t)
-        est = t[0].item()
-        if not (est > 0 and est < float("inf")):
-            raise RuntimeError(f"the power method on D^-1 A gave the eigenvalue estimate {est}: it must be finite and positive")
-        lam = o["boost_factor"] * est
-    return chebyshev_coefficients(lam, lam / o["cond_est"], o["degree"])
+    if o["lambda_max"] is None and o["max_power_iters"] < 1:
+        raise ValueError("max_power_iters < 1 and no lambda_max given")
+    return o
+
+
+def _distributed_lambda_est(op, minv, reduce, max_power_iters=10):
+    """The eigenvalue estimate of the host loop: max_power_iters steps of the power method on D^-1 A through op.apply from
+    power_start_vector over this rank's rows, <x, y> and <y, y> reduced across the ranks."""
+    live = minv != 0
+    y = torch.where(live, power_start_vector(minv.numel(), minv.device), torch.zeros_like(minv))
+    t = torch.zeros(2, dtype=torch.float64, device=minv.device)
+    t[1] = torch.dot(y, y)
+    reduce(t[1:2])
+    ax = torch.empty_like(minv)
+    for _ in range(max_power_iters):
+        xv = y * (1.0 / torch.sqrt(t[1]))
+        op.apply(xv[None, :], ax[None, :])
+        y = torch.where(live, minv * ax, torch.zeros_like(minv))
+        t[0], t[1] = torch.dot(xv, y), torch.dot(y, y)
+        reduce(t)
+    est = t[0].item()
+    if not (est > 0 and est < float("inf")):
+        raise RuntimeError(f"the power method on D^-1 A gave the eigenvalue estimate {est}: it must be finite and positive")
+    return est
+
+
+def _native_operator(op):
+    """(kind, handles) of an operator the collective entry points take: ("csr", (l3k_csr_dist,)) for a
+    system.DistributedCsrOperator, ("mf", (l3k_mf, l3k_halo)) for a matrix-free operator on a distributed.NativeHalo"""
+    from . import capi
+    from .system import DistributedCsrOperator
+    if isinstance(op, DistributedCsrOperator):
+        return "csr", (op._h,)
+    mf, halo = getattr(op, "mf", None), getattr(op, "halo", None)
+    if mf is not None and getattr(halo, "_h", None) and getattr(mf, "_h", None):
+        return "mf", (mf._h, halo._h)
+    raise capi.L3KError("the collective solve inside the library takes a system.DistributedCsrOperator or a "
+                        "distributed.NativeDistributedOperator (a MatrixFreeSystem on a NativeHalo)")
+
+
+class DistributedChebyshev:
+    """Handle of l3k_csr_dist_cheb_create / l3k_cheb_create_dist: the Chebyshev-Jacobi preconditioner of a partitioned operator
+    (a system.DistributedCsrOperator, or a distributed.NativeDistributedOperator), with the power method and its reductions inside
+    the library.  Creation and apply are collective; options as ChebyshevPreconditioner's.  `op` and `minv` are kept alive here."""
+
+    def __init__(self, op, minv, degree=1, cond_est=30., max_power_iters=10, boost_factor=1.1, lambda_max=None):
+        from . import capi
+        kind, handles = _native_operator(op)
+        self.op, self.system, self.minv = op, op, minv
+        if minv is None or not minv.is_contiguous():
+            raise capi.L3KError("minv must be a contiguous tensor over the owned dofs of the operator")
+        opts = capi.ChebOpts(int(degree), float(cond_est), int(max_power_iters), float(boost_factor),
+                             0.0 if lambda_max is None else float(lambda_max))
+        create = capi.load().l3k_csr_dist_cheb_create if kind == "csr" else capi.load().l3k_cheb_create_dist
+        self._h = C.c_void_p()
+        capi.check(create(*handles, _vp(minv), C.byref(opts), C.byref(self._h)))
+
+    info = ChebyshevPreconditioner.info
+    close = ChebyshevPreconditioner.close
+    __del__ = ChebyshevPreconditioner.__del__
+
+    def apply(self, r, z):
+        """z <- p(D^-1 A) D^-1 r over the owned rows (l3k_cheb_apply; collective)"""
+        from . import capi
+        if _overlap(r, z, r.numel()):
+            raise capi.L3KError("r and z must be distinct vectors that do not overlap")
+        capi.check(capi.load().l3k_cheb_apply(self._h, _vp(r), _vp(z)))
+        return z
+
+
+def _pcg_distributed_native(op, b, x, minv, opts, precond, throw_on_fail):
+    """pcg_distributed(native=True): l3k_csr_dist_pcg_solve / l3k_pcg_solve_dist"""
+    from . import capi
+    kind, handles = _native_operator(op)
+    n = b.numel()
+    if x.numel() != n or not (b.is_contiguous() and x.is_contiguous()) or (n and _overlap(b, x, n)):
+        raise capi.L3KError("b and x must be distinct contiguous vectors over the owned dofs")
+    cheb = None
+    if precond is not None:
+        if minv is None:
+            raise capi.L3KError("pcg_distributed(precond=...) needs minv: the preconditioner is a polynomial in D^-1 A")
+        if isinstance(precond, DistributedChebyshev):
+            cheb = precond
+        elif isinstance(precond, dict):
+            cheb = DistributedChebyshev(op, minv, **_chebyshev_options(precond))
+        else:  # another preconditioner's numbers on this operator: no power method
+            i = precond.info
+            cheb = DistributedChebyshev(op, minv, degree=i.degree, cond_est=i.lambda_max / i.lambda_min, lambda_max=i.lambda_max)
+        minv = cheb.minv
+    solve = capi.load().l3k_csr_dist_pcg_solve if kind == "csr" else capi.load().l3k_pcg_solve_dist
+    res = capi.CgResult()
+    try:
+        capi.check(solve(*handles, _vp(b), _vp(x), _vp(minv), cheb._h if cheb is not None else None, C.byref(opts), C.byref(res)))
+    finally:
+        if cheb is not None and cheb is not precond:
+            cheb.close()
+    return _from_c([res], throw_on_fail)[0]

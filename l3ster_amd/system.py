@@ -1315,8 +1315,9 @@ class DistributedCsrOperator:
     distributed.NativeHalo) run inside every apply.  AssembledSystem(..., halo=...).end() returns one; it can also be built from any
     CsrOperator over local dofs (arrays filled by assemble_global / condense_global on a partitioned hex mesh, after
     dirichlet_local) plus the halo.  n = n_owned_dofs: the owned dofs.  solve.pcg_distributed takes it as its `op` (with minv from
-    jacobi_inverse, and with precond=dict(...) for Chebyshev); it offers no energy= keyword, so the loop takes <p, A p> from
-    l3k_cg_dot_pap.  apply, diag and jacobi_inverse are collective.  Applies are bitwise reproducible."""
+    jacobi_inverse, and with precond=dict(...) for Chebyshev): its host loop takes <p, A p> from apply(..., energy=s), and with
+    native=True the whole iteration runs inside the library (l3k_csr_dist_pcg_solve).  apply, diag and jacobi_inverse are
+    collective.  Applies are bitwise reproducible."""
 
     def __init__(self, local, halo, n_owned=None, _handle=None):
         lib = capi.load()
@@ -1360,9 +1361,11 @@ class DistributedCsrOperator:
                                      border_rows=self._rows(i.d_border_rows, i.n_border_rows),
                                      ghost_rows=self._rows(i.d_ghost_rows, i.n_ghost_rows))
 
-    def apply(self, X, Y, alpha=1.0, beta=0.0):
+    def apply(self, X, Y, alpha=1.0, beta=0.0, energy=None):
         """Y <- alpha A X + beta Y on the owned rows; X, Y: (ncols, ld) multivectors or 1-D vectors over the owned rows
-        (l3k_csr_dist_apply; collective)"""
+        (l3k_csr_dist_apply; collective).  energy: the PCG's device scalar block S (8 doubles); for one column with alpha = 1 and
+        beta = 0, S[1] receives this rank's share of <X, A X> from the same launches (l3k_csr_dist_apply_energy) and
+        self.energy_fused says that it did -- the protocol of distributed.DistributedOperator.apply."""
         if X.dim() == 1 and Y.dim() == 1:
             X, Y2 = X[None, :], Y[None, :]
         else:
@@ -1371,7 +1374,21 @@ class DistributedCsrOperator:
         nc2, ldy = MatrixFreeSystem._cols(Y2)
         if nc != nc2 or X.shape[1] < self.n or Y2.shape[1] < self.n:
             raise L3KError("X and Y must have the same number of columns and at least n_owned rows")
-        check(capi.load().l3k_csr_dist_apply(self._h, _ptr(X), ldx, _ptr(Y2), ldy, nc, alpha, beta))
+        self.energy_fused = energy is not None and nc == 1 and alpha == 1.0 and beta == 0.0
+        if self.energy_fused:
+            if energy.numel() < 8 or not energy.is_contiguous():
+                raise L3KError("energy is the PCG's scalar block: a contiguous tensor of 8 doubles")
+            check(capi.load().l3k_csr_dist_apply_energy(self._h, _ptr(X), _ptr(Y2), _ptr(energy)))
+        else:
+            check(capi.load().l3k_csr_dist_apply(self._h, _ptr(X), ldx, _ptr(Y2), ldy, nc, alpha, beta))
+        return Y
+
+    def apply_energy(self, X, Y, S):
+        """Y <- A X (one column over the owned rows) and S[1] <- this rank's share of <X, A X> (l3k_csr_dist_apply_energy;
+        collective): S is the PCG's scalar block (8 doubles); no other slot of it is written"""
+        if X.numel() != self.n or Y.numel() != self.n or S.numel() < 8 or not (X.is_contiguous() and Y.is_contiguous()):
+            raise L3KError("X and Y are contiguous vectors over the owned rows, S has 8 entries")
+        check(capi.load().l3k_csr_dist_apply_energy(self._h, _ptr(X), _ptr(Y), _ptr(S)))
         return Y
 
     def _diag(self, want_diag, want_minv, damping, threshold):
