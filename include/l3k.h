@@ -639,6 +639,66 @@ int l3k_csr_pcg_solve_cols(l3k_csr* A, const double* d_b, size_t ldb, double* d_
 int l3k_csr_cheb_create(l3k_csr* A, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
 int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result);
 
+/* ---- sparse direct solver on a CSR operator: band Cholesky ------------------------------------------------------------------
+ * What the reference reaches through Amesos2 (Klu2 / Lapack, solve/Amesos2Solvers.hpp:18-32: pre-ordering and symbolic
+ * factorisation on the first call, numeric factorisation and solve on every call), for the matrices this library hands to a
+ * solver: after l3k_csr_dirichlet they are symmetric and positive definite, so the factorisation is A = L L^T without pivoting.
+ * Single rank.  VALUE symmetry is assumed, not checked: only the lower triangle of the permuted matrix is read.
+ *
+ * Symbolic phase (host, once, in l3k_chol_create): the ACTIVE rows are the rows that store an entry; empty rows (internal dofs of
+ * a condensed graph, dofs outside field_inds) stay outside the factorisation and x keeps its value there, the frozen-row rule of
+ * l3k_csr_diag and the PCG.  The graph must be structurally symmetric (-1, the message names the first stored (i, j) without a
+ * stored (j, i)).  The active rows are ordered by reverse Cuthill-McKee, component by component, each from a pseudo-peripheral
+ * node, ties by lowest degree then lowest index: the same permutation on every run and machine.  The factor lives in blocks of
+ * NB x NB (32 or 64): block column K stores its diagonal block and the H(K) blocks below it, H the smallest heights that hold every
+ * entry of the permuted lower triangle with K + H(K) non-decreasing -- a variable band closed under fill; the last block is
+ * padded with identity.
+ * Numeric phase (device, the context's stream, ordinary launches): l3k_chol_factor copies A's CURRENT values into the storage
+ * and factors right-looking, three launches per block column (diagonal block in LDS; panel; trailing update on the FP64 matrix
+ * cores); l3k_chol_solve gathers b, substitutes forwards and backwards (two launches per block column each way, all columns
+ * together) and scatters into x.  No kernel waits for another workgroup and nothing accumulates atomically in floating point:
+ * factor and solve are bitwise reproducible.
+ *
+ * l3k_chol_opts: max_bytes = the most the factor may occupy, 0 = 8 GiB; block = NB: 32, 64, or 0 = 64 once the ordered matrix
+ *   stores an entry 64 or more rows off the diagonal, else 32.
+ * l3k_chol_create: symbolic only; A must outlive the object, and its graph must not change.  -1: a null argument, another block,
+ *   an unsymmetric graph, a factor above max_bytes (the message states the bytes needed and the largest H; nothing is allocated
+ *   -- a 3-D system too large for a band method is refused here, not by the allocator).  One readback of the graph: synchronises.
+ * l3k_chol_factor: numeric; the call a time loop repeats after it has assembled again.  A pivot that is not positive and finite
+ *   is replaced by 1 and counted, nothing faults and no NaN is made of it; one readback at the end (synchronises) returns -2,
+ *   "matrix is not positive definite", with n_bad_pivots and first_bad_row (the caller's numbering) in the info.
+ * l3k_chol_solve: x <- A^-1 b on the active rows for ncols columns (column c at + c * ld; ld >= n for ncols > 1); other rows of
+ *   x are not written.  b and x may be the same buffer.  -1 unless the last l3k_chol_factor succeeded.  The workspace is the
+ *   object's; it grows at the first solve with more columns than any before, never otherwise.
+ * l3k_chol_order (host only, no context, host arrays): the symbolic phase alone.  perm_out [n]: perm_out[k] = the row ordered
+ *   k-th for k < n_active, then -1; heights_out [at least n / 32 + 1]: H(K) for the ceil(n_active / nb) block columns; *nb in:
+ *   0, 32 or 64 as l3k_chol_opts::block, out: the block size used; *bytes in: a limit as max_bytes with 0 = none, out: the bytes
+ *   the factor needs (set before the limit is applied).  Validates the graph as l3k_csr_create does.                           */
+typedef struct l3k_chol l3k_chol;
+typedef struct
+{
+    size_t max_bytes;
+    int    block; /* 0 = library's choice */
+} l3k_chol_opts;
+typedef struct
+{
+    int64_t n, n_active, n_blocks;
+    int     block;        /* NB in use                                                                    */
+    int64_t max_height;   /* largest H(K)                                                                 */
+    size_t  factor_bytes; /* of the block storage                                                         */
+    double  factor_flops; /* of one l3k_chol_factor                                                       */
+    double  update_flops; /* ... the share of its trailing updates (the matrix-core launches)             */
+    int64_t n_bad_pivots, first_bad_row; /* of the last l3k_chol_factor; first_bad_row = -1 if there was none */
+    int     factored;     /* the last l3k_chol_factor succeeded                                           */
+} l3k_chol_info;
+int l3k_chol_create(l3k_csr* A, const l3k_chol_opts* opts, l3k_chol** out);
+int l3k_chol_factor(l3k_chol* c);
+int l3k_chol_solve(l3k_chol* c, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols);
+int l3k_chol_info_get(const l3k_chol* c, l3k_chol_info* out);
+int l3k_chol_destroy(l3k_chol* c);
+int l3k_chol_order(int64_t n, const int64_t* row_ptr, const int32_t* col_ind, int32_t* perm_out, int32_t* heights_out, int* nb,
+                   int64_t* n_active, size_t* bytes);
+
 /* ---- CSR sparsity graph of a mesh, built on the device -------------------------------------------------------------------
  * computeLocalGraph of the reference (algsys/SparsityGraph.hpp:26-81: rows over-allocated, filled with duplicates, then sorted
  * and de-duplicated) in front of makeSparsityGraph (:299), for one rank: the d_row_ptr / d_col_ind that l3k_assembled_scatter,

@@ -721,6 +721,45 @@ private:
     bool          m_owner{};
 };
 
+// The sparse direct solver on a single-rank CSR operator (l3k_chol_*): band Cholesky for the symmetric positive definite systems
+// of the assembled path, where the reference solves with Amesos2 (alg_sys.solve(Klu2{}) / Lapack{}, solve/Amesos2Solvers.hpp:18-32).
+// The constructor runs the symbolic phase (host) and throws on a structurally unsymmetric graph or a factor above max_bytes
+// (0 = 8 GiB); block: 0 = chosen, 32 or 64.  The operator (a CsrOperator, or the l3k_csr of a closed AssembledSystem) must outlive
+// the object.  RAII, move-only.
+//   factor   ~ numericFactorization of the operator's current values; throws "matrix is not positive definite" (see info)
+//   solve    ~ X <- A^-1 B on the rows that store entries, ncols columns; B and X may be the same buffer
+//   info     ~ n, n_active, n_blocks, block, max_height, factor_bytes, factor_flops, n_bad_pivots, first_bad_row, factored
+class Cholesky
+{
+public:
+    explicit Cholesky(l3k_csr* A, size_t max_bytes = 0, int block = 0)
+    {
+        const l3k_chol_opts o{max_bytes, block};
+        check(l3k_chol_create(A, &o, &m_chol));
+    }
+    explicit Cholesky(const CsrOperator& A, size_t max_bytes = 0, int block = 0) : Cholesky{A.get(), max_bytes, block} {}
+    Cholesky(const Cholesky&)            = delete;
+    Cholesky& operator=(const Cholesky&) = delete;
+    Cholesky(Cholesky&& o) noexcept : m_chol{o.m_chol} { o.m_chol = nullptr; }
+    ~Cholesky() { l3k_chol_destroy(m_chol); }
+    void factor() { check(l3k_chol_factor(m_chol)); }
+    void solve(const double* d_b, double* d_x) const { check(l3k_chol_solve(m_chol, d_b, 0, d_x, 0, 1)); }
+    void solve(const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols) const
+    {
+        check(l3k_chol_solve(m_chol, d_b, ldb, d_x, ldx, ncols));
+    }
+    l3k_chol_info info() const
+    {
+        l3k_chol_info i{};
+        check(l3k_chol_info_get(m_chol, &i));
+        return i;
+    }
+    l3k_chol* get() const { return m_chol; }
+
+private:
+    l3k_chol* m_chol{};
+};
+
 // The CSR sparsity graph of a mesh over its local dofs, built on the device: computeLocalGraph in front of makeSparsityGraph
 // (algsys/SparsityGraph.hpp:26-81, :299) for one rank.  field_inds strictly ascending, empty = all dofs of the node; kind
 // L3K_GRAPH_FULL or L3K_GRAPH_CONDENSED (primary nodes only, hexes).  The mesh must outlive the object.

@@ -66,6 +66,18 @@ class CsrInfo(C.Structure):
                 ("mean_row_len", C.c_double), ("lanes_per_row", C.c_int)]
 
 
+class CholOpts(C.Structure):
+    """l3k_chol_opts: the memory limit of the factor (0 = 8 GiB) and the block size (0 = chosen, 32 or 64)"""
+    _fields_ = [("max_bytes", C.c_size_t), ("block", C.c_int)]
+
+
+class CholInfo(C.Structure):
+    """l3k_chol_info: sizes of the symbolic phase and the outcome of the last numeric factorisation"""
+    _fields_ = [("n", C.c_int64), ("n_active", C.c_int64), ("n_blocks", C.c_int64), ("block", C.c_int), ("max_height", C.c_int64),
+                ("factor_bytes", C.c_size_t), ("factor_flops", C.c_double), ("update_flops", C.c_double),
+                ("n_bad_pivots", C.c_int64), ("first_bad_row", C.c_int64), ("factored", C.c_int)]
+
+
 class GraphInfo(C.Structure):
     """l3k_graph_info: the statistics of the one readback of l3k_graph_create"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
@@ -277,6 +289,12 @@ SIGNATURES = {
                                          C.POINTER(CgResult)]),
     "l3k_csr_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
     "l3k_csr_pcg_solve_cheb": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_chol_create": (C.c_int, [_vp, C.POINTER(CholOpts), C.POINTER(_vp)]),
+    "l3k_chol_factor": (C.c_int, [_vp]),
+    "l3k_chol_solve": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int]),
+    "l3k_chol_info_get": (C.c_int, [_vp, C.POINTER(CholInfo)]),
+    "l3k_chol_destroy": (C.c_int, [_vp]),
+    "l3k_chol_order": (C.c_int, [C.c_int64, c_int64_p, c_int32_p, c_int32_p, c_int32_p, c_int_p, c_int64_p, C.POINTER(C.c_size_t)]),
     "l3k_graph_create": (C.c_int, [_vp, C.c_int, c_int_p, C.c_int, C.POINTER(_vp)]),
     "l3k_graph_info_get": (C.c_int, [_vp, C.POINTER(GraphInfo)]),
     "l3k_graph_fill": (C.c_int, [_vp, _vp, _vp]),

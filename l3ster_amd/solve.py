@@ -690,3 +690,81 @@ def _pcg_distributed_native(op, b, x, minv, opts, precond, throw_on_fail):
         if cheb is not None and cheb is not precond:
             cheb.close()
     return _from_c([res], throw_on_fail)[0]
+
+
+class CholeskySolver:
+    """Handle of l3k_chol_create: the sparse direct solver on a single-rank system.CsrOperator -- the one AssembledSystem.end()
+    returns included -- where the reference uses Amesos2 (Klu2 / Lapack, solve/Amesos2Solvers.hpp:18-32).  Band Cholesky: the
+    matrix is taken as symmetric positive definite (what the assembled path produces once the Dirichlet conditions are applied);
+    only its lower triangle, after a reverse Cuthill-McKee ordering, is read.  Creation runs the symbolic phase on the host and
+    refuses a structurally unsymmetric graph and a factor above max_bytes (0 = 8 GiB); block = 0 (chosen), 32 or 64.  factor()
+    reads A's current values: a time loop assembles again and calls it again.  Rows of A that store nothing (the internal dofs of
+    a condensed system) are left alone.  Factor and solve are bitwise reproducible.  A is kept alive here."""
+
+    def __init__(self, A, max_bytes=0, block=0):
+        from . import capi
+        from .system import CsrOperator, DistributedCsrOperator
+        if isinstance(A, DistributedCsrOperator):
+            raise capi.L3KError("CholeskySolver: a DistributedCsrOperator is refused: the direct solver works on the matrix of one "
+                                "rank; solve a partitioned system with solve.pcg_distributed")
+        if not isinstance(A, CsrOperator):
+            raise capi.L3KError("CholeskySolver takes a system.CsrOperator (AssembledSystem.end() returns one)")
+        self.A, self.n = A, A.n
+        self._h = C.c_void_p()
+        opts = capi.CholOpts(int(max_bytes), int(block))
+        capi.check(capi.load().l3k_chol_create(A._h, C.byref(opts), C.byref(self._h)))
+
+    @property
+    def info(self):
+        """n, n_active, n_blocks, block, max_height, factor_bytes, factor_flops, update_flops, n_bad_pivots, first_bad_row,
+        factored (l3k_chol_info)"""
+        import types
+        from . import capi
+        i = capi.CholInfo()
+        capi.check(capi.load().l3k_chol_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.CholInfo._fields_})
+
+    def factor(self):
+        """The numeric factorisation of A's current values (l3k_chol_factor); raises "matrix is not positive definite" with the
+        counts in .info"""
+        from . import capi
+        capi.check(capi.load().l3k_chol_factor(self._h))
+        return self
+
+    def solve(self, b, x=None):
+        """x <- A^-1 b on the rows of A that store entries; b, x: 1-D vectors over the n rows or (ncols, ld >= n) multivectors
+        with contiguous rows, x = None: in place of b (l3k_chol_solve).  The other rows of x keep their values."""
+        from . import capi
+        x = b if x is None else x
+        B, X = (b[None, :], x[None, :]) if b.dim() == 1 and x.dim() == 1 else (b, x)
+        if B.dim() != 2 or X.dim() != 2 or B.shape[0] != X.shape[0] or B.shape[1] < self.n or X.shape[1] < self.n:
+            raise capi.L3KError("b and x must have the same number of columns and at least n rows")
+        if B.dtype != torch.float64 or X.dtype != torch.float64 or B.stride(1) != 1 or X.stride(1) != 1:
+            raise capi.L3KError("b and x are float64 with contiguous rows")
+        ldb = B.stride(0) if B.shape[0] > 1 else max(B.shape[1], 1)
+        ldx = X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1)
+        capi.check(capi.load().l3k_chol_solve(self._h, C.c_void_p(B.data_ptr()), ldb, C.c_void_p(X.data_ptr()), ldx, B.shape[0]))
+        return x
+
+    def close(self):
+        if getattr(self, "_h", None):
+            from . import capi
+            capi.load().l3k_chol_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+
+def direct_solve(A, b, x, max_bytes=0):
+    """The reference's solver.solve(A, b, x) with a direct solver: symbolic phase, numeric factorisation and solve in one call.
+    Keep a CholeskySolver instead where the matrix, or its graph, serves more than one solve."""
+    solver = CholeskySolver(A, max_bytes)
+    try:
+        solver.factor().solve(b, x)
+    finally:
+        solver.close()
+    return x
