@@ -1283,6 +1283,70 @@ int l3k_meshfile_load(const char* path, size_t part, int order, l3k_meshfile_par
 int l3k_meshfile_part_get(const l3k_meshfile_part* part, l3k_meshfile_part_desc* out); /* pointers live as long as part */
 int l3k_meshfile_part_destroy(l3k_meshfile_part* part);
 
+/* ---- ParaView export: .vtu / .pvtu files of a solution (post/VtkExport.hpp) -------------------------------------------------------
+ * PvtuExporter{comm, mesh} + ExportDefinition + exportSolution (:16-39, :524-549).  Every rank writes `<path without extension>_<rank>.vtu`
+ * (makeVtuFileName :498-505), rank 0 also `<path without extension>.pvtu` (:586-596) naming one piece per rank by its stem; no rank
+ * talks to another: the caller passes rank and n_ranks.  Missing parent directories are created (:544).
+ * The .vtu (makeDataDescription :618-691): UnstructuredGrid, version 1.0, LittleEndian, header_type UInt64, one Piece of the rank's
+ * local nodes (owned + ghost, getNNodes()) and sum p^d linear sub-cells; every DataArray is format="appended" with its offset into one
+ * <AppendedData encoding="base64"> block that starts with `_`: Position (Float64 x 3, z = +0.0 on quads; makeCoordsSerialized :365-394),
+ * connectivity, offsets (UInt32), types (UInt8: 12 hexes, 9 quads; serializeTopology :304-363), then one Float64 array per field group.
+ * Each array is ONE base64 stream of `uint64 payload bytes || payload`, standard alphabet, `=` padding at the array's end only:
+ * 4 * ceil((8 + bytes) / 3) text bytes (util/Base64.hpp:219-226).
+ * Sub-cells (serializeElementSubtopo :252-285): an order-p element gives p^d cells over its lexicographic node grid, elements in mesh
+ * order, sub-cells layer / row / column, vertices base, +1, +n+1, +n (quads; hexes: the same four one layer up after them), entries are
+ * local node indices; offsets = 2^d, 2 * 2^d, ...
+ * Field groups (encodeField :450-466): a group names 1, 2 or 3 rows of the SoA field storage (n_fields, ld); 1 row = 1 component, 2 or
+ * 3 rows = 3 components node-interleaved, the third +0.0 for a group of 2.
+ * PointData attributes, in both files: Scalars = the first 1-component group, Vectors = the first 3-component group, Scalars first.
+ * (The reference's .pvtu loop :117-143 labels a second vector group as Scalars when there is no scalar group; not reproduced.)
+ * Coordinates of a node shared by several elements come from the LOWEST local element that contains it (the reference: whichever
+ * thread stores last, :378-388), so two creations give the same bytes.
+ *
+ * l3k_vtk_create runs the coordinate and topology kernels, encodes the four mesh sections on the device and keeps them as host text
+ * (m_encoded_coords / m_encoded_topo, :95); an export encodes the field groups only, chunk by chunk through two device and two
+ * pinned host buffers of opts->chunk_bytes text bytes (0 = default; rounded down to a multiple of 16, at least 16): the host writes
+ * chunk k while chunk k + 1 is encoded and copied.  The calls are synchronous: the files are complete when l3k_vtk_export returns.
+ * Refusals (-1, nothing written): null arguments; a group of 0 or more than 3 rows ("Field groupings must have size 1 (scalar), 2 (2D),
+ * or 3 (3D)", :454-455); a row index >= n_fields ("Out of bounds index", :536-537); ld < local nodes; a group name that is empty or
+ * contains " < > &; rank outside [0, n_ranks); a path whose directory cannot be created; more than 2^32 - 1 local nodes or
+ * connectivity entries (the reference overflows its UInt32 arrays silently).  A file that could not be completed is removed.
+ * Out of scope: writes that outlive the call (flushWriteQueue :712-717), updateNodeCoords (:566-571; meshes here are immutable:
+ * create a new exporter), line elements, cell data, compression, .pvd series, MPI-IO.                                               */
+typedef struct l3k_vtk l3k_vtk;
+typedef struct
+{
+    size_t chunk_bytes; /* text bytes per pipeline chunk; 0 = default */
+} l3k_vtk_opts;
+typedef struct
+{
+    int      dim, order;
+    int64_t  n_points, n_cells, n_conn; /* local nodes, sub-cells, connectivity entries                          */
+    uint64_t raw_bytes[4];              /* payload of Position, connectivity, offsets, types                     */
+    uint64_t encoded_bytes[4];          /* ... their text                                                        */
+    size_t   chunk_bytes;               /* of an exporter: the chunk in use (not above the largest array's text) */
+    int      store_bytes;               /* of an exporter: text bytes a lane of the encoder stores at once       */
+} l3k_vtk_info;
+/* host only: getLocalTopoSize :291-302 and the section sizes of serializeTopology / makeCoordsSerialized */
+int l3k_vtk_sizes(int dim, int order, int64_t n_elems, int64_t n_nodes, l3k_vtk_info* out);
+/* util::encodeAsBase64 (util/Base64.hpp) of `uint64 n_bytes || payload` on the device, the kernel on its own: d_payload 8-byte
+ * aligned, d_text 16-byte aligned with text_capacity >= 4 * ceil((8 + n_bytes) / 3); queued on the context's stream */
+int l3k_vtk_encode(l3k_ctx* ctx, const void* d_payload, uint64_t n_bytes, char* d_text, uint64_t text_capacity);
+/* PvtuExporter::PvtuExporter :524-530 (updateNodeCoords + initTopo) */
+int l3k_vtk_create(l3k_mesh* mesh, const l3k_vtk_opts* opts, l3k_vtk** out);
+int l3k_vtk_info_get(const l3k_vtk* vtk, l3k_vtk_info* out);
+int l3k_vtk_destroy(l3k_vtk* vtk);
+/* PvtuExporter::exportSolution :532-549.  names [n_groups]; n_comps [n_groups] rows per group; comp_inds: the groups' row indices one
+ * group after the other; d_fields: SoA (n_fields, ld) on the device */
+int l3k_vtk_export(l3k_vtk* vtk, const char* path, int rank, int n_ranks, int n_groups, const char* const* names, const int* n_comps,
+                   const int* comp_inds, const double* d_fields, size_t ld, int n_fields);
+/* host only: makePvtuFileContents :170-182 and makeDataDescription :618-691 into buf (no terminator); *needed = the length; buf ==
+ * NULL: the size query.  encoded_mesh_bytes: the text bytes of Position, connectivity, offsets, types */
+int l3k_vtk_pvtu_text(const char* path, int n_ranks, int n_groups, const char* const* names, const int* n_comps, char* buf,
+                      size_t capacity, size_t* needed);
+int l3k_vtk_vtu_header_text(int64_t n_points, int64_t n_cells, const uint64_t* encoded_mesh_bytes, int n_groups, const char* const* names,
+                            const int* n_comps, char* buf, size_t capacity, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

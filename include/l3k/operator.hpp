@@ -19,6 +19,7 @@
 //       AssembledSystem(mesh, halo, ...) ~ algsys::AssembledSystem on one rank of a partitioned mesh
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
 //   l3k::computeIntegral / computeNormL2 ~ post/Integral.hpp:113-128, post/NormL2.hpp:31-62 (one rank)
+//   l3k::ExportDefinition / PvtuExporter ~ post/VtkExport.hpp:16-97: .vtu / .pvtu files from the field storage on the device
 // Errors: the reference throws std::runtime_error from util::throwingAssert (util/Assertion.hpp:88-95); so does this
 // wrapper, with the text of l3k_last_error().  RAII handles, no torch, no other dependency than l3k.h + the HIP runtime
 // of the caller for device memory.
@@ -30,6 +31,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include <span>
 #include <stdexcept>
 #include <string>
@@ -1004,6 +1006,74 @@ public:
 
 private:
     l3k_meshfile_part* m_part = nullptr;
+};
+
+// ExportDefinition (post/VtkExport.hpp:16-39): a file name and named groups of 1, 2 or 3 rows of the SoA field storage
+class ExportDefinition
+{
+public:
+    struct FieldDef
+    {
+        std::string        name;
+        std::vector< int > inds;
+    };
+    explicit ExportDefinition(std::string file_name) : m_file_name{std::move(file_name)} {}
+    void defineField(std::string name, std::span< const int > inds)
+    {
+        m_defs.push_back(FieldDef{std::move(name), {inds.begin(), inds.end()}});
+    }
+    void               defineField(std::string name, std::initializer_list< int > inds) { defineField(std::move(name), std::span{inds}); }
+    const std::string& fileName() const { return m_file_name; }
+    auto               begin() const { return m_defs.begin(); }
+    auto               end() const { return m_defs.end(); }
+    size_t             size() const { return m_defs.size(); }
+
+private:
+    std::string             m_file_name;
+    std::vector< FieldDef > m_defs;
+};
+
+// PvtuExporter (post/VtkExport.hpp:41-97) of one rank's DeviceMesh (l3k_vtk_*): the constructor computes the node coordinates and
+// the sub-cell topology on the device and keeps their text; exportSolution writes `<name>_<rank>.vtu` and, on rank 0, `<name>.pvtu`
+// from the SoA field storage d_fields (n_fields, ld) on the device.  Where the reference takes the communicator, this takes rank and
+// size: no rank talks to another.  The files are complete on return (no write queue, hence no flushWriteQueue); meshes are immutable
+// (no updateNodeCoords: create a new exporter).  RAII, move-only; the mesh must outlive the object.
+class PvtuExporter
+{
+public:
+    explicit PvtuExporter(const DeviceMesh& mesh, int rank = 0, int n_ranks = 1, size_t chunk_bytes = 0) : m_rank{rank}, m_n_ranks{n_ranks}
+    {
+        const l3k_vtk_opts o{chunk_bytes};
+        check(l3k_vtk_create(mesh.get(), &o, &m_vtk));
+    }
+    PvtuExporter(const PvtuExporter&)            = delete;
+    PvtuExporter& operator=(const PvtuExporter&) = delete;
+    PvtuExporter(PvtuExporter&& o) noexcept : m_vtk{o.m_vtk}, m_rank{o.m_rank}, m_n_ranks{o.m_n_ranks} { o.m_vtk = nullptr; }
+    ~PvtuExporter() { l3k_vtk_destroy(m_vtk); }
+    void exportSolution(const ExportDefinition& export_def, const double* d_fields, size_t ld, int n_fields) const
+    {
+        std::vector< const char* > names;
+        std::vector< int >         n_comps, inds;
+        for (const auto& def : export_def)
+        {
+            names.push_back(def.name.c_str());
+            n_comps.push_back(int(def.inds.size()));
+            inds.insert(inds.end(), def.inds.begin(), def.inds.end());
+        }
+        check(l3k_vtk_export(m_vtk, export_def.fileName().c_str(), m_rank, m_n_ranks, int(names.size()), names.data(), n_comps.data(),
+                             inds.data(), d_fields, ld, n_fields));
+    }
+    l3k_vtk_info info() const
+    {
+        l3k_vtk_info i{};
+        check(l3k_vtk_info_get(m_vtk, &i));
+        return i;
+    }
+    l3k_vtk* get() const { return m_vtk; }
+
+private:
+    l3k_vtk* m_vtk{};
+    int      m_rank{}, m_n_ranks{};
 };
 } // namespace l3k
 #endif

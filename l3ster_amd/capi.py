@@ -110,6 +110,18 @@ class AsmDistInfo(C.Structure):
     _fields_ = [("n_owned", C.c_int64), ("n_ghost", C.c_int64), ("dist", C.c_void_p)]
 
 
+class VtkOpts(C.Structure):
+    """l3k_vtk_opts: text bytes per pipeline chunk of the ParaView export (0 = default)"""
+    _fields_ = [("chunk_bytes", C.c_size_t)]
+
+
+class VtkInfo(C.Structure):
+    """l3k_vtk_info: points, sub-cells, connectivity entries, raw and encoded bytes of Position / connectivity / offsets / types"""
+    _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_points", C.c_int64), ("n_cells", C.c_int64), ("n_conn", C.c_int64),
+                ("raw_bytes", C.c_uint64 * 4), ("encoded_bytes", C.c_uint64 * 4), ("chunk_bytes", C.c_size_t),
+                ("store_bytes", C.c_int)]
+
+
 class MeshDesc(C.Structure):
     _fields_ = [("dim", C.c_int), ("order", C.c_int), ("n_elems", C.c_int64), ("n_interior_elems", C.c_int64),
                 ("elem_nodes", c_uint32_p), ("elem_verts", c_double_p), ("n_owned_nodes", C.c_int64),
@@ -350,6 +362,17 @@ SIGNATURES = {
     "l3k_meshfile_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(_vp)]),
     "l3k_meshfile_part_get": (C.c_int, [_vp, C.POINTER(MeshFilePartDesc)]),
     "l3k_meshfile_part_destroy": (C.c_int, [_vp]),
+    "l3k_vtk_sizes": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(VtkInfo)]),
+    "l3k_vtk_encode": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64]),
+    "l3k_vtk_create": (C.c_int, [_vp, C.POINTER(VtkOpts), C.POINTER(_vp)]),
+    "l3k_vtk_info_get": (C.c_int, [_vp, C.POINTER(VtkInfo)]),
+    "l3k_vtk_destroy": (C.c_int, [_vp]),
+    "l3k_vtk_export": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), c_int_p, c_int_p, _vp, C.c_size_t,
+                                 C.c_int]),
+    "l3k_vtk_pvtu_text": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), c_int_p, _vp, C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
+    "l3k_vtk_vtu_header_text": (C.c_int, [C.c_int64, C.c_int64, c_uint64_p, C.c_int, C.POINTER(C.c_char_p), c_int_p, _vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
 }
 
 _lib = None
