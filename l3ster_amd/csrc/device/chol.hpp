@@ -22,10 +22,14 @@ using mfma_d4         = __attribute__((ext_vector_type(4))) double;
 // status[0]: non-positive or non-finite pivots met, status[1]: the row (in the permuted numbering) of the first
 constexpr int status_words = 2;
 
-// the device translation units are built with -ffinite-math-only, which folds the usual tests: the exponent bits decide
-__device__ __forceinline__ bool notFinite(double v)
+// Is the pivot with these bits positive and finite?  The device translation units are built with -ffinite-math-only, which folds
+// the usual tests -- and folds a test of the exponent bits as well once it sits behind a parameter of type double (the compiler
+// marks such a parameter as never NaN or Inf: the pivot test came out as !(0 < d), which takes +Inf for a good pivot).  So the
+// decision is made on an integer that never was a double parameter: good are the bits of +denorm_min .. +DBL_MAX, that is
+// 1 .. 0x7fefffffffffffff; 0, the sign bit, and an exponent of all ones (Inf, NaN) fall outside
+__device__ __forceinline__ bool goodPivotBits(unsigned long long bits)
 {
-    return (static_cast< unsigned long long >(__double_as_longlong(v)) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+    return bits - 1ull < 0x7fefffffffffffffull;
 }
 
 // ---- fill: storage <- lower triangle of P A P^T (the storage was zeroed); the padding of the last block <- identity
@@ -67,7 +71,7 @@ static __global__ __launch_bounds__(threads) void cholDiagKernel(double* __restr
     {
         __syncthreads();
         double     d   = s[c * NB + c];
-        const bool bad = notFinite(d) || d <= 0.;
+        const bool bad = !goodPivotBits(__builtin_bit_cast(unsigned long long, d));
         if (bad)
         {
             d = 1.;
