@@ -1202,7 +1202,11 @@ int l3k_boundary_match(l3k_ctx* ctx, int dim, int64_t n_elems, const uint32_t* c
  * node spacing is legal and merely slow.
  * Errors (-1, l3k_last_error names the call): dim outside {2, 3}, order outside 1..8, negative counts, null arrays with non-zero
  * counts, a listed side whose element index or side is "outside the mesh", a vertex of a listed side or a translation that is not
- * finite, a tolerance that is not finite and positive.
+ * finite, a tolerance that is not finite and positive; and a box of the destination vertices or a tolerance from which no grid can
+ * be made, whatever the counts: a box whose extent is not finite (vertices at -1e308 and 1e308), a tolerance whose double is not
+ * finite, a cell edge h = max(2 tolerance, extent / 2^20) for which 1 / h is zero or not finite (a subnormal tolerance on a box of
+ * one point) or for which the cell below the box has no finite origin.  The message names the box or the tolerance; as with every
+ * error of this call, nothing is launched and nothing is written to the outputs.
  *
  * l3k_periodic_merge (host only, no context).  pair_a / pair_b: n_pairs node pairs, e.g. concatenated from several
  * l3k_periodic_match calls -- all computed on the UNMERGED numbering (periodic in x and in y on a square: the four corner nodes

@@ -13,6 +13,8 @@
 // listed side nodes.  Work per source node grows with the number of destination nodes in the 3^dim cells around it: a handful as
 // long as the tolerance is below the node spacing; a tolerance above the node spacing is legal and merely slow (every source node
 // then walks all the destination nodes within 3 h of it).  Integer and fp64 work with no reuse: plain one-thread-per-item kernels, no LDS.
+// The box of the destination vertices and the grid over it are made on the host (host/periodic.hpp), which refuses a box or a
+// tolerance that gives no grid before anything is launched.
 #include "objects.hpp"
 
 #include "device/periodic.hpp"
@@ -211,37 +213,19 @@ extern "C" int l3k_periodic_match(l3k_ctx* ctx, int dim, int order, int64_t n_el
         setError("l3k_periodic_match: %s", wrong);
         return -1;
     }
-    // the destination nodes are convex combinations of the vertices of their sides' elements: the box of those vertices holds them
-    const int nv = 1 << dim;
-    double    lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
-    for (int64_t f = 0; f < n_src + n_dst; ++f)
+    // the vertices of the listed sides, the box of the destination vertices and the grid over it: on the host, in a unit that is not
+    // finite-math, which refuses what gives no grid before anything is launched or written
+    Grid grid;
+    if (const std::string wrong = l3k::host::periodicBoxAndGrid(dim, elem_verts, n_src, src_elem, n_dst, dst_elem, tolerance, &grid);
+        !wrong.empty())
     {
-        const bool    is_dst = f >= n_src;
-        const double* v      = elem_verts + (is_dst ? dst_elem[f - n_src] : src_elem[f]) * nv * 3;
-        for (int c = 0; c < nv; ++c)
-            if (!l3k::host::allFinite(v + c * 3, size_t(dim)))
-            {
-                setError("l3k_periodic_match: element %lld has a vertex that is not finite",
-                         (long long)(is_dst ? dst_elem[f - n_src] : src_elem[f]));
-                return -1;
-            }
-        for (int c = 0; c < nv; ++c)
-            for (int a = 0; a < dim; ++a)
-            {
-                const double x = v[c * 3 + a];
-                if (is_dst)
-                {
-                    const bool first = f == n_src && c == 0;
-                    lo[a]            = first || x < lo[a] ? x : lo[a];
-                    hi[a]            = first || x > hi[a] ? x : hi[a];
-                }
-            }
+        setError("l3k_periodic_match: %s", wrong.c_str());
+        return -1;
     }
     *n_pairs = *n_unmatched = *n_ambiguous = 0;
     *first_unmatched                       = -1;
     if (n_src == 0)
         return 0;
-    const Grid grid = makeGrid(dim, lo, hi, tolerance);
 
     L3K_HIP(hipSetDevice(ctx->device));
     hipStream_t       s   = ctx->stream;

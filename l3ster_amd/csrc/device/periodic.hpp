@@ -1,5 +1,6 @@
 // periodic.hpp -- the per-item work of l3k_periodic_match (api_periodic.hip), one function per kernel: plain one-thread-per-item
-// code that also compiles for the host, so that a stand-alone program can walk it over a mesh on the CPU.
+// code that also compiles for the host, so that a stand-alone program can walk it over a mesh on the CPU
+// (tests/cpp/periodic_walk.cpp).
 #ifndef L3K_DEVICE_PERIODIC_HPP
 #define L3K_DEVICE_PERIODIC_HPP
 
@@ -13,32 +14,15 @@ namespace l3k::periodic
 inline constexpr int      cell_bits = 21; // per axis: 3 * 21 = 63 bits of key
 inline constexpr uint32_t no_match  = 0xffffffffu;
 
-// The uniform grid the destination nodes are binned on: origin one cell below the box of the destination vertices, m cells per axis
+// The uniform grid the destination nodes are binned on: origin one cell below the box of the destination vertices, m cells per axis.
+// It is made on the host, in a unit without -ffinite-math-only (host/periodic.hpp: periodicMakeGrid), which refuses a box or a
+// tolerance that gives no finite lo, inv_h > 0 and m <= 2^cell_bits.
 struct Grid
 {
     double  lo[3];
     double  inv_h;
     int64_t m;
 };
-
-// box_lo / box_hi: a box that holds every destination node (they are convex combinations of the vertices of their sides).  The cell
-// edge h is at least 2 tolerance, so that a partner lies in the source node's own or an adjacent cell, and coarse enough for
-// cell_bits bits per axis with one cell of margin on either side.
-inline Grid makeGrid(int dim, const double* box_lo, const double* box_hi, double tolerance)
-{
-    double extent = 0.;
-    for (int a = 0; a < dim; ++a)
-        extent = box_hi[a] - box_lo[a] > extent ? box_hi[a] - box_lo[a] : extent;
-    double h = 2. * tolerance > extent / double(1 << 20) ? 2. * tolerance : extent / double(1 << 20);
-    while (!(std::ceil(extent / h) + 3. < double(int64_t(1) << cell_bits)))
-        h *= 2.;
-    Grid g;
-    for (int a = 0; a < 3; ++a)
-        g.lo[a] = a < dim ? box_lo[a] - h : 0.;
-    g.inv_h = 1. / h;
-    g.m     = int64_t(std::ceil(extent / h)) + 3;
-    return g;
-}
 
 // element-local node of side node q of `side` (sides as for l3k_bnd_create: the last axis first, low side before high side; the
 // side's nodes in the lexicographic order of the remaining axes), as its index per axis

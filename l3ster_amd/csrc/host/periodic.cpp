@@ -5,13 +5,15 @@
 // lowest node id, the kept nodes are ranked in ascending old id, and elem_nodes is rewritten through that map.  Only non-internal
 // nodes can be paired, a representative is never above the nodes it stands for, and ranks ascend with the old ids, so the
 // [non-internal | internal, contiguous per element] numbering l3k_mesh_create, the condensation and the partitioner rely on
-// survives.  Also the finiteness checks of l3k_periodic_match (host/periodic.hpp).
+// survives.  Also the finiteness checks of l3k_periodic_match and the construction of its box and grid (host/periodic.hpp): this
+// unit is not built with -ffinite-math-only, so a box or a tolerance the grid cannot be made from is refused here.
 #include "host/periodic.hpp"
 #include "l3k.h"
 
 #include <cmath>
 #include <cstdint>
 #include <new>
+#include <string>
 #include <vector>
 
 namespace l3k::dev
@@ -35,6 +37,74 @@ const char* periodicCheckReals(int dim, const double* translation, const double*
     if (!(std::isfinite(*tolerance) && *tolerance > 0.))
         return "the tolerance must be finite and positive";
     return nullptr;
+}
+
+std::string periodicMakeGrid(int dim, const double* box_lo, const double* box_hi, double tolerance, l3k::periodic::Grid* grid)
+{
+    using l3k::periodic::cell_bits;
+    double extent = 0.;
+    for (int a = 0; a < dim; ++a)
+    {
+        const double e = box_hi[a] - box_lo[a];
+        if (!std::isfinite(e)) // finite vertices, e.g. -1e308 and 1e308, whose difference overflows
+            return "the box of the destination vertices has an extent that is not finite";
+        extent = e > extent ? e : extent;
+    }
+    const double two_tol = 2. * tolerance;
+    if (!std::isfinite(two_tol))
+        return "the tolerance is too large: twice the tolerance is not finite";
+    double h = two_tol > extent / double(1 << 20) ? two_tol : extent / double(1 << 20);
+    // h >= extent / 2^20 leaves at most 2^20 + 3 cells: the doubling guards the rounding of the quotient, a few turns at the most
+    const double cell_limit = double(int64_t(1) << cell_bits);
+    for (int turn = 0; !(std::ceil(extent / h) + 3. < cell_limit); ++turn)
+    {
+        if (turn == 64 || !std::isfinite(h))
+            return "the box of the destination vertices and the tolerance give no finite cell edge";
+        h *= 2.;
+    }
+    const double inv_h = 1. / h;
+    if (!std::isfinite(h) || !(h > 0.))
+        return "the box of the destination vertices and the tolerance give no finite cell edge";
+    if (!std::isfinite(inv_h))
+        return "the tolerance is too small: the inverse of the cell edge is not finite";
+    if (inv_h == 0.)
+        return "the tolerance or the box of the destination vertices is too large: the inverse of the cell edge is zero";
+    for (int a = 0; a < 3; ++a)
+    {
+        grid->lo[a] = a < dim ? box_lo[a] - h : 0.;
+        if (!std::isfinite(grid->lo[a]))
+            return "the box of the destination vertices has no finite cell below it";
+    }
+    grid->inv_h = inv_h;
+    grid->m     = int64_t(std::ceil(extent / h)) + 3;
+    return {};
+}
+
+std::string periodicBoxAndGrid(int dim, const double* elem_verts, int64_t n_src, const int64_t* src_elem, int64_t n_dst,
+                               const int64_t* dst_elem, double tolerance, l3k::periodic::Grid* grid)
+{
+    const int nv = 1 << dim;
+    double    lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+    for (int64_t f = 0; f < n_src + n_dst; ++f)
+    {
+        const bool    is_dst = f >= n_src;
+        const int64_t e      = is_dst ? dst_elem[f - n_src] : src_elem[f];
+        const double* v      = elem_verts + e * nv * 3;
+        for (int c = 0; c < nv; ++c)
+            if (!allFinite(v + c * 3, size_t(dim)))
+                return "element " + std::to_string(e) + " has a vertex that is not finite";
+        if (!is_dst)
+            continue;
+        for (int c = 0; c < nv; ++c)
+            for (int a = 0; a < dim; ++a)
+            {
+                const double x     = v[c * 3 + a];
+                const bool   first = f == n_src && c == 0;
+                lo[a]              = first || x < lo[a] ? x : lo[a];
+                hi[a]              = first || x > hi[a] ? x : hi[a];
+            }
+    }
+    return periodicMakeGrid(dim, lo, hi, tolerance, grid);
 }
 } // namespace l3k::host
 

@@ -431,7 +431,8 @@ def periodic_match(ctx, mesh, src, dst, translation, tolerance=1e-12):
     """The destination node every source node is the image of (l3k_periodic_match; bcs/PeriodicBC.hpp): mesh supplies dim, order,
     elem_nodes and elem_verts; src and dst are (face_elem, face_side) lists of element sides; source node s matches destination
     node d iff |x_s + translation - x_d| < tolerance, the nearest wins, ties to the lowest id.  Returns (pair_src uint32 [n],
-    pair_dst uint32 [n], n_unmatched, n_ambiguous, first_unmatched), pairs ascending in the source node."""
+    pair_dst uint32 [n], n_unmatched, n_ambiguous, first_unmatched), pairs ascending in the source node.  L3KError for what the
+    call refuses (include/l3k.h), a box of the destination vertices or a tolerance from which no grid can be made among it."""
     en = np.ascontiguousarray(mesh.elem_nodes, dtype=np.uint32)
     ev = np.ascontiguousarray(mesh.elem_verts, dtype=np.float64)
     se, ss = _sides(*src)
@@ -540,7 +541,8 @@ class ElevatedMesh:
         boundary id: a new mesh in which every node of the source boundaries is the node of the destination boundaries it is the
         image of.  All definitions are matched on this (unmerged) mesh and merged at once, so the corners of a mesh periodic along
         several axes become one node.  Raises L3KError naming the definition and the lowest unmatched node when a source node has
-        no partner ("each node at X belonging to source must have a corresponding node at X + translation").
+        no partner ("each node at X belonging to source must have a corresponding node at X + translation"), and with the message
+        of l3k_periodic_match for a tolerance or a destination boundary it refuses (include/l3k.h).
         The new mesh is taken by everything that takes this one (DeviceMesh, MatrixFreeSystem, BoundaryTerm,
         partition.PartitionedMesh, solve.PMultigrid, SparsityGraph); it has the same elem_verts, face_elem / face_side, bnd_id,
         boundary_ids and elem_domain, new elem_nodes, n_owned_nodes, n_global_nodes and n_noninternal, and carries node_map (old
