@@ -9,7 +9,8 @@
 //
 // A system made by l3k_asm_create_condensed (quads) eliminates the element-internal dofs: the same pipeline, with the split kernel
 // of device/quad_condense.hpp in the scatter's place, a per-element store of the internal rows that l3k_asm_begin zeroes and
-// l3k_asm_end factors, and l3k_asm_recover / l3k_asm_schur_updates on the factored store.
+// l3k_asm_end factors, and l3k_asm_recover / l3k_asm_schur_updates on the factored store.  Scatter, split and
+// elimination put their entries into the CSR arrays by the one rule of device/csr_scatter.hpp.
 //
 // A system made by l3k_asm_create_dist lives on one rank's part of a partitioned mesh: the same arrays over the local dofs
 // [owned | ghost], filled by the same rank-local calls; l3k_asm_end is then collective and hands out a distributed operator
@@ -116,13 +117,6 @@ int64_t subBatch(size_t workspace_bytes, size_t per_system, int64_t count, int64
 }
 // the split of a sub-batch of a condensed system: primary block -> CSR arrays, internal rows -> the store (quad_condense.hpp);
 // d_elem_of: the elements of side systems (several of one element may share the launch: atomics), nullptr for element systems
-template < int U >
-int launchQuadSplitU(const l3k::dev::QuadSplitArgs& a, bool atomic, int64_t blocks, hipStream_t s)
-{
-    if (atomic)
-        return l3k::dev::launchKernel("quadSplitKernel", l3k::dev::quadSplitKernel< U, true >, dim3(unsigned(blocks)), dim3(64), 0, s, a);
-    return l3k::dev::launchKernel("quadSplitKernel", l3k::dev::quadSplitKernel< U, false >, dim3(unsigned(blocks)), dim3(64), 0, s, a);
-}
 int launchQuadSplit(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, const int64_t* d_elem_of, int64_t at, int64_t n, const double* d_K,
                     const double* d_F, unsigned long long* d_count, hipStream_t s)
 {
@@ -154,18 +148,16 @@ int launchQuadSplit(l3k_asm* A, const KernelTerm& t, const uint32_t* d_nodes, co
         a.slot[u] = int(std::lower_bound(A->field_inds.begin(), A->field_inds.end(), t.field_inds[u]) - A->field_inds.begin()); // (checkTerm: present)
     }
     const int64_t blocks = n * n1d * n1d; // (subBatch caps n)
-    switch (t.kp.n_unknowns)
+    const int rc = l3k::dev::withUnknowns< 8 >(t.kp.n_unknowns, [&](auto u) {
+        return l3k::dev::launchKernel< 0 >("quadSplitKernel", d_elem_of ? l3k::dev::quadSplitKernel< u(), true > : l3k::dev::quadSplitKernel< u(), false >,
+                                           dim3(unsigned(blocks)), dim3(64), 0, s, a);
+    });
+    if (rc == l3k::dev::not_instantiated)
     {
-    case 1: return launchQuadSplitU< 1 >(a, d_elem_of != nullptr, blocks, s);
-    case 2: return launchQuadSplitU< 2 >(a, d_elem_of != nullptr, blocks, s);
-    case 3: return launchQuadSplitU< 3 >(a, d_elem_of != nullptr, blocks, s);
-    case 4: return launchQuadSplitU< 4 >(a, d_elem_of != nullptr, blocks, s);
-    case 5: return launchQuadSplitU< 5 >(a, d_elem_of != nullptr, blocks, s);
-    case 6: return launchQuadSplitU< 6 >(a, d_elem_of != nullptr, blocks, s);
-    case 7: return launchQuadSplitU< 7 >(a, d_elem_of != nullptr, blocks, s);
-    case 8: return launchQuadSplitU< 8 >(a, d_elem_of != nullptr, blocks, s);
-    default: setError("l3k_asm_add: %d unknowns not supported (1..8)", t.kp.n_unknowns); return -1;
+        setError("l3k_asm_add: %d unknowns not supported (1..8)", t.kp.n_unknowns);
+        return -1;
     }
+    return rc;
 }
 // The quad route of both l3k_asm_add_* calls: the local systems [first, first + count) of a term -- Nd = NN U dofs each, their node
 // rows d_nodes[first + i] -- formed by form(at, n, d_K, d_F, d_flag) on the context's stream into one half of the object's pipeline

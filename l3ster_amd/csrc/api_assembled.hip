@@ -5,23 +5,29 @@
 // element matrices (the output of l3k_local_assemble, resident in HBM) is summed into the VALUES ARRAY of the caller's
 // CSR graph (local row pointers / sorted local column indices, i.e. what Tpetra::CrsGraph::getLocalRowPtrsDevice /
 // getLocalIndicesDevice hand out): the Tpetra side takes the finished values with one setAllValues, or one
-// sumIntoLocalValues per row batch -- not one call per element row.
+// sumIntoLocalValues per row batch -- not one call per element row.  How an entry finds its place in the graph, and what happens
+// to one that has none, is the rule of device/csr_scatter.hpp, which the three scatter kernels below share with the condensed ones.
 #include "objects.hpp"
+
+#include "device/csr_scatter.hpp"
+#include "device/launch.hpp"
 
 #include <cstdlib>
 
 namespace
 {
-struct ScatterArgs
+using l3k::dev::csrFind;
+using l3k::dev::csrHolds;
+using l3k::dev::csrLowerBound;
+using l3k::dev::launchKernel;
+using l3k::dev::withNodes1d;
+using l3k::dev::withUnknowns;
+
+struct ScatterArgs : l3k::dev::CsrSink // (the global system: row_ptr, col_ind, values, rhs, ldr, n_missing)
 {
     const uint32_t* elem_nodes;
     const uint8_t*  dirichlet; // per local dof, or null
     const double *  K, *F;
-    const int64_t*  row_ptr;
-    const int32_t*  col_ind;
-    double *        values, *rhs;
-    size_t          ldr;
-    unsigned long long* n_missing;
     int64_t         first, count;
     int             NN, dpn, n_rhs, skip_dirichlet, U_rt;
     int             field_inds[l3k::dev::max_unknowns];
@@ -52,45 +58,20 @@ __global__ __launch_bounds__(64) void assembledScatterPerEntryKernel(const Scatt
         const int64_t col = int64_t(en[j / a.U_rt]) * a.dpn + a.field_inds[j % a.U_rt];
         if (a.skip_dirichlet && a.dirichlet && a.dirichlet[col])
             continue;
-        int64_t lo = rb, hi = re; // first position with col_ind >= col
-        while (lo < hi)
-        {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.col_ind[mid] < col)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        if (lo < re && a.col_ind[lo] == col)
-            unsafeAtomicAdd(a.values + lo, Kr[j]);
+        const int64_t pos = csrLowerBound(a.col_ind, rb, re, col);
+        if (csrHolds(a.col_ind, re, pos, col))
+            unsafeAtomicAdd(a.values + pos, Kr[j]);
         else
-            ++missing; // (Tpetra's sumIntoLocalValues skips entries outside the graph and reports how many it took)
+            ++missing;
     }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
-}
-
-// first position in [lo, hi) with col_ind >= col
-__device__ __forceinline__ int64_t lowerBound(const int32_t* __restrict__ col_ind, int64_t lo, int64_t hi, int64_t col)
-{
-    while (lo < hi)
-    {
-        const int64_t mid = (lo + hi) >> 1;
-        if (col_ind[mid] < col)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
+    csrCountMissing(a, missing);
 }
 
 // One wave per (element, ROW NODE b): the U rows (b, u) of K_e, the lanes over the Nd consecutive ENTRIES of a row, so that a
 // wave-instruction reads 512 contiguous bytes of K_e and its atomic adds fall on runs of neighbouring CSR values (dense
 // 64-byte requests: the memory-side atomic units are a request-rate limit -- a first form with one column NODE per lane,
 // i.e. atomics at a stride of U values, ran at 0.6 x the rate of the per-entry kernel above although it searched 16 x less).
-// The position of an entry's column in the CSR row of (b, u = 0) is found by ONE binary search and reused for the rows
-// u = 1 .. U-1: the rows of one node carry the same columns in a finite-element graph; the candidate position is checked
-// against col_ind and a row without that structure falls back to its own search (same results).
+// Every column of the row, Dirichlet columns skipped on request; the search rule is that of device/csr_scatter.hpp.
 template < int U >
 __global__ __launch_bounds__(64) void assembledScatterKernel(const ScatterArgs a)
 {
@@ -99,39 +80,12 @@ __global__ __launch_bounds__(64) void assembledScatterKernel(const ScatterArgs a
     const int       b    = int(blockIdx.x - e * a.NN);
     const uint32_t* en   = a.elem_nodes + (a.first + e) * a.NN;
     const int       lane = threadIdx.x;
-    const int64_t   nb   = int64_t(en[b]) * a.dpn;
-    int64_t         row[U], rb[U], re[U];
-    bool            live[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-        row[u]  = nb + a.field_inds[u];
-        live[u] = !(a.skip_dirichlet && a.dirichlet && a.dirichlet[row[u]]);
-    }
+    l3k::dev::NodeRows< U > rows(int64_t(en[b]) * a.dpn, a.field_inds, a.dirichlet, a.skip_dirichlet);
     if (a.F && a.rhs)
-        for (int t = lane; t < a.n_rhs * U; t += 64) // (n_rhs * U may exceed the wave: e.g. 17 right-hand sides of 4 unknowns)
-        {
-            const int r = t / U, u = t - r * U;
-            bool      lv = false;
-            int64_t   rw = 0;
-#pragma unroll
-            for (int uu = 0; uu < U; ++uu) // (compile-time indexing of the per-unknown registers)
-                if (uu == u)
-                {
-                    lv = live[uu];
-                    rw = row[uu];
-                }
-            if (lv)
-                unsafeAtomicAdd(a.rhs + size_t(r) * a.ldr + rw, a.F[(e * a.n_rhs + r) * Nd + b * U + u]);
-        }
+        rows.addRhs(a, lane, a.n_rhs, a.F + e * a.n_rhs * Nd + b * U, Nd);
     if (!a.K || !a.values)
         return;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-        rb[u] = a.row_ptr[row[u]];
-        re[u] = a.row_ptr[row[u] + 1];
-    }
+    rows.loadRanges(a.row_ptr);
     const double* Kb      = a.K + (e * Nd + int64_t(b) * U) * Nd; // rows (b, 0 .. U-1)
     unsigned      missing = 0;
     for (int j = lane; j < Nd; j += 64)
@@ -140,30 +94,16 @@ __global__ __launch_bounds__(64) void assembledScatterKernel(const ScatterArgs a
         const int64_t col = int64_t(en[bp]) * a.dpn + a.field_inds[j - bp * U];
         if (a.skip_dirichlet && a.dirichlet && a.dirichlet[col])
             continue;
-        const int64_t rel = lowerBound(a.col_ind, rb[0], re[0], col) - rb[0]; // the entry's one search
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            if (!live[u])
-                continue;
-            int64_t pos = rb[u] + rel;
-            if (u > 0 && !(pos < re[u] && a.col_ind[pos] == col))
-                pos = lowerBound(a.col_ind, rb[u], re[u], col);
-            if (pos < re[u] && a.col_ind[pos] == col)
-                unsafeAtomicAdd(a.values + pos, Kb[int64_t(u) * Nd + j]);
-            else
-                ++missing; // (Tpetra's sumIntoLocalValues skips entries outside the graph and reports how many it took)
-        }
+        missing += rows.addEntry(a, col, [&](int u) { return Kb[int64_t(u) * Nd + j]; });
     }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
+    csrCountMissing(a, missing);
 }
 // The scatter for element matrices in the TILED layout of the assembly kernel (device/assemble.hpp, TILED): blocks
 // [u][u'][bx'][bz][bx][by][by'][bz'].  One wave per (element, row node b): for every row (b, u) the 4 n runs of n^2 doubles that
 // hold the row (one per (u', bx')) are read -- consecutive lanes, consecutive addresses -- and laid down in LDS in the row's
 // column order (b', u'), u' fastest: from there the lanes walk the row's consecutive entries exactly as assembledScatterKernel
-// does (dense atomic requests), and the CSR position of an entry is searched once, for the first live row of the node (kept
-// in LDS as an offset into the row), and re-used for the others after a check.
+// does (dense atomic requests).  The search rule of device/csr_scatter.hpp, with the first LIVE row of the node as the searched
+// one and the position it finds kept in LDS (relv, an offset into the row) as the guess for the others.
 template < int U, int N1 >
 __global__ __launch_bounds__(64) void assembledScatterTiledKernel(const ScatterArgs a)
 {
@@ -218,41 +158,21 @@ __global__ __launch_bounds__(64) void assembledScatterTiledKernel(const ScatterA
             int64_t pos;
             if (!have_rel)
             {
-                pos     = lowerBound(a.col_ind, rb, re, col);
+                pos     = csrLowerBound(a.col_ind, rb, re, col);
                 relv[j] = int32_t(pos - rb);
+                if (!csrHolds(a.col_ind, re, pos, col))
+                    pos = -1;
             }
             else
-            {
-                pos = rb + relv[j];
-                if (!(pos < re && a.col_ind[pos] == col))
-                    pos = lowerBound(a.col_ind, rb, re, col);
-            }
-            if (pos < re && a.col_ind[pos] == col)
+                pos = csrFind(a.col_ind, rb, re, rb + relv[j], col);
+            if (pos >= 0)
                 unsafeAtomicAdd(a.values + pos, rowv[j]);
             else
                 ++missing;
         }
         have_rel = true;
     }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
-}
-template < int U >
-int launchScatterTiled(const ScatterArgs& a, int N1, int64_t blocks, hipStream_t s)
-{
-    const size_t lds = size_t(a.NN) * U * (sizeof(double) + sizeof(int32_t));
-    switch (N1)
-    {
-    case 2: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 2 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 3: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 3 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 4: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 4 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 5: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 5 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 6: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 6 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 7: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 7 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    case 8: hipLaunchKernelGGL((assembledScatterTiledKernel< U, 8 >), dim3(unsigned(blocks)), dim3(64), lds, s, a); break;
-    default: return 1;
-    }
-    return 0;
+    csrCountMissing(a, missing);
 }
 } // namespace
 
@@ -300,23 +220,6 @@ __global__ __launch_bounds__(256) void tiledToRowMajorKernel(const double* __res
         const int bxp = bp % N1, byp = (bp / N1) % N1, bzp = bp / N2;
         out[o]        = rowbuf[((u * U + up) * N1 + bxp) * N2 + byp * N1 + bzp];
     }
-}
-template < int U >
-int launchTiledToRowMajorU(int N1, int64_t blocks, const double* Kt, double* K, hipStream_t s)
-{
-    const size_t lds = sizeof(double) * size_t(U) * U * N1 * N1 * N1;
-    switch (N1)
-    {
-    case 2: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 2 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 3: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 3 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 4: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 4 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 5: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 5 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 6: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 6 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 7: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 7 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    case 8: hipLaunchKernelGGL((tiledToRowMajorKernel< U, 8 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K); break;
-    default: return 1;
-    }
-    return 0;
 }
 // The x-major tiled layout -> the reference's row-major K_e, bitwise symmetric, in ONE pass over the matrix
 // (AssembleLocalSystem.hpp:168-182: getSystem returns the lower triangle mirrored).  The assembly kernels form K[i][j] and K[j][i]
@@ -405,32 +308,6 @@ __global__ __launch_bounds__(256) void tiledXToRowMajorSymKernel(const double* _
         __syncthreads();
     }
 }
-template < int U, int N1 >
-int launchTiledXOne(int64_t count, const double* Kt, double* K, hipStream_t s)
-{
-    constexpr size_t lds    = sizeof(double) * size_t(N1) * U * (N1 * N1 * U + 1);
-    if constexpr (lds > 64 * 1024) // (order 7 with 4 unknowns)
-        if (!l3k::dev::allowDynamicLds(reinterpret_cast< const void* >(&tiledXToRowMajorSymKernel< U, N1 >), lds))
-            return 1;
-    const int64_t blocks = ((count + 7) / 8) * 8 * N1 * N1;
-    hipLaunchKernelGGL((tiledXToRowMajorSymKernel< U, N1 >), dim3(unsigned(blocks)), dim3(256), lds, s, Kt, K, count);
-    return 0;
-}
-template < int U >
-int launchTiledXU(int N1, int64_t count, const double* Kt, double* K, hipStream_t s)
-{
-    switch (N1)
-    {
-    case 2: return launchTiledXOne< U, 2 >(count, Kt, K, s);
-    case 3: return launchTiledXOne< U, 3 >(count, Kt, K, s);
-    case 4: return launchTiledXOne< U, 4 >(count, Kt, K, s);
-    case 5: return launchTiledXOne< U, 5 >(count, Kt, K, s);
-    case 6: return launchTiledXOne< U, 6 >(count, Kt, K, s);
-    case 7: return launchTiledXOne< U, 7 >(count, Kt, K, s);
-    case 8: return launchTiledXOne< U, 8 >(count, Kt, K, s);
-    default: return 1;
-    }
-}
 // `count` element matrices: x-major tiled (d_Kt, formed with ElemArgs::K_tiled == 2) -> row-major, bitwise symmetric (d_K), on stream s
 int launchTiledXToRowMajorSym(int U, int N1, int64_t count, const double* d_Kt, double* d_K, hipStream_t s)
 {
@@ -440,45 +317,35 @@ int launchTiledXToRowMajorSym(int U, int N1, int64_t count, const double* d_Kt, 
         setError("x-major tiled -> row-major: shape (order %d, %d unknowns, %lld elements) not supported", N1 - 1, U, (long long)count);
         return -1;
     }
-    int rc = 1;
-    switch (U)
-    {
-    case 1: rc = launchTiledXU< 1 >(N1, count, d_Kt, d_K, s); break;
-    case 2: rc = launchTiledXU< 2 >(N1, count, d_Kt, d_K, s); break;
-    case 3: rc = launchTiledXU< 3 >(N1, count, d_Kt, d_K, s); break;
-    case 4: rc = launchTiledXU< 4 >(N1, count, d_Kt, d_K, s); break;
-    default: break;
-    }
-    if (rc || hipGetLastError() != hipSuccess)
-    {
-        setError("x-major tiled -> row-major kernel launch failed (order %d, %d unknowns)", N1 - 1, U);
-        return -3;
-    }
-    return 0;
+    return withUnknowns< 4 >(U, [&](auto u) {
+        return withNodes1d(N1, [&](auto n) {
+            constexpr size_t lds = sizeof(double) * size_t(n()) * u() * (n() * n() * u() + 1); // (above the default: order 7 with 4 unknowns)
+            return launchKernel< lds >("tiledXToRowMajorSymKernel", tiledXToRowMajorSymKernel< u(), n() >, dim3(unsigned(blocks)), dim3(256), lds,
+                                       s, d_Kt, d_K, count);
+        });
+    });
 }
 int launchTiledToRowMajor(int U, int N1, int64_t count, const double* d_Kt, double* d_K, hipStream_t s)
 {
     const int64_t blocks = count * N1 * N1 * N1;
-    if (blocks > int64_t(0x7fffffff) || U < 1 || U > 4 || size_t(U) * U * N1 * N1 * N1 * sizeof(double) > 64 * 1024)
+    const size_t  lds    = sizeof(double) * size_t(U) * U * N1 * N1 * N1;
+    if (blocks > int64_t(0x7fffffff) || U < 1 || U > 4 || lds > l3k::dev::default_dynamic_lds)
     {
         setError("tiled -> row-major: shape (order %d, %d unknowns, %lld elements) not supported", N1 - 1, U, (long long)count);
         return -1;
     }
-    int rc = 1;
-    switch (U)
-    {
-    case 1: rc = launchTiledToRowMajorU< 1 >(N1, blocks, d_Kt, d_K, s); break;
-    case 2: rc = launchTiledToRowMajorU< 2 >(N1, blocks, d_Kt, d_K, s); break;
-    case 3: rc = launchTiledToRowMajorU< 3 >(N1, blocks, d_Kt, d_K, s); break;
-    case 4: rc = launchTiledToRowMajorU< 4 >(N1, blocks, d_Kt, d_K, s); break;
-    default: break;
-    }
-    if (rc || hipGetLastError() != hipSuccess)
+    const int rc = withUnknowns< 4 >(U, [&](auto u) {
+        return withNodes1d(N1, [&](auto n) {
+            return launchKernel< l3k::dev::default_dynamic_lds >("tiledToRowMajorKernel", tiledToRowMajorKernel< u(), n() >, dim3(unsigned(blocks)),
+                                                                 dim3(256), lds, s, d_Kt, d_K);
+        });
+    });
+    if (rc == l3k::dev::not_instantiated)
     {
         setError("tiled -> row-major kernel launch failed (order %d, %d unknowns)", N1 - 1, U);
         return -3;
     }
-    return 0;
+    return rc;
 }
 
 // the launch of the batch scatter on `s` (shared by l3k_assembled_scatter and the pipelined l3k_assemble_global)
@@ -523,22 +390,21 @@ int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint
     a.U_rt = n_unknowns;
     if (tiled)
     {
-        int rc = 1;
-        switch (n_unknowns)
-        {
-        case 1: rc = launchScatterTiled< 1 >(a, N1, blocks, s); break;
-        case 2: rc = launchScatterTiled< 2 >(a, N1, blocks, s); break;
-        case 3: rc = launchScatterTiled< 3 >(a, N1, blocks, s); break;
-        case 4: rc = launchScatterTiled< 4 >(a, N1, blocks, s); break;
-        default: break;
-        }
-        if (rc)
+        const size_t lds = size_t(NN) * n_unknowns * (sizeof(double) + sizeof(int32_t)); // (24 KiB at order 7 with 4 unknowns)
+        const int    rc  = withUnknowns< 4 >(n_unknowns, [&](auto u) {
+            return withNodes1d(N1, [&](auto n) {
+                return launchKernel< l3k::dev::default_dynamic_lds >("assembledScatterTiledKernel", assembledScatterTiledKernel< u(), n() >,
+                                                                     dim3(unsigned(blocks)), dim3(64), lds, s, a);
+            });
+        });
+        if (rc == l3k::dev::not_instantiated)
         {
             setError("tiled scatter: shape (order %d, %d unknowns) not instantiated", m->order, n_unknowns);
             return -1;
         }
+        return rc;
     }
-    else if (ctx->tune.scatter_per_entry) // (the round-2 kernel, kept as the cross-check of the per-row-node one)
+    if (ctx->tune.scatter_per_entry) // (the round-2 kernel, kept as the cross-check of the per-row-node one)
     {
         const int64_t rows = count * NN * n_unknowns;
         if (rows > int64_t(0x7fffffff))
@@ -546,23 +412,17 @@ int launchAssembledScatterRows(const l3k_ctx* ctx, const l3k_mesh* m, const uint
             setError("batch too large: %lld element rows in one launch", (long long)rows);
             return -1;
         }
-        hipLaunchKernelGGL(assembledScatterPerEntryKernel, dim3(unsigned(rows)), dim3(64), 0, s, a);
+        return launchKernel< 0 >("assembledScatterPerEntryKernel", assembledScatterPerEntryKernel, dim3(unsigned(rows)), dim3(64), 0, s, a);
     }
-    else
-        switch (n_unknowns)
-        {
-        case 1: hipLaunchKernelGGL(assembledScatterKernel< 1 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(assembledScatterKernel< 2 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 3: hipLaunchKernelGGL(assembledScatterKernel< 3 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 4: hipLaunchKernelGGL(assembledScatterKernel< 4 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 5: hipLaunchKernelGGL(assembledScatterKernel< 5 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 6: hipLaunchKernelGGL(assembledScatterKernel< 6 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 7: hipLaunchKernelGGL(assembledScatterKernel< 7 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(assembledScatterKernel< 8 >, dim3(unsigned(blocks)), dim3(64), 0, s, a); break;
-        default: setError("l3k_assembled_scatter: %d unknowns not supported (1..8)", n_unknowns); return -1;
-        }
-    L3K_HIP(hipGetLastError());
-    return 0;
+    const int rc = withUnknowns< 8 >(n_unknowns, [&](auto u) {
+        return launchKernel< 0 >("assembledScatterKernel", assembledScatterKernel< u() >, dim3(unsigned(blocks)), dim3(64), 0, s, a);
+    });
+    if (rc == l3k::dev::not_instantiated)
+    {
+        setError("l3k_assembled_scatter: %d unknowns not supported (1..8)", n_unknowns);
+        return -1;
+    }
+    return rc;
 }
 
 extern "C" {

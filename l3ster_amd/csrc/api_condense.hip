@@ -5,10 +5,11 @@
 // Element systems are formed by l3k_local_assemble into buffers of the system (row-major K_e, column-major F_e), the
 // condensation kernels of the system's (order, unknowns) shape (device/condense.hpp, Instance::condense) eliminate the internal
 // dofs in place, and S_e / g_e leave the device only through l3k_condense_local: l3k_condense_global sums them into the caller's
-// CSR graph with the primary-node scatter below, pipelined on two streams as l3k_assemble_global is.  Recovery is stateless: it
+// CSR graph with the primary-node scatter below (the hand-off of device/csr_scatter.hpp), pipelined on two streams as l3k_assemble_global is.  Recovery is stateless: it
 // forms and eliminates the element systems again (the reference caches K_ii^-1 K_ib per element: 4.5 MB at order 6).
 #include "objects.hpp"
 #include "device/condense.hpp"
+#include "device/csr_scatter.hpp"
 
 namespace
 {
@@ -17,40 +18,21 @@ using l3k::dev::primaryNodeOf;
 
 constexpr int cond_nb = 32; // CondShape::NB: pivots per panel (the factored diagonal blocks take Ni U x NB doubles per element)
 
-struct CondScatterArgs
+struct CondScatterArgs : l3k::dev::CsrSink // (the condensed system: row_ptr, col_ind, values, rhs, ldr, n_missing)
 {
-    const uint32_t*     elem_nodes;
-    const uint8_t*      dirichlet; // per local dof, or null
-    const double *      K, *F;     // eliminated element systems: row-major K_e (Schur block mirrored), column-major F_e
-    const int*          fail;      // per element: its pivot failed (nothing of it is scattered)
-    const int64_t*      row_ptr;
-    const int32_t*      col_ind;
-    double *            values, *rhs;
-    size_t              ldr;
-    unsigned long long* n_missing;
-    int64_t             first;
-    int                 n, NN, Np, dpn, n_rhs, skip_dirichlet;
-    int                 field_inds[l3k::dev::max_unknowns];
+    const uint32_t* elem_nodes;
+    const uint8_t*  dirichlet; // per local dof, or null
+    const double *  K, *F;     // eliminated element systems: row-major K_e (Schur block mirrored), column-major F_e
+    const int*      fail;      // per element: its pivot failed (nothing of it is scattered)
+    int64_t         first;
+    int             n, NN, Np, dpn, n_rhs, skip_dirichlet;
+    int             field_inds[l3k::dev::max_unknowns];
 };
-
-// first position in [lo, hi) with col_ind >= col
-__device__ __forceinline__ int64_t lowerBoundCol(const int32_t* __restrict__ col_ind, int64_t lo, int64_t hi, int64_t col)
-{
-    while (lo < hi)
-    {
-        const int64_t mid = (lo + hi) >> 1;
-        if (col_ind[mid] < col)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 
 // The primary-node variant of api_assembled.hip's assembledScatterKernel: one wave per (element, PRIMARY row node), the U rows of
 // the node, the lanes over the primary columns (b', u') of the row; the entries stay where the condensation left them, in the
-// element's row-major K_e (rows and columns of primary dofs: S_e), so rows of internal dofs are never touched.  One search per
-// entry shared by the node's U rows, as there.
+// element's row-major K_e (rows and columns of primary dofs: S_e), so rows of internal dofs are never touched.  The search rule
+// is that of device/csr_scatter.hpp.
 template < int U >
 __global__ __launch_bounds__(64) void condensedScatterKernel(const CondScatterArgs a)
 {
@@ -62,39 +44,12 @@ __global__ __launch_bounds__(64) void condensedScatterKernel(const CondScatterAr
     const uint32_t* en   = a.elem_nodes + (a.first + e) * a.NN;
     const int       b    = primaryNodeOf(q, a.n);
     const int       lane = threadIdx.x;
-    const int64_t   nb   = int64_t(en[b]) * a.dpn;
-    int64_t         row[U], rb[U], re[U];
-    bool            live[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-        row[u]  = nb + a.field_inds[u];
-        live[u] = !(a.skip_dirichlet && a.dirichlet && a.dirichlet[row[u]]);
-    }
+    l3k::dev::NodeRows< U > rows(int64_t(en[b]) * a.dpn, a.field_inds, a.dirichlet, a.skip_dirichlet);
     if (a.F && a.rhs)
-        for (int t = lane; t < a.n_rhs * U; t += 64)
-        {
-            const int r = t / U, u = t - r * U;
-            bool      lv = false;
-            int64_t   rw = 0;
-#pragma unroll
-            for (int uu = 0; uu < U; ++uu)
-                if (uu == u)
-                {
-                    lv = live[uu];
-                    rw = row[uu];
-                }
-            if (lv)
-                unsafeAtomicAdd(a.rhs + size_t(r) * a.ldr + rw, a.F[(e * a.n_rhs + r) * Nd + b * U + u]);
-        }
+        rows.addRhs(a, lane, a.n_rhs, a.F + e * a.n_rhs * Nd + b * U, Nd);
     if (!a.K || !a.values)
         return;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-        rb[u] = a.row_ptr[row[u]];
-        re[u] = a.row_ptr[row[u] + 1];
-    }
+    rows.loadRanges(a.row_ptr);
     const double* Kb      = a.K + (e * Nd + int64_t(b) * U) * Nd; // rows (b, 0 .. U-1)
     unsigned      missing = 0;
     for (int j = lane; j < Nbd; j += 64)
@@ -103,23 +58,10 @@ __global__ __launch_bounds__(64) void condensedScatterKernel(const CondScatterAr
         const int64_t col = int64_t(en[bp]) * a.dpn + a.field_inds[up];
         if (a.skip_dirichlet && a.dirichlet && a.dirichlet[col])
             continue;
-        const int64_t rel = lowerBoundCol(a.col_ind, rb[0], re[0], col) - rb[0];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            if (!live[u])
-                continue;
-            int64_t pos = rb[u] + rel;
-            if (u > 0 && !(pos < re[u] && a.col_ind[pos] == col))
-                pos = lowerBoundCol(a.col_ind, rb[u], re[u], col);
-            if (pos < re[u] && a.col_ind[pos] == col)
-                unsafeAtomicAdd(a.values + pos, Kb[int64_t(u) * Nd + bp * U + up]);
-            else
-                ++missing;
-        }
+        const double* Kj = Kb + bp * U + up; // (one pointer per lane: the rows' addresses are not kept in registers across the loop)
+        missing += rows.addEntry(a, col, [&](int u) { return Kj[int64_t(u) * Nd]; });
     }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
+    csrCountMissing(a, missing);
 }
 
 struct CondShapeH // the host's view of CondShape
@@ -243,20 +185,15 @@ int launchCondensedScatter(l3k_mf* mf, int64_t first, int64_t count, const Half&
     for (int u = 0; u < l3k::dev::max_unknowns; ++u)
         a.field_inds[u] = mf->field_inds[u];
     const dim3 grid(unsigned(count * sh.Np));
-    switch (mf->kp.n_unknowns)
+    const int  rc = l3k::dev::withUnknowns< 8 >(mf->kp.n_unknowns, [&](auto u) {
+        return l3k::dev::launchKernel< 0 >("condensedScatterKernel", condensedScatterKernel< u() >, grid, dim3(64), 0, s, a);
+    });
+    if (rc == l3k::dev::not_instantiated)
     {
-    case 1: hipLaunchKernelGGL(condensedScatterKernel< 1 >, grid, dim3(64), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(condensedScatterKernel< 2 >, grid, dim3(64), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(condensedScatterKernel< 3 >, grid, dim3(64), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(condensedScatterKernel< 4 >, grid, dim3(64), 0, s, a); break;
-    case 5: hipLaunchKernelGGL(condensedScatterKernel< 5 >, grid, dim3(64), 0, s, a); break;
-    case 6: hipLaunchKernelGGL(condensedScatterKernel< 6 >, grid, dim3(64), 0, s, a); break;
-    case 7: hipLaunchKernelGGL(condensedScatterKernel< 7 >, grid, dim3(64), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(condensedScatterKernel< 8 >, grid, dim3(64), 0, s, a); break;
-    default: setError("l3k_condense_global: %d unknowns not supported (1..8)", mf->kp.n_unknowns); return -1;
+        setError("l3k_condense_global: %d unknowns not supported (1..8)", mf->kp.n_unknowns);
+        return -1;
     }
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return rc;
 }
 } // namespace
 

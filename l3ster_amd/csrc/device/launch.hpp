@@ -1,9 +1,13 @@
-// launch.hpp -- the host-side steps every element-kernel launcher shares: the functor from its parameter blob, the
-// dynamic-LDS attribute, the checked launch, the grid of a global-scratch route, the column loop.
+// launch.hpp -- the host-side steps the kernel launchers share: the functor from an element kernel's parameter blob, the
+// dynamic-LDS attribute, the checked launch, the dispatch of a run-time shape to its instantiation, the grid of a global-scratch
+// route, the column loop.
 #ifndef L3K_DEVICE_LAUNCH_HPP
 #define L3K_DEVICE_LAUNCH_HPP
 
 #include "common.hpp"
+
+#include <type_traits>
+#include <utility>
 
 namespace l3k::dev
 {
@@ -17,16 +21,21 @@ K functorFrom(const void* kparam_blob)
     return kern;
 }
 
-// `kernel` on `stream` with `lds` bytes of dynamic LDS (allowDynamicLds first); -3 and "<name> launch failed: ..." on error
-template < typename... Params, typename... Args >
+// dynamic LDS a kernel may take without the attribute; allowDynamicLds is a device query and a locked table look-up per call
+inline constexpr size_t default_dynamic_lds = 64 * 1024;
+
+// `kernel` on `stream` with `lds` bytes of dynamic LDS; -3 and "<name> launch failed: ..." on error.  LDS_BOUND: what the launcher
+// knows at compile time that lds cannot exceed (0: a kernel without dynamic LDS); allowDynamicLds runs first unless that rules it out
+template < size_t LDS_BOUND = SIZE_MAX, typename... Params, typename... Args >
 int launchKernel(const char* name, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                  const Args&... args)
 {
-    if (!allowDynamicLds(reinterpret_cast< const void* >(kernel), lds))
-    {
-        setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
-        return -3;
-    }
+    if constexpr (LDS_BOUND > default_dynamic_lds)
+        if (!allowDynamicLds(reinterpret_cast< const void* >(kernel), lds))
+        {
+            setError("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", lds);
+            return -3;
+        }
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
@@ -35,6 +44,28 @@ int launchKernel(const char* name, void (*kernel)(Params...), dim3 grid, dim3 bl
         return -3;
     }
     return 0;
+}
+
+// f(std::integral_constant< int, K >) for the run-time k = K in [LO, LO + sizeof...(I)): the instantiated set; not_instantiated outside it
+inline constexpr int not_instantiated = 1;
+template < int LO, int... I, typename F >
+int withConstant(int k, std::integer_sequence< int, I... >, F&& f)
+{
+    int rc = not_instantiated;
+    (void)((k == LO + I && (rc = f(std::integral_constant< int, LO + I >{}), true)) || ...);
+    return rc;
+}
+// ... for a kernel's number of unknowns U in 1 .. MAX
+template < int MAX, typename F >
+int withUnknowns(int U, F&& f)
+{
+    return withConstant< 1 >(U, std::make_integer_sequence< int, MAX >{}, f);
+}
+// ... for a hex element's nodes per direction N1 = order + 1 in 2 .. 8
+template < typename F >
+int withNodes1d(int N1, F&& f)
+{
+    return withConstant< 2 >(N1, std::make_integer_sequence< int, 7 >{}, f);
 }
 
 // The grid of a global-scratch route (the element's buffers exceed the LDS): persistent workgroups, two per CU (no LDS, the

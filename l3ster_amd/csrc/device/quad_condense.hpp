@@ -6,7 +6,8 @@
 // every local system of every term is SPLIT into it on the way to the CSR arrays:
 //   1. quadSplitKernel:     one wave per (local system, row node), the lanes over the row's entries as in assembledScatterKernel
 //                           (api_assembled.hip): a primary row sums its primary columns into the condensed graph and F_b into the
-//                           rhs, an internal row is added to the element's slot of the store.  K_bi is dropped: it is K_ib^T.
+//                           rhs (the node rows and the search rule of csr_scatter.hpp, no Dirichlet skip), an internal row is added
+//                           to the element's slot of the store.  K_bi is dropped: it is K_ib^T.
 //   2. quadEliminateKernel: a TEAM of 16, 64 or 256 threads per element, 256 / team elements per workgroup (an order-2 block of 3
 //                           unknowns is 3 x 3: one workgroup per element would idle 61 of 64 lanes).  The slot is copied to the
 //                           LDS where teams x slot fits cond_lds_bytes, else it is worked on in place in global memory (same body).
@@ -14,7 +15,8 @@
 //                           then the rank-1 update of the rows below it -- the K_ib and F_i columns ride along, which leaves
 //                           [ L^T | W = L^-1 K_ib | h = L^-1 F_i ] in the slot.  Then schurProduct: W^T W and W^T h by FMAs over k
 //                           ascending (fma(W[k][a], W[k][b], .) and its mirror image are the same operation: bitwise symmetric),
-//                           subtracted from the CSR values and the rhs with the addressing of kernel 1.
+//                           subtracted from the CSR values and the rhs with the addressing of kernel 1 (csrFind of csr_scatter.hpp:
+//                           the guess is the position next to the node's previous field).
 //   3. quadRecoverKernel:   y = h - W x_b, back substitution with L^T column by column, plain stores: one writer per dof, a fixed
 //                           summation order.
 //   4. quadSchurOutKernel:  schurProduct of a factored store into the caller's arrays instead of the CSR.
@@ -25,6 +27,7 @@
 
 #include "common.hpp"
 #include "condense.hpp"
+#include "csr_scatter.hpp"
 #include "launch.hpp"
 
 namespace l3k::dev
@@ -77,16 +80,12 @@ __global__ void __launch_bounds__(256) quadPrimaryNodesKernel(const uint32_t* __
     }
 }
 
-struct QuadSplitArgs
+struct QuadSplitArgs : CsrSink // (the condensed system: row_ptr, col_ind, values, rhs, ldr, n_missing)
 {
     const uint32_t* nodes;     // [.][NN] node rows of the local systems (element systems: the mesh's; side systems: the sides' elements')
     const int64_t*  elem_of;   // [.] element of local system i, or nullptr: i itself
     const double *  K, *F;     // the sub-batch: [count][Nd][Nd] row-major, [count][R][Nd]
-    const int64_t*  row_ptr;
-    const int32_t*  col_ind;
-    double *        values, *rhs, *store;
-    size_t          ldr;
-    unsigned long long* n_missing;
+    double*         store;
     int64_t         first, count;
     int             n1d, dpn, n_rhs, Us, Nis, LD;
     int             field_inds[max_unknowns]; // of the term's unknowns
@@ -100,18 +99,6 @@ __device__ __forceinline__ void storeAdd(double* p, double v)
         unsafeAtomicAdd(p, v);
     else
         *p += v;
-}
-__device__ __forceinline__ int64_t condLowerBound(const int32_t* __restrict__ col_ind, int64_t lo, int64_t hi, int64_t col)
-{
-    while (lo < hi)
-    {
-        const int64_t mid = (lo + hi) >> 1;
-        if (col_ind[mid] < col)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
 }
 
 // ATOMIC = false: no two local systems of the launch belong to one element (a domain term); true: sides
@@ -146,22 +133,12 @@ __global__ __launch_bounds__(64) void quadSplitKernel(const QuadSplitArgs a)
         }
         return;
     }
-    const int64_t nb = int64_t(en[b]) * a.dpn;
+    NodeRows< U > rows(int64_t(en[b]) * a.dpn, a.field_inds, nullptr, 0); // (no Dirichlet skip: every row is live)
     if (a.F)
-        for (int t = lane; t < a.n_rhs * U; t += 64)
-        {
-            const int r = t / U, u = t - r * U;
-            unsafeAtomicAdd(a.rhs + size_t(r) * a.ldr + nb + a.field_inds[u], a.F[(e * a.n_rhs + r) * Nd + b * U + u]);
-        }
+        rows.addRhs(a, lane, a.n_rhs, a.F + e * a.n_rhs * Nd + b * U, Nd);
     if (!Kb)
         return;
-    int64_t rb[U], re[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-        rb[u] = a.row_ptr[nb + a.field_inds[u]];
-        re[u] = a.row_ptr[nb + a.field_inds[u] + 1];
-    }
+    rows.loadRanges(a.row_ptr);
     unsigned missing = 0;
     for (int j = lane; j < Nd; j += 64)
     {
@@ -169,37 +146,19 @@ __global__ __launch_bounds__(64) void quadSplitKernel(const QuadSplitArgs a)
         if (!quadIsPrimary(bp, n))
             continue;
         const int64_t col = int64_t(en[bp]) * a.dpn + a.field_inds[j - bp * U];
-        const int64_t rel = condLowerBound(a.col_ind, rb[0], re[0], col) - rb[0]; // one search, reused for the node's other rows
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            int64_t pos = rb[u] + rel;
-            if (u > 0 && !(pos < re[u] && a.col_ind[pos] == col))
-                pos = condLowerBound(a.col_ind, rb[u], re[u], col);
-            if (pos < re[u] && a.col_ind[pos] == col)
-                unsafeAtomicAdd(a.values + pos, Kb[int64_t(u) * Nd + j]);
-            else
-                ++missing;
-        }
+        missing += rows.addEntry(a, col, [&](int u) { return Kb[int64_t(u) * Nd + j]; });
     }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
+    csrCountMissing(a, missing);
 }
 
-struct QuadCondArgs
+struct QuadCondArgs : CsrSink // (elimination: the condensed system -- row_ptr, col_ind, values, rhs, ldr, n_missing)
 {
     double*         store;      // [n_elems][Nis][LD]
     const uint32_t* elem_nodes; // [n_elems][n1d^2]
     const int*      fields;     // [Us] the system's field_inds (device)
     int64_t         first, count; // the elements of the launch
     int             n1d, dpn, n_rhs, Us, Nis, Nbs, LD, team;
-    // elimination: the condensed system
-    const int64_t*  row_ptr;
-    const int32_t*  col_ind;
-    double *        values, *rhs;
-    size_t          ldr;
-    unsigned*           n_failed;
-    unsigned long long* n_missing;
+    unsigned*       n_failed;   // elimination: elements whose pivot test failed
     // updates out: [count][Nbs][Nbs], [count][R][Nbs], either may be null
     double *outW, *outw;
     // recovery
@@ -233,7 +192,7 @@ __device__ __forceinline__ void schurProduct(const QuadCondArgs& a, const double
                 rb                = a.row_ptr[row];
                 re                = a.row_ptr[row + 1];
                 col0              = int64_t(en[quadPrimaryNodeOf(bq, a.n1d)]) * a.dpn;
-                pos               = condLowerBound(a.col_ind, rb, re, col0 + a.fields[0]);
+                pos               = csrLowerBound(a.col_ind, rb, re, col0 + a.fields[0]);
             }
             for (int s = 0; s < a.Us; ++s)
             {
@@ -245,12 +204,9 @@ __device__ __forceinline__ void schurProduct(const QuadCondArgs& a, const double
                     a.outW[(at * a.Nbs + ar) * a.Nbs + br] = acc;
                 else
                 {
-                    // (the columns of one node are adjacent in a row of the graph, fields ascending)
-                    const int64_t col = col0 + a.fields[s];
-                    int64_t       ps  = pos + s;
-                    if (!(ps < re && a.col_ind[ps] == col))
-                        ps = condLowerBound(a.col_ind, rb, re, col);
-                    if (ps < re && a.col_ind[ps] == col)
+                    // (the columns of one node are adjacent in a row of the graph, fields ascending: the guess of csrFind)
+                    const int64_t ps = csrFind(a.col_ind, rb, re, pos + s, col0 + a.fields[s]);
+                    if (ps >= 0)
                         unsafeAtomicAdd(a.values + ps, -acc);
                     else
                         ++missing;
@@ -269,8 +225,7 @@ __device__ __forceinline__ void schurProduct(const QuadCondArgs& a, const double
             else
                 unsafeAtomicAdd(a.rhs + size_t(r) * a.ldr + condDof(a, en, ar, true), -acc);
         }
-    if (missing && a.n_missing)
-        atomicAdd(a.n_missing, static_cast< unsigned long long >(missing));
+    csrCountMissing(a, missing);
 }
 
 // Every loop bound below depends on the shape alone, so the teams of a workgroup (and the idle team of a last workgroup) meet at

@@ -153,19 +153,27 @@ def test_condense_global_vs_dense_schur(ctx, ne, p):
         r_h[bd] += G[e].T
     assert np.abs(A_h - Sg_plain).max() <= 1e-13 * np.abs(A_h).max()
     assert np.abs(r_h - rhs_plain.T).max() <= 1e-13 * max(1.0, np.abs(r_h).max())
-    # a graph that lacks entries: they are skipped and counted
-    r5 = int(np.flatnonzero(np.diff(row_ptr))[3])
-    keep = np.ones(len(col_ind), bool)
-    keep[row_ptr[r5]:row_ptr[r5 + 1]][::2] = False
-    rp2 = np.concatenate([[0], np.cumsum(keep)])[row_ptr].astype(np.int64)
-    vals2 = torch.zeros(int(keep.sum()), dtype=torch.float64, device="cuda")
-    missing = mf.condense_global(torch.as_tensor(rp2, device="cuda"), torch.as_tensor(col_ind[keep], device="cuda"), vals2)
-    torch.cuda.synchronize()
-    assert missing >= (~keep).sum()
-    A2 = sp.csr_matrix((vals2.cpu().numpy(), col_ind[keep], rp2), shape=(n, n)).toarray()
-    dropped = np.zeros((n, n), bool)
-    dropped[r5, col_ind[row_ptr[r5]:row_ptr[r5 + 1]][::2]] = True
-    assert np.abs(np.where(dropped, 0.0, Sg_plain) - A2).max() <= 1e-13 * np.abs(Sg_plain).max()
+    # graphs that lack entries: they are skipped and counted, once per (element, primary dof i, primary dof j) that lands on one
+    # (no pivot fails here).  Every second entry removed from (1) the fourth non-empty row, (2) the u = 0 row of a node inside a
+    # face between two elements: the row the node's one search runs in is then the sparse one, and the guesses it hands to the
+    # rows u > 0 miss (device/csr_scatter.hpp), as in case (c) of test_graphs_where_the_shared_search_falls_back
+    elem_dofs = (part.elem_nodes[:, primary].astype(np.int64)[:, :, None] * U + np.arange(U)).reshape(part.n_elems, -1)
+    shared_by = np.bincount(part.elem_nodes[:, primary].ravel(), minlength=part.n_local_nodes)
+    face_nodes = np.flatnonzero((shared_by == 2) & (part.node_boundary == 0))
+    assert face_nodes.size > 0
+    for thinned_row in (int(np.flatnonzero(np.diff(row_ptr))[3]), int(face_nodes[face_nodes.size // 2]) * U):
+        keep = np.ones(len(col_ind), bool)
+        keep[row_ptr[thinned_row]:row_ptr[thinned_row + 1]][::2] = False
+        assert (~keep).sum() > 1
+        rp2 = np.concatenate([[0], np.cumsum(keep)])[row_ptr].astype(np.int64)
+        vals2 = torch.zeros(int(keep.sum()), dtype=torch.float64, device="cuda")
+        missing = mf.condense_global(torch.as_tensor(rp2, device="cuda"), torch.as_tensor(col_ind[keep], device="cuda"), vals2)
+        torch.cuda.synchronize()
+        dropped = np.zeros((n, n), bool)
+        dropped[thinned_row, col_ind[row_ptr[thinned_row]:row_ptr[thinned_row + 1]][::2]] = True
+        assert missing == sum(int(dropped[np.ix_(d, d)].sum()) for d in elem_dofs), thinned_row
+        A2 = sp.csr_matrix((vals2.cpu().numpy(), col_ind[keep], rp2), shape=(n, n)).toarray()
+        assert np.abs(np.where(dropped, 0.0, Sg_plain) - A2).max() <= 1e-13 * np.abs(Sg_plain).max(), thinned_row
 
 
 @pytest.mark.parametrize("ne,p", [(3, 2), (2, 4)])
