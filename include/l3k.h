@@ -787,6 +787,75 @@ int l3k_assemble_global(l3k_mf* mf, int64_t first, int64_t count, const int64_t*
                         double* d_values, double* d_rhs, size_t ldr, int skip_dirichlet, size_t workspace_bytes,
                         int64_t* n_missing);
 
+/* ---- matrix-free systems of several terms over one set of rows -----------------------------------------------------------------
+ * algsys::MatrixFreeSystem of the reference is the sum of every assembleProblem(kernel, domain ids / boundary ids, field_access,
+ * dof_inds) call made on it (algsys/MatrixFreeSystem.hpp:24-89: the declarations; :722-802: each call pushes its kernels onto the
+ * per-domain lists the operator walks); tests/MultiDomainTest.cpp runs four kernels on four domains, each on a dof of its own.  An
+ * l3k_mf is ONE domain kernel over every element of its mesh.  l3k_mfs is the sum: any number of l3k_mf and l3k_bnd terms, each on
+ * `rows` or on an l3k_mesh over the same nodes that holds only SOME of the elements (made with l3k_mesh_create from the selected
+ * rows of elem_nodes / elem_verts, interior elements first; node counts, dofs_per_node, order, dim and Dirichlet mask those of the
+ * whole mesh; such a mesh has launch ranges and, in deterministic mode, a colouring of its own).  No element kernel knows of it.
+ *
+ * l3k_mfs_create: `rows` fixes the row space, the ghost layout and the Dirichlet mask; n_rhs >= 1 the columns the sum serves.
+ *   Nothing is owned: rows and every term must outlive the object.                                   (MatrixFreeSystem.hpp:24-54)
+ * l3k_mfs_add_domain / l3k_mfs_add_boundary: assembleProblem(kernel, domain ids / boundary ids)       (:56-89, :789-802).  Refused
+ *   with -1 and a message naming the offence: a finalized system; a term of another context; a term whose mesh differs from
+ *   `rows` in dim, order, owned or ghost node count or dofs_per_node; a Dirichlet mask that differs from that of `rows` (compared
+ *   byte for byte on the device, one readback; the message names the first differing dof; a mesh without a mask counts as all
+ *   zero); an l3k_mf with attached boundary terms ("add them with l3k_mfs_add_boundary"); a term with n_rhs below the system's.
+ * l3k_mfs_finalize: endAssembly's bookkeeping (:876-885): the coverage mask active[n_local_dofs] -- 1 on the dofs
+ *   (node, field_inds[u]) of every node of a term's elements (of a boundary term: of its sides' elements), 0 elsewhere -- and the
+ *   number of active owned rows.  Adds are refused afterwards; apply, diag_rhs and the solvers are refused before.
+ * l3k_mfs_info_get: n_terms, n_rows (owned dofs), n_active_rows, n_dirichlet_rows (owned), n_rhs, finalized.
+ * l3k_mfs_active: the coverage mask into d_mask [n_local_dofs] (device).
+ *
+ * l3k_mfs_apply: Y <- alpha A X + beta Y, A = the sum of the terms (Operator::apply, :1020-1140), single rank; the split-phase
+ *   pieces follow l3k_mf_scale / l3k_mf_apply_elems / l3k_mf_dirichlet_rows and take the same arguments:
+ *   l3k_mfs_scale: y <- beta y on EVERY owned row.  l3k_mfs_apply_elems: every term in the order added, domain terms with the
+ *   `which` classes of l3k_mf_apply_elems on their own meshes, boundary terms as l3k_mf_apply_elems runs attached ones (which = 3:
+ *   the sides of interior elements, 4: none).  l3k_mfs_dirichlet_rows: y += alpha x on the owned Dirichlet rows, once.
+ *   Inside a sum no term writes rows: every row of every term is accumulated (a second kernel on the same element would overwrite
+ *   the first, and the scale would miss rows) -- an override of the launch, the l3k_mf is not modified and keeps working alone.
+ *   Rows no term covers get beta y.  Deterministic contexts: the terms in add order, each colour by colour -- the same bits on
+ *   every run.  A refused call leaves y untouched.
+ * l3k_mfs_diag_rhs: computeDiagAndRhs (:888-941) summed over the terms: the arguments and the `finalize` flag of l3k_mf_diag_rhs;
+ *   accumulates, zeroes nothing.  Every term forms its own n_rhs columns: -1 unless all terms have the system's n_rhs.
+ * l3k_mfs_jacobi_inverse: NativeJacobiImpl::init (solve/NativePreconditioners.hpp:75-96), l3k_jacobi_inverse's formula on the active
+ *   owned rows and 0 on the others -- decided by the mask, not by the value of the diagonal -- so the PCG's frozen-row rule leaves
+ *   x as it is on rows no term covers (as l3k_csr_diag does for empty rows).
+ * l3k_mfs_apply_energy: y <- A x, s[1] <- <x, A x> by the fixed-order dot product behind the apply.
+ * l3k_mfs_pcg_solve / _pcg_solve_cols / l3k_mfs_cheb_create / l3k_mfs_pcg_solve_cheb: alg_sys.solve(CG{...}) (solve/BelosSolvers.hpp:116-122)
+ *   -- the loops of l3k_pcg_solve / l3k_pcg_solve_cols / l3k_cheb_create / l3k_pcg_solve_cheb on the sum; single rank.
+ * Not provided for sums: the partitioned apply and solve in one call (l3k_mf_apply_dist, l3k_pcg_solve_dist; the split-phase
+ * pieces above serve a partitioned host), p-multigrid, the fused stores of exclusive rows. */
+typedef struct l3k_mfs l3k_mfs;
+typedef struct
+{
+    int64_t n_terms, n_rows, n_active_rows, n_dirichlet_rows;
+    int     n_rhs, finalized;
+} l3k_mfs_info;
+int l3k_mfs_create(l3k_mesh* rows, int n_rhs, l3k_mfs** out);
+int l3k_mfs_add_domain(l3k_mfs* S, l3k_mf* term);
+int l3k_mfs_add_boundary(l3k_mfs* S, l3k_bnd* term);
+int l3k_mfs_finalize(l3k_mfs* S);
+int l3k_mfs_info_get(const l3k_mfs* S, l3k_mfs_info* out);
+int l3k_mfs_active(const l3k_mfs* S, uint8_t* d_mask);
+int l3k_mfs_destroy(l3k_mfs* S);
+int l3k_mfs_apply(l3k_mfs* S, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha, double beta);
+int l3k_mfs_scale(l3k_mfs* S, double* d_y, size_t ldy, int ncols, double beta);
+int l3k_mfs_apply_elems(l3k_mfs* S, int which, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, double* d_y,
+                        size_t ldy, double* d_yghost, size_t ldyg, int ncols, double alpha, double beta);
+int l3k_mfs_dirichlet_rows(l3k_mfs* S, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha);
+int l3k_mfs_diag_rhs(l3k_mfs* S, int which, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs, size_t ldr,
+                     double* d_diag_ghost, double* d_rhs_ghost, size_t ldrg, int finalize);
+int l3k_mfs_jacobi_inverse(l3k_mfs* S, const double* d_diag, double damping, double threshold, double* d_minv);
+int l3k_mfs_apply_energy(l3k_mfs* S, const double* d_x, double* d_y, double* d_s);
+int l3k_mfs_pcg_solve(l3k_mfs* S, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts, l3k_cg_result* result);
+int l3k_mfs_pcg_solve_cols(l3k_mfs* S, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                           const l3k_cg_opts* opts, l3k_cg_result* results);
+int l3k_mfs_cheb_create(l3k_mfs* S, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out);
+int l3k_mfs_pcg_solve_cheb(l3k_mfs* S, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result);
+
 /* ---- the assembled system as one object: hexes and quads ---------------------------------------------------------------------
  * algsys::AssembledSystem of the reference (algsys/AssembledSystem.hpp: beginAssembly / assembleProblem / endAssembly, then the
  * solver on the matrix), for one rank.  The calls above it in this header stay what they are (hexes; quads refused); this route

@@ -13,6 +13,8 @@
 //   l3k::Halo                    ~ comm::ImportExportContext + comm::Import / comm::Export  comm/ImportExport.hpp:29-72,130-215
 //   l3k::Transfer                ~ (no counterpart: the p-multigrid transfer of a partitioned mesh, next to l3k_pmg_*)
 //   l3k::SquareMesh              ~ makeSquareMesh(...) at an order, one rank              mesh/primitives/SquareMesh.hpp
+//   l3k::MultiTermSystem         ~ algsys::MatrixFreeSystem as the sum of its assembleProblem calls     algsys/MatrixFreeSystem.hpp:24-89
+//   l3k::ElementSubset           ~ the elements of some domains as a mesh over the same nodes (a term of a MultiTermSystem)
 //   l3k::AssembledSystem         ~ algsys::AssembledSystem: beginAssembly / assembleProblem / endAssembly, hexes and quads
 //   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
 //   l3k::DistributedCsr          ~ ... of an MPI run: the ranks' local matrices applied as one (sub-assembled form)
@@ -574,6 +576,129 @@ public:
 
 private:
     l3k_mf* m_mf{};
+};
+
+// Some of the elements of a mesh (CubeMesh, SquareMesh, anything with a view()) as a mesh over the SAME nodes: what DeviceMesh
+// takes for a term of a MultiTermSystem that lives on part of the mesh.  The order of `elems` is kept, except that the interior
+// elements come first, stably; the node-level arrays are the parent's, which must outlive this object
+class ElementSubset
+{
+public:
+    template < typename Mesh >
+    ElementSubset(const Mesh& mesh, std::span< const int64_t > elems) : m_view{mesh.view()}
+    {
+        const auto&   v  = mesh.view();
+        const int64_t n1 = v.order + 1, N = v.dim == 2 ? n1 * n1 : n1 * n1 * n1, nvd = (int64_t(1) << v.dim) * 3;
+        for (const int64_t e : elems)
+            if (e < 0 || e >= v.n_elems)
+                throw std::runtime_error{"ElementSubset: element " + std::to_string(e) + " outside the mesh"};
+        int64_t n_interior = 0;
+        for (int cls = 0; cls < 2; ++cls)
+            for (const int64_t e : elems)
+                if ((e < v.n_interior_elems) == (cls == 0))
+                {
+                    m_nodes.insert(m_nodes.end(), v.elem_nodes + e * N, v.elem_nodes + (e + 1) * N);
+                    m_verts.insert(m_verts.end(), v.elem_verts + e * nvd, v.elem_verts + (e + 1) * nvd);
+                    m_boundary.push_back(v.elem_boundary ? v.elem_boundary[e] : uint8_t{0});
+                    n_interior += cls == 0;
+                }
+        m_view.n_elems          = int64_t(elems.size());
+        m_view.n_interior_elems = n_interior;
+        m_view.elem_nodes       = m_nodes.data();
+        m_view.elem_verts       = m_verts.data();
+        m_view.elem_boundary    = m_boundary.data();
+    }
+    ElementSubset(const ElementSubset&)            = delete;
+    ElementSubset& operator=(const ElementSubset&) = delete;
+    const l3k_hostmesh_view& view() const { return m_view; }
+
+private:
+    l3k_hostmesh_view       m_view;
+    std::vector< uint32_t > m_nodes;
+    std::vector< double >   m_verts;
+    std::vector< uint8_t >  m_boundary;
+};
+
+// algsys::MatrixFreeSystem as the sum of its assembleProblem calls (l3k_mfs_*; algsys/MatrixFreeSystem.hpp:24-89, :789-802): domain
+// and boundary terms over the rows of `rows`, each on `rows` or on a DeviceMesh of an ElementSubset with the same dofs_per_node and
+// Dirichlet mask.  assembleProblem(term) ..., endAssembly(), then apply / diagAndRhs / jacobiInverse / solve as on a
+// MatrixFreeSystem.  Rows no term covers get beta*y from apply and 0 from jacobiInverse, so a solve leaves x as it is there.  The
+// terms and `rows` must outlive the object.  RAII, move-only
+class MultiTermSystem
+{
+public:
+    explicit MultiTermSystem(const DeviceMesh& rows, int n_rhs = 1) : m_n{rows.nOwnedDofs()} { check(l3k_mfs_create(rows.get(), n_rhs, &m_sys)); }
+    MultiTermSystem(const MultiTermSystem&)            = delete;
+    MultiTermSystem& operator=(const MultiTermSystem&) = delete;
+    MultiTermSystem(MultiTermSystem&& o) noexcept : m_sys{o.m_sys}, m_n{o.m_n} { o.m_sys = nullptr; }
+    ~MultiTermSystem() { l3k_mfs_destroy(m_sys); }
+    void assembleProblem(const MatrixFreeSystem& term) { check(l3k_mfs_add_domain(m_sys, term.get())); }
+    void assembleProblem(const BoundaryTerm& term) { check(l3k_mfs_add_boundary(m_sys, term.get())); }
+    // the coverage mask and the count of active rows; no term may be added afterwards
+    void         endAssembly() { check(l3k_mfs_finalize(m_sys)); }
+    l3k_mfs_info info() const
+    {
+        l3k_mfs_info i{};
+        check(l3k_mfs_info_get(m_sys, &i));
+        return i;
+    }
+    // 1 on the local dofs a term has an entry on, 0 elsewhere, into d_mask [n_local_dofs]
+    void active(uint8_t* d_mask) const { check(l3k_mfs_active(m_sys, d_mask)); }
+    // Y <- alpha*A*X + beta*Y, A the sum of the terms (Operator::apply)
+    void apply(const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols = 1, double alpha = 1., double beta = 0.) const
+    {
+        check(l3k_mfs_apply(m_sys, d_x, ldx, d_y, ldy, ncols, alpha, beta));
+    }
+    // diag(A) and rhs with Dirichlet lifting, summed over the terms; the caller zeroes d_diag / d_rhs first
+    void diagAndRhs(const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs, size_t ldr) const
+    {
+        check(l3k_mfs_diag_rhs(m_sys, 2, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, nullptr, nullptr, 0, 1));
+    }
+    void jacobiInverse(const double* d_diag, double* d_minv, double damping = 1., double threshold = 0.) const
+    {
+        check(l3k_mfs_jacobi_inverse(m_sys, d_diag, damping, threshold, d_minv));
+    }
+    // alg_sys.solve(CG{opts, NativeJacobiOpts{}}): d_x holds the initial guess and the result; throws if not converged
+    l3k_cg_result solve(const double* d_b, double* d_x, const double* d_minv, l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        l3k_cg_result res{};
+        check(l3k_mfs_pcg_solve(m_sys, d_b, d_x, d_minv, &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    std::vector< l3k_cg_result > solve(const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                                       l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        std::vector< l3k_cg_result > res(static_cast< size_t >(ncols));
+        check(l3k_mfs_pcg_solve_cols(m_sys, d_b, ldb, d_x, ldx, ncols, d_minv, &opts, res.data()));
+        for (const auto& r : res)
+            if (!r.converged)
+                throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    // the Chebyshev-Jacobi preconditioner of the sum and the solve with it
+    Chebyshev chebyshev(const double* d_minv, l3k_cheb_opts opts = {1, 30., 10, 1.1, 0.}) const
+    {
+        l3k_cheb* c = nullptr;
+        check(l3k_mfs_cheb_create(m_sys, d_minv, &opts, &c));
+        return Chebyshev{c};
+    }
+    l3k_cg_result solve(const double* d_b, double* d_x, const Chebyshev& cheb, l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const
+    {
+        l3k_cg_result res{};
+        check(l3k_mfs_pcg_solve_cheb(m_sys, d_b, d_x, cheb.get(), &opts, &res));
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"};
+        return res;
+    }
+    void     applyEnergy(const double* d_x, double* d_y, double* d_s) const { check(l3k_mfs_apply_energy(m_sys, d_x, d_y, d_s)); }
+    int64_t  nOwnedDofs() const { return m_n; }
+    l3k_mfs* get() const { return m_sys; }
+
+private:
+    l3k_mfs* m_sys{};
+    int64_t  m_n{};
 };
 
 // The assembled or condensed system in front of the solver: a square CSR matrix on the device (row_ptr int64 [n + 1], col_ind

@@ -98,6 +98,12 @@ class AsmInfo(C.Structure):
                 ("d_rhs", C.c_void_p), ("csr", C.c_void_p)]
 
 
+class MfsInfo(C.Structure):
+    """l3k_mfs_info: terms, owned rows, active and Dirichlet rows among them, columns, state of a sum of matrix-free terms"""
+    _fields_ = [("n_terms", C.c_int64), ("n_rows", C.c_int64), ("n_active_rows", C.c_int64), ("n_dirichlet_rows", C.c_int64),
+                ("n_rhs", C.c_int), ("finalized", C.c_int)]
+
+
 class CsrDistInfo(C.Structure):
     """l3k_csr_dist_info: the sizes of a distributed CSR operator, its three row lists and its local operator"""
     _fields_ = [("n_owned", C.c_int64), ("n_ghost", C.c_int64), ("n_interior_rows", C.c_int64), ("n_border_rows", C.c_int64),
@@ -324,6 +330,26 @@ SIGNATURES = {
     "l3k_asm_cond_info_get": (C.c_int, [_vp, C.POINTER(AsmCondInfo)]),
     "l3k_asm_recover": (C.c_int, [_vp, _vp, C.c_size_t]),
     "l3k_asm_schur_updates": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "l3k_mfs_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    "l3k_mfs_add_domain": (C.c_int, [_vp, _vp]),
+    "l3k_mfs_add_boundary": (C.c_int, [_vp, _vp]),
+    "l3k_mfs_finalize": (C.c_int, [_vp]),
+    "l3k_mfs_info_get": (C.c_int, [_vp, C.POINTER(MfsInfo)]),
+    "l3k_mfs_active": (C.c_int, [_vp, _vp]),
+    "l3k_mfs_destroy": (C.c_int, [_vp]),
+    "l3k_mfs_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),
+    "l3k_mfs_scale": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_double]),
+    "l3k_mfs_apply_elems": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t,
+                                      C.c_int, C.c_double, C.c_double]),
+    "l3k_mfs_dirichlet_rows": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double]),
+    "l3k_mfs_diag_rhs": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.c_int]),
+    "l3k_mfs_jacobi_inverse": (C.c_int, [_vp, _vp, C.c_double, C.c_double, _vp]),
+    "l3k_mfs_apply_energy": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "l3k_mfs_pcg_solve": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_mfs_pcg_solve_cols": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, _vp, C.POINTER(CgOpts),
+                                         C.POINTER(CgResult)]),
+    "l3k_mfs_cheb_create": (C.c_int, [_vp, _vp, C.POINTER(ChebOpts), C.POINTER(_vp)]),
+    "l3k_mfs_pcg_solve_cheb": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
     "l3k_csr_dist_create": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(_vp)]),
     "l3k_csr_dist_info_get": (C.c_int, [_vp, C.POINTER(CsrDistInfo)]),
     "l3k_csr_dist_apply": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_double, C.c_double]),

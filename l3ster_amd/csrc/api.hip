@@ -1040,6 +1040,14 @@ int l3k_mf_route(l3k_mf* mf, int which, int ncols, int with_energy, char* buf, s
     return 0;
 }
 
+extern "C++" int scaleRows(l3k_ctx* ctx, double* d_y, size_t ldy, int64_t rows, int ncols, double beta)
+{
+    if (beta == 1. || rows <= 0)
+        return 0;
+    hipLaunchKernelGGL(scaleKernel, dim3(gridFor(rows)), dim3(256), 0, ctx->stream, d_y, ldy, rows, ncols, beta);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
 int l3k_mf_scale(l3k_mf* mf, double* d_y, size_t ldy, int ncols, double beta)
 {
     if (!mf || !d_y)
@@ -1049,22 +1057,21 @@ int l3k_mf_scale(l3k_mf* mf, double* d_y, size_t ldy, int ncols, double beta)
     }
     const l3k_mesh* m    = mf->mesh;
     const int64_t   rows = m->nOwnedDofs();
-    if (beta == 1. || rows == 0)
-        return 0;
     // rows of exclusive nodes are left to the element kernel (it writes alpha*A*x + beta*y there)
     const int64_t r0 = mf->fuse ? m->exclusive_begin * m->dofs_per_node : rows;
     const int64_t r1 = mf->fuse ? m->exclusive_end * m->dofs_per_node : rows;
-    if (r0 > 0)
-        hipLaunchKernelGGL(scaleKernel, dim3(gridFor(r0)), dim3(256), 0, mf->ctx->stream, d_y, ldy, r0, ncols, beta);
-    if (rows > r1)
-        hipLaunchKernelGGL(scaleKernel, dim3(gridFor(rows - r1)), dim3(256), 0, mf->ctx->stream, d_y + r1, ldy, rows - r1,
-                           ncols, beta);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    if (int rc = scaleRows(mf->ctx, d_y, ldy, r0, ncols, beta))
+        return rc;
+    return scaleRows(mf->ctx, d_y + r1, ldy, rows - r1, ncols, beta);
 }
 
 int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg,
                        double* d_y, size_t ldy, double* d_yghost, size_t ldyg, int ncols, double alpha, double beta)
+{
+    return mfApplyElems(mf, which, d_x, ldx, d_xghost, ldxg, d_y, ldy, d_yghost, ldyg, ncols, alpha, beta, mf && mf->fuse);
+}
+extern "C++" int mfApplyElems(l3k_mf* mf, int which, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, double* d_y, size_t ldy,
+                              double* d_yghost, size_t ldyg, int ncols, double alpha, double beta, int fuse)
 {
     if (!mf || !d_x || !d_y)
     {
@@ -1089,7 +1096,7 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     }
     applyOperands(a, d_x, ldx, d_xghost, ldxg, d_y, ldy, d_yghost, ldyg, alpha);
     a.beta      = beta;
-    a.fuse_beta = mf->fuse;
+    a.fuse_beta = fuse;
     const auto  launch = [&](const l3k::dev::Instance* inst, l3k::dev::ElemArgs& ac) {
         return forEachLaunchRange(mf, which, ac, [&](l3k::dev::ElemArgs& r) { return inst->apply(r, mf->blobPtr(), mf->ctx->stream); });
     };
@@ -1119,6 +1126,16 @@ int l3k_mf_apply_elems(l3k_mf* mf, int which, const double* d_x, size_t ldx, con
     return 0;
 }
 
+extern "C++" int dirichletRowsOf(l3k_ctx* ctx, const l3k_mesh* m, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha)
+{
+    const auto& rows = m->owned_dirichlet_rows;
+    if (rows.n == 0)
+        return 0;
+    hipLaunchKernelGGL(dirichletRowsKernel, dim3(gridFor(int64_t(rows.n))), dim3(256), 0, ctx->stream, rows.ptr,
+                       int64_t(rows.n), d_x, ldx, d_y, ldy, ncols, alpha);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
 int l3k_mf_dirichlet_rows(l3k_mf* mf, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha)
 {
     if (!mf || !d_x || !d_y)
@@ -1126,13 +1143,7 @@ int l3k_mf_dirichlet_rows(l3k_mf* mf, const double* d_x, size_t ldx, double* d_y
         setError("l3k_mf_dirichlet_rows: null argument");
         return -1;
     }
-    const auto& rows = mf->mesh->owned_dirichlet_rows;
-    if (rows.n == 0)
-        return 0;
-    hipLaunchKernelGGL(dirichletRowsKernel, dim3(gridFor(int64_t(rows.n))), dim3(256), 0, mf->ctx->stream, rows.ptr,
-                       int64_t(rows.n), d_x, ldx, d_y, ldy, ncols, alpha);
-    L3K_HIP(hipGetLastError());
-    return 0;
+    return dirichletRowsOf(mf->ctx, mf->mesh, d_x, ldx, d_y, ldy, ncols, alpha);
 }
 
 // s[1] += sum over the owned Dirichlet rows of x_d^2 (their share of x^T A x: those rows of the operator are the identity)
@@ -1299,11 +1310,16 @@ int l3k_mf_dirichlet_finalize(l3k_mf* mf, const double* d_dirichlet_vals, size_t
         setError("l3k_mf_dirichlet_finalize: null argument");
         return -1;
     }
-    const auto& rows = mf->mesh->owned_dirichlet_rows;
+    return dirichletFinalizeOf(mf->ctx, mf->mesh, d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, mf->n_rhs);
+}
+extern "C++" int dirichletFinalizeOf(l3k_ctx* ctx, const l3k_mesh* m, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs,
+                                     size_t ldr, int n_rhs)
+{
+    const auto& rows = m->owned_dirichlet_rows;
     if (rows.n == 0)
         return 0;
-    hipLaunchKernelGGL(dirichletFinalizeKernel, dim3(gridFor(int64_t(rows.n))), dim3(256), 0, mf->ctx->stream, rows.ptr,
-                       int64_t(rows.n), d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, mf->n_rhs);
+    hipLaunchKernelGGL(dirichletFinalizeKernel, dim3(gridFor(int64_t(rows.n))), dim3(256), 0, ctx->stream, rows.ptr, int64_t(rows.n),
+                       d_dirichlet_vals, ldg, d_diag, d_rhs, ldr, n_rhs);
     L3K_HIP(hipGetLastError());
     return 0;
 }

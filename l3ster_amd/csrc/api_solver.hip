@@ -868,6 +868,70 @@ int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb*
     return l3k::solver::pcgSolvePrecond(csrOp(A), "l3k_csr_pcg_solve_cheb", d_b, d_x, chebPrecond(c), opts, result);
 }
 } // extern "C"
+// ------------------------------------------------------------------------------------------------ sums of matrix-free terms
+// The same loops on l3k_mfs (include/l3k.h), single rank
+namespace
+{
+using l3k::solver::mfsOp;
+int mfsSolvable(const l3k_mfs* S, const char* message, const char* who)
+{
+    if (!S->finalized)
+    {
+        setError("%s: call l3k_mfs_finalize first", who);
+        return -1;
+    }
+    if (S->rows->n_ghost_nodes != 0)
+    {
+        setError(message, who);
+        return -1;
+    }
+    return 0;
+}
+} // namespace
+extern "C" {
+int l3k_mfs_pcg_solve(l3k_mfs* S, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!S || !d_b || !d_x || !result)
+    {
+        setError("l3k_mfs_pcg_solve: null argument");
+        return -1;
+    }
+    if (int rc = mfsSolvable(S, pcg_single_rank, "l3k_mfs_pcg_solve"))
+        return rc;
+    return pcgSolve(mfsOp(S), d_b, d_x, d_minv, opts, result);
+}
+int l3k_mfs_pcg_solve_cols(l3k_mfs* S, const double* d_b, size_t ldb, double* d_x, size_t ldx, int ncols, const double* d_minv,
+                           const l3k_cg_opts* opts, l3k_cg_result* results)
+{
+    if (int rc = pcgCheckCols("l3k_mfs_pcg_solve_cols", S, S ? size_t(S->rows->nOwnedDofs()) : 0, d_b, ldb, d_x, ldx, ncols, results))
+        return rc;
+    if (int rc = mfsSolvable(S, pcg_single_rank, "l3k_mfs_pcg_solve")) // (each column is an l3k_mfs_pcg_solve)
+        return rc;
+    return pcgSolveCols(mfsOp(S), d_b, ldb, d_x, ldx, ncols, d_minv, opts, results);
+}
+int l3k_mfs_cheb_create(l3k_mfs* S, const double* d_minv, const l3k_cheb_opts* opts, l3k_cheb** out)
+{
+    if (!S || !d_minv || !out)
+    {
+        setError("l3k_mfs_cheb_create: null argument");
+        return -1;
+    }
+    if (int rc = mfsSolvable(S, cheb_single_rank, "l3k_mfs_cheb_create"))
+        return rc;
+    return chebCreate(mfsOp(S), "l3k_mfs_cheb_create", d_minv, opts, out);
+}
+int l3k_mfs_pcg_solve_cheb(l3k_mfs* S, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
+{
+    if (!S || !d_b || !d_x || !c || !result)
+    {
+        setError("l3k_mfs_pcg_solve_cheb: null argument");
+        return -1;
+    }
+    if (int rc = mfsSolvable(S, cheb_single_rank, "l3k_mfs_pcg_solve_cheb"))
+        return rc;
+    return l3k::solver::pcgSolvePrecond(mfsOp(S), "l3k_mfs_pcg_solve_cheb", d_b, d_x, chebPrecond(c), opts, result);
+}
+} // extern "C"
 // ------------------------------------------------------------------------------------------------ collective solves
 // The same loops on a partitioned operator (include/l3k.h; solve/BelosSolvers.hpp:116-122 in an MPI run).  Every refusal comes
 // before the first collective call: a rank that returns -1 here has left no peer waiting inside an exchange

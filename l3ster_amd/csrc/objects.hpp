@@ -506,6 +506,35 @@ struct l3k_bnd : KernelTerm
     DevBuf< double >       coef_ws;      // coefficient workspace of l3k_bnd_local_assemble and of the accumulating route
 };
 
+// the sum of several terms over one set of rows (api_mfs.hip): domain and boundary terms in the order they were added, on `rows` or
+// on meshes over the same nodes; nothing is owned but the coverage mask
+struct l3k_mfs
+{
+    struct Term
+    {
+        l3k_mf*  mf; // exactly one of the two
+        l3k_bnd* bnd;
+    };
+    l3k_ctx*            ctx;
+    l3k_mesh*           rows;
+    int                 n_rhs;
+    bool                finalized = false;
+    std::vector< Term > terms;
+    DevBuf< uint8_t >   active; // [n_local_dofs]: 1 where a term has an entry (l3k_mfs_finalize)
+    DevBuf< unsigned long long > word; // what the checking and counting kernels report through
+    int64_t             n_active_rows = 0;
+};
+// api.hip: l3k_mf_apply_elems with the fused store of the exclusive rows switched by the caller (`fuse`: l3k_mf::fuse for a system
+// on its own; 0 inside a sum, where every row is accumulated and none written); the system itself is not modified
+int mfApplyElems(l3k_mf* mf, int which, const double* d_x, size_t ldx, const double* d_xghost, size_t ldxg, double* d_y, size_t ldy,
+                 double* d_yghost, size_t ldyg, int ncols, double alpha, double beta, int fuse);
+// api.hip: y <- beta y on the first `rows` rows of `ncols` columns (beta == 1: nothing), and y += alpha x on the owned Dirichlet rows
+// of a mesh, on the context's stream
+int scaleRows(l3k_ctx* ctx, double* d_y, size_t ldy, int64_t rows, int ncols, double beta);
+int dirichletRowsOf(l3k_ctx* ctx, const l3k_mesh* m, const double* d_x, size_t ldx, double* d_y, size_t ldy, int ncols, double alpha);
+// ... and diag = 1, rhs = g (null: 0) there, the last step of a diag / rhs pass
+int dirichletFinalizeOf(l3k_ctx* ctx, const l3k_mesh* m, const double* d_dirichlet_vals, size_t ldg, double* d_diag, double* d_rhs, size_t ldr,
+                        int n_rhs);
 // api.hip: the system's device instantiation for `ncols` columns, or nullptr with the error set (callers return -4)
 const l3k::dev::Instance* instanceFor(const l3k_mf* mf, int ncols);
 // ... of a boundary term (`what`: optional prefix of the message)

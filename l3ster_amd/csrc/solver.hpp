@@ -11,14 +11,14 @@ namespace l3k::solver
 {
 // The operator of a solve: n rows (of a partitioned system: this rank's owned rows), y <- A x, and y <- A x with s[1] <- this rank's
 // <x, A x>, on the context's stream.  The PCG loops, the power method and the Chebyshev recurrence are written ONCE over this
-// value; mfOp and csrOp make it for one rank, mfDistOp and csrDistOp for a partitioned system.  reduce_fn and its object `halo` are the reduction hook:
+// value; mfOp, mfsOp and csrOp make it for one rank, mfDistOp and csrDistOp for a partitioned system.  reduce_fn and its object `halo` are the reduction hook:
 // the loops call reduce(s, first, count) wherever a dot product has landed in s[first .. first + count); the partitioned makers
 // set l3k_halo_allreduce_sum over the halo's ranks, the single-rank makers leave it null and nothing is enqueued
 struct LinOp
 {
     l3k_ctx* ctx;
     int64_t  n;
-    void*    object; // the l3k_mf, l3k_csr or l3k_csr_dist behind it
+    void*    object; // the l3k_mf, l3k_mfs, l3k_csr or l3k_csr_dist behind it
     int (*apply_fn)(const LinOp&, const double*, double*);
     int (*energy_fn)(const LinOp&, const double*, double*, double*);
     int (*reduce_fn)(void* halo, double* d_vals, int count) = nullptr;
@@ -31,6 +31,8 @@ struct LinOp
     int reduce(double* d_s, int first, int count) const { return reduce_fn ? reduce_fn(halo, d_s + first, count) : 0; }
 };
 LinOp mfOp(l3k_mf* mf);
+// the sum of several matrix-free terms (api_mfs.hip): l3k_mfs_apply, and <x, A x> from the fixed-order dot product behind it
+LinOp mfsOp(l3k_mfs* S);
 // the partitioned operators: (l3k_mf, l3k_halo) through l3k_mf_apply_dist, l3k_csr_dist through l3k_csr_dist_apply / _apply_energy
 LinOp mfDistOp(l3k_mf* mf, l3k_halo* halo);
 LinOp csrDistOp(l3k_csr_dist* D);

@@ -84,6 +84,42 @@ class PartitionedMesh:
     synthetic_vector = system.CubePartition.synthetic_vector
 
 
+def element_subset(part, elems):
+    """Some of the elements of `part` (a CubePartition, SquarePartition, ElevatedMesh, PartitionedMesh, ...) as a part over the SAME
+    nodes: what system.DeviceMesh takes for a term of a system.MultiTermSystem that lives on part of the mesh.  elems: indices
+    into part's elements, each at most once; their order is kept, except that the interior elements (those below
+    part.n_interior_elems) come first, stably, and n_interior_elems is counted again.  Everything at node level (node counts,
+    numbering, ghosts, neighbour lists, boundary flags of the nodes) is part's own, shared and not copied; elem_index holds the
+    element of `part` behind each element of the subset.  ValueError for an index outside the mesh or listed twice."""
+    import copy
+    idx = np.asarray(elems)
+    if idx.size and not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("element_subset: elems must be integer indices")
+    idx = idx.astype(np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= part.n_elems):
+        bad = idx[(idx < 0) | (idx >= part.n_elems)][0]
+        raise ValueError(f"element_subset: element {int(bad)} outside [0, {part.n_elems})")
+    if np.unique(idx).size != idx.size:
+        raise ValueError("element_subset: an element is listed twice")
+    interior = idx < part.n_interior_elems
+    idx = np.concatenate([idx[interior], idx[~interior]])  # interior first, stable
+    sub = copy.copy(part)  # (shallow: the node-level arrays are the very objects of `part`)
+    sub.elem_nodes = np.ascontiguousarray(np.asarray(part.elem_nodes)[idx])
+    sub.elem_verts = np.ascontiguousarray(np.asarray(part.elem_verts)[idx])
+    sub.n_elems, sub.n_interior_elems = int(idx.size), int(np.count_nonzero(interior))
+    sub.elem_index = idx
+    for name in ("elem_boundary", "elem_domain", "elem_global"):  # per-element attributes some parts carry
+        if hasattr(part, name):
+            setattr(sub, name, np.asarray(getattr(part, name))[idx])
+    if hasattr(part, "face_elem"):  # boundary elements by physical id (ElevatedMesh): those of absent elements are the side of none
+        where = np.full(part.n_elems, -1, dtype=np.int64)
+        where[idx] = np.arange(idx.size)
+        fe = np.asarray(part.face_elem, dtype=np.int64)
+        sub.face_elem = np.where(fe >= 0, where[np.maximum(fe, 0)], -1)
+        sub.face_side = np.where(sub.face_elem >= 0, np.asarray(part.face_side), 255).astype(np.uint8)
+    return sub
+
+
 def rcb_partition(elem_verts, n_parts):
     """Recursive coordinate bisection of the element centroids into n_parts parts of (nearly) equal element counts: the
     stand-in for mesh::partitionMesh (mesh/PartitionMesh.hpp:142-183, METIS_PartMeshNodal) when no partition vector comes

@@ -126,11 +126,16 @@ def _overlap(u, v, n):
 
 def _entry(system, name):
     """(the entry point `name` for this kind of system, its number of rows): l3k_<name> for a MatrixFreeSystem,
-    l3k_csr_<name> for a system.CsrOperator -- the same loops inside the library on either operator"""
+    l3k_csr_<name> for a system.CsrOperator, l3k_mfs_<name> for a system.MultiTermSystem -- the same loops inside the library on
+    each operator"""
     from . import capi
-    from .system import CsrOperator
+    from .system import CsrOperator, MultiTermSystem
     if isinstance(system, CsrOperator):
         return getattr(capi.load(), "l3k_csr_" + name), system.n
+    if isinstance(system, MultiTermSystem):
+        if name == "pcg_solve_pmg":
+            raise capi.L3KError("p-multigrid is not provided for a MultiTermSystem")
+        return getattr(capi.load(), "l3k_mfs_" + name), system.mesh.n_owned_dofs
     return getattr(capi.load(), "l3k_" + name), system.mesh.n_owned_dofs
 
 

@@ -7,6 +7,7 @@ Mirrors (names, argument meaning, error behaviour) for this path only:
   * ElevatedMesh      -- readMesh + convertMeshToOrder for unstructured quads / hexes, boundaries by physical id (getBoundary)
   * MatrixFreeSystem  -- algsys::MatrixFreeSystem: assembleProblem -> Operator.apply(X, Y, alpha, beta)
                          (algsys/MatrixFreeSystem.hpp:24-89,1020-1140)
+  * MultiTermSystem   -- ... as the sum of several assembleProblem calls: kernels by domain and by dof set (:24-89, 789-802)
 Vectors are torch tensors of shape (ncols, n_owned_dofs), i.e. column-major [row][col] multivectors with owned rows
 only -- the host-view layout of the Tpetra multivectors of the reference.  torch is plumbing here (device memory,
 streams); all compute goes through libl3k.so.
@@ -574,6 +575,12 @@ class ElevatedMesh:
         if missing.size:
             raise L3KError(f"the mesh has no domain with id {missing.tolist()}")
         return np.nonzero(np.isin(self.elem_domain, ids))[0]
+
+    def subset(self, domain_ids):
+        """The elements with the listed domain ids as a part over the nodes of this mesh (partition.element_subset): what
+        DeviceMesh takes for a term of a MultiTermSystem that lives on those domains only."""
+        from . import partition
+        return partition.element_subset(self, self.elements_of(domain_ids))
 
 
 class DeviceMesh:
@@ -1600,3 +1607,118 @@ class AssembledSystem:
         w = torch.empty((max(count, 0), self.n_rhs, nb), dtype=torch.float64, device=dev)
         check(capi.load().l3k_asm_schur_updates(self._h, first, count, _ptr(W), _ptr(w)))
         return W, w
+
+
+class MultiTermSystem:
+    """algsys::MatrixFreeSystem as the sum of its assembleProblem calls (l3k_mfs_*; algsys/MatrixFreeSystem.hpp:24-89): any number
+    of MatrixFreeSystem and BoundaryTerm terms over the rows of `mesh`, each on `mesh` itself or on a DeviceMesh over the same
+    nodes that holds some of the elements (DeviceMesh(ctx, partition.element_subset(part, elems), dofs_per_node, the same mask);
+    ElevatedMesh.subset(domain_ids) for the domains of a mesh file).  add(term) ..., finalize(), then the calls of a
+    MatrixFreeSystem with its names and arguments: code that drives the split-phase pieces takes either.  solve.pcg and
+    solve.ChebyshevPreconditioner take the object as they take a MatrixFreeSystem.  The terms are kept alive here."""
+
+    def __init__(self, mesh, n_rhs=1):
+        self.mesh, self.ctx, self.n_rhs = mesh, mesh.ctx, n_rhs
+        self.terms = []
+        self._h = C.c_void_p()
+        check(capi.load().l3k_mfs_create(mesh._h, n_rhs, C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and capi is not None:
+            capi.load().l3k_mfs_destroy(self._h)
+            self._h = None
+
+    def add(self, term):
+        """assembleProblem(kernel, domain ids / boundary ids): a MatrixFreeSystem (without attached boundary terms) or a
+        BoundaryTerm joins the sum; refused after finalize()"""
+        if isinstance(term, BoundaryTerm):
+            check(capi.load().l3k_mfs_add_boundary(self._h, term._h))
+        elif isinstance(term, MatrixFreeSystem):
+            check(capi.load().l3k_mfs_add_domain(self._h, term._h))
+        else:
+            raise L3KError("MultiTermSystem.add takes a MatrixFreeSystem or a BoundaryTerm")
+        self.terms.append(term)
+        return self
+
+    def finalize(self):
+        """The coverage mask of the terms and the number of active rows (l3k_mfs_finalize); opens apply, diag_rhs and the solvers"""
+        check(capi.load().l3k_mfs_finalize(self._h))
+        return self
+
+    @property
+    def info(self):
+        """n_terms, n_rows (owned dofs), n_active_rows, n_dirichlet_rows, n_rhs, finalized"""
+        import types
+        i = capi.MfsInfo()
+        check(capi.load().l3k_mfs_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.MfsInfo._fields_})
+
+    def active(self):
+        """uint8 device tensor over the local dofs: 1 where a term has an entry"""
+        import torch
+        out = torch.empty(self.mesh.n_owned_dofs + self.mesh.n_ghost_dofs, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+        check(capi.load().l3k_mfs_active(self._h, _ptr(out)))
+        return out
+
+    _cols = staticmethod(MatrixFreeSystem._cols)
+
+    def apply(self, X, Y, alpha=1.0, beta=0.0):
+        nc, ldx = self._cols(X)
+        nc2, ldy = self._cols(Y)
+        if nc != nc2:
+            raise L3KError("X and Y must have the same number of columns")  # MatrixFreeSystem.hpp:1035
+        check(capi.load().l3k_mfs_apply(self._h, _ptr(X), ldx, _ptr(Y), ldy, nc, alpha, beta))
+        return Y
+
+    def apply_energy(self, X, Y, S):
+        """Y <- A X (one column) and S[1] <- <X, A X> (l3k_mfs_apply_energy): S is the PCG's device scalar block (8 doubles)"""
+        check(capi.load().l3k_mfs_apply_energy(self._h, _ptr(X), _ptr(Y), _ptr(S)))
+        return Y
+
+    def scale(self, Y, beta):
+        nc, ldy = self._cols(Y)
+        check(capi.load().l3k_mfs_scale(self._h, _ptr(Y), ldy, nc, beta))
+
+    def apply_elems(self, which, X, XG, Y, YG, alpha, beta):
+        nc, ldx = self._cols(X)
+        _, ldy = self._cols(Y)
+        ldxg = self._cols(XG)[1] if XG is not None else 0
+        ldyg = self._cols(YG)[1] if YG is not None else 0
+        check(capi.load().l3k_mfs_apply_elems(self._h, which, _ptr(X), ldx, _ptr(XG), ldxg, _ptr(Y), ldy, _ptr(YG), ldyg,
+                                              nc, alpha, beta))
+
+    def dirichlet_rows(self, X, Y, alpha):
+        nc, ldx = self._cols(X)
+        _, ldy = self._cols(Y)
+        check(capi.load().l3k_mfs_dirichlet_rows(self._h, _ptr(X), ldx, _ptr(Y), ldy, nc, alpha))
+
+    def diag_rhs(self, dirichlet_vals=None, which=2, diag=None, rhs=None, diag_ghost=None, rhs_ghost=None, finalize=True):
+        """computeDiagAndRhs summed over the terms: the arguments and results of MatrixFreeSystem.diag_rhs"""
+        import torch
+        n_owned, n_ghost = self.mesh.n_owned_dofs, self.mesh.n_ghost_dofs
+        dev = torch.device("cuda", self.ctx.device)
+        if diag is None:
+            diag = torch.zeros(n_owned, dtype=torch.float64, device=dev)
+        if rhs is None:
+            rhs = torch.zeros((self.n_rhs, n_owned), dtype=torch.float64, device=dev)
+        if n_ghost and diag_ghost is None:
+            diag_ghost = torch.zeros(n_ghost, dtype=torch.float64, device=dev)
+            rhs_ghost = torch.zeros((self.n_rhs, n_ghost), dtype=torch.float64, device=dev)
+        g = dirichlet_vals
+        check(capi.load().l3k_mfs_diag_rhs(self._h, which, _ptr(g), 0 if g is None else g.shape[1], _ptr(diag), _ptr(rhs),
+                                           rhs.shape[1], _ptr(diag_ghost), _ptr(rhs_ghost), max(n_ghost, 1), int(finalize)))
+        return diag, rhs
+
+    def jacobi_inverse(self, diag, damping=1.0, threshold=0.0):
+        """sign(d) damping / max(|d|, threshold) on the active owned rows, 0 on the rows no term covers (l3k_mfs_jacobi_inverse): the
+        PCG leaves x as it is there"""
+        import torch
+        if diag.numel() != self.mesh.n_owned_dofs or not diag.is_contiguous():
+            raise L3KError("diag must be a contiguous tensor over the owned dofs")
+        out = torch.empty_like(diag)
+        check(capi.load().l3k_mfs_jacobi_inverse(self._h, _ptr(diag), float(damping), float(threshold), _ptr(out)))
+        return out
+
+    def new_ghost_buffer(self, ncols, like):
+        import torch
+        return torch.zeros((ncols, max(self.mesh.n_ghost_dofs, 1)), dtype=torch.float64, device=like.device)
