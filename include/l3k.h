@@ -1420,6 +1420,94 @@ int l3k_vtk_pvtu_text(const char* path, int n_ranks, int n_groups, const char* c
 int l3k_vtk_vtu_header_text(int64_t n_points, int64_t n_cells, const uint64_t* encoded_mesh_bytes, int n_groups, const char* const* names,
                             const int* n_comps, char* buf, size_t capacity, size_t* needed);
 
+/* ---- restarted GMRES -----------------------------------------------------------------------------------------------------
+ * The reference's second Krylov solver: Gmres, a Belos adapter (solve/BelosSolvers.hpp:124-130) with the restart options of
+ * IterSolverOpts, max_restarts = 39 and restart_length = 250 (solve/SolverInterface.hpp:26-37).  Belos is not part of the reference
+ * tree; the arithmetic is the textbook restarted GMRES(m) of Saad and Schultz for one column: Arnoldi with classical Gram-Schmidt
+ * and one re-orthogonalisation (CGS2), Givens rotations on the Hessenberg matrix, all on the context's stream, single rank.  It
+ * serves any square operator -- l3k_csr_create accepts matrices that are not symmetric positive definite, which the PCG cannot
+ * solve -- on l3k_mf, l3k_mfs and l3k_csr, with the preconditioners of the PCG: none, Jacobi d_minv, l3k_cheb, l3k_pmg.
+ *
+ * The preconditioner is applied on the RIGHT (Belos's adapter calls setLeftPrec): the iteration is GMRES on the live principal block
+ * of A M^-1, so the residual it minimises is the true residual b - A x over the live rows, and achieved_tol has the meaning it
+ * has in l3k_cg_result.  A row is live where the mask -- d_minv, or the minv the l3k_cheb / the finest smoother of the l3k_pmg was
+ * created on; NULL: every row -- is non-zero on its bits.  Frozen rows keep x bit for bit and carry r = 0.
+ *
+ *   cycle:  r = mask(b - A x); beta = ||r||; res = beta / scale   (residual_scaling as in l3k_cg_opts)
+ *           stop if res <= tol, iterations = max_iters, or more than max_restarts restarts would be needed
+ *           v_0 = r / beta; g = beta e_0
+ *           for k = 0 .. m - 1:  z = M^-1 v_k;  w = A z
+ *               h1 = V^T w;  w -= V h1, h2 = V^T w;  w -= V h2, t = V^T w, nu^2 = <w, w>        (V = [v_0 .. v_k])
+ *               H[0..k, k] = h1 + h2, H[k+1, k] = nu; the stored Givens rotations, a new one, g;  estimate = |g_{k+1}| / scale
+ *               orth_loss = max(orth_loss, max_j |t_j| / nu);  iterations += 1
+ *               breakdown if nu <= 2^-52 ||H[0..k, k]||: the cycle ends here;  else v_{k+1} = w / nu
+ *               every check_every iterations and at the end of the cycle the host reads 64 bytes and leaves if estimate <= tol
+ *           y = R^-1 g;  x += M^-1 (V y)
+ * iterations counts Arnoldi steps; the explicit residual at the head of every cycle is not counted.  The solve ends only on an
+ * explicit residual: when the estimate passes and the residual does not, another cycle starts and counts as a restart.  Every dot
+ * product is a two-stage reduction in a fixed order without atomics: equal bits for equal input on any context.
+ *
+ * l3k_gmres: the workspace of GMRES(restart_length) on n rows -- restart_length + 1 basis vectors at a distance ld (n rounded up to
+ * a multiple of 4), w, z, u, H, g, the rotations, the partial sums, the scalar block.  restart_length above n is lowered to n
+ * (l3k_gmres_info).  max_bytes: 0 = no guard; otherwise creation refuses a workspace above it and names the bytes needed, as
+ * l3k_chol_create does.  One workspace serves any number of solves of its n, one at a time.
+ * opts == NULL: {1e-6, 10000, 0, 1, 39}.  -1 with a message naming the call: a null argument; a workspace whose n is not the
+ * operator's number of rows; restart_length < 1, or min(restart_length, n) above 2046; b and x overlapping; an l3k_mf with ghost nodes or an l3k_mfs that is not
+ * finalized or has ghost nodes (single rank only: there is no collective GMRES); a cheb or pmg made for another system; in the
+ * pieces k < 1 or an ld that is not a multiple of 4. */
+typedef struct l3k_gmres l3k_gmres;
+typedef struct
+{
+    double tol;
+    int    max_iters;
+    int    residual_scaling;
+    int    check_every;
+    int    max_restarts;
+} l3k_gmres_opts;
+typedef struct
+{
+    double achieved_tol; /* ||mask(b - A x)|| / scale of the last explicit residual                    */
+    double estimate;     /* |g_{k+1}| / scale at the last step the host looked at                      */
+    double orth_loss;    /* max over the steps of max_j |<v_j, w>| / nu after the two projections      */
+    int    iterations, restarts, converged, breakdown;
+} l3k_gmres_result;
+typedef struct
+{
+    int64_t n, ld;
+    int     restart_length;
+    size_t  bytes;
+} l3k_gmres_info;
+/* solve/BelosSolvers.hpp:124-130, solve/SolverInterface.hpp:26-37 (all entries of this section) */
+int l3k_gmres_create(l3k_ctx* ctx, int64_t n, int restart_length, size_t max_bytes, l3k_gmres** out);
+int l3k_gmres_info_get(const l3k_gmres* G, l3k_gmres_info* out);
+int l3k_gmres_destroy(l3k_gmres* G);
+int l3k_gmres_solve(l3k_gmres* G, l3k_mf* mf, const double* d_b, double* d_x, const double* d_minv, const l3k_gmres_opts* opts,
+                    l3k_gmres_result* result);
+int l3k_gmres_solve_cheb(l3k_gmres* G, l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_gmres_opts* opts,
+                         l3k_gmres_result* result);
+int l3k_gmres_solve_pmg(l3k_gmres* G, l3k_mf* mf, const double* d_b, double* d_x, l3k_pmg* M, const l3k_gmres_opts* opts,
+                        l3k_gmres_result* result);
+int l3k_csr_gmres_solve(l3k_gmres* G, l3k_csr* A, const double* d_b, double* d_x, const double* d_minv, const l3k_gmres_opts* opts,
+                        l3k_gmres_result* result);
+int l3k_csr_gmres_solve_cheb(l3k_gmres* G, l3k_csr* A, const double* d_b, double* d_x, l3k_cheb* c, const l3k_gmres_opts* opts,
+                             l3k_gmres_result* result);
+int l3k_mfs_gmres_solve(l3k_gmres* G, l3k_mfs* S, const double* d_b, double* d_x, const double* d_minv, const l3k_gmres_opts* opts,
+                        l3k_gmres_result* result);
+int l3k_mfs_gmres_solve_cheb(l3k_gmres* G, l3k_mfs* S, const double* d_b, double* d_x, l3k_cheb* c, const l3k_gmres_opts* opts,
+                             l3k_gmres_result* result);
+/* The pieces, for tests and for hosts that run the loop themselves (solve/BelosSolvers.hpp:124-130, solve/SolverInterface.hpp:26-37).
+ * d_V: k basis vectors, column j at d_V + j * ld, ld a multiple of 4 and >= n; rows in [n, ld) are never read.  d_mask NULL: every
+ * row live; w counts as 0 on a frozen row whatever it holds there.
+ *   multi_dot: h[j] = <v_j, w> for j < k, h[k] = <w, w>
+ *   project  : w -= V h_in (0 stored on the frozen rows), then h_out as multi_dot of the new w; h_in[k] is not read
+ *   combine  : x += [minv (.)] sum_j y_j v_j on the live rows of minv
+ * All three are queued on the context's stream; multi_dot and project keep their partial sums in a buffer of the context, grown
+ * on demand, so two of them must not run at the same time on one context. */
+int l3k_gmres_multi_dot(l3k_ctx* ctx, const double* d_V, size_t ld, int k, const double* d_w, const double* d_mask, int64_t n, double* d_h);
+int l3k_gmres_project(l3k_ctx* ctx, const double* d_V, size_t ld, int k, double* d_w, const double* d_mask, int64_t n, const double* d_h_in,
+                      double* d_h_out);
+int l3k_gmres_combine(l3k_ctx* ctx, const double* d_V, size_t ld, int k, const double* d_y, const double* d_minv, int64_t n, double* d_x);
+
 #ifdef __cplusplus
 }
 #endif

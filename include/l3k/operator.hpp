@@ -17,6 +17,7 @@
 //   l3k::ElementSubset           ~ the elements of some domains as a mesh over the same nodes (a term of a MultiTermSystem)
 //   l3k::AssembledSystem         ~ algsys::AssembledSystem: beginAssembly / assembleProblem / endAssembly, hexes and quads
 //   l3k::CsrOperator             ~ the assembled / condensed tpetra_crsmatrix_t in front of Belos  solve/BelosSolvers.hpp:116-122
+//   l3k::Gmres                   ~ Gmres, the restarted GMRES in front of the same operators      solve/BelosSolvers.hpp:124-130
 //   l3k::DistributedCsr          ~ ... of an MPI run: the ranks' local matrices applied as one (sub-assembled form)
 //       AssembledSystem(mesh, halo, ...) ~ algsys::AssembledSystem on one rank of a partitioned mesh
 //   l3k::BoundaryTerm            ~ a BoundaryEquationKernel on a set of boundary views   algsys/EvaluateLocalOperator.hpp:238-330
@@ -885,6 +886,80 @@ public:
 
 private:
     l3k_chol* m_chol{};
+};
+
+// Restarted GMRES(restart_length) on a single-rank operator (l3k_gmres_*): alg_sys.solve(Gmres{opts, precond}), the reference's
+// second Krylov solver (solve/BelosSolvers.hpp:124-130, restart_length = 250 and max_restarts = 39 of solve/SolverInterface.hpp:26-37),
+// for systems that are not symmetric positive definite.  The object is the workspace on n rows (restart_length above n is lowered
+// to n; max_bytes: 0 = no guard, otherwise the constructor throws and names the bytes needed); it serves any number of solves.
+// The preconditioner acts on the right: achieved_tol is the true residual over the rows with minv != 0, which keep x.  RAII, move-only.
+//   solve(system, b, x, minv)  ~ no preconditioner (nullptr) or Jacobi; throws "Solver failed to converge" like the reference
+//   solve(system, b, x, cheb)  ~ with the Chebyshev-Jacobi preconditioner created on that system
+//   info                       ~ n, ld, restart_length, bytes
+class Gmres
+{
+public:
+    static constexpr l3k_gmres_opts default_opts{1e-6, 10000, 0, 1, 39};
+    Gmres(Context& ctx, int64_t n, int restart_length = 250, size_t max_bytes = 0)
+    {
+        check(l3k_gmres_create(ctx.get(), n, restart_length, max_bytes, &m_gmres));
+    }
+    Gmres(const Gmres&)            = delete;
+    Gmres& operator=(const Gmres&) = delete;
+    Gmres(Gmres&& o) noexcept : m_gmres{o.m_gmres} { o.m_gmres = nullptr; }
+    ~Gmres() { l3k_gmres_destroy(m_gmres); }
+    l3k_gmres_result solve(const MatrixFreeSystem& A, const double* d_b, double* d_x, const double* d_minv, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_gmres_solve(m_gmres, A.get(), d_b, d_x, d_minv, &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const MatrixFreeSystem& A, const double* d_b, double* d_x, const Chebyshev& cheb, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_gmres_solve_cheb(m_gmres, A.get(), d_b, d_x, cheb.get(), &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const MultiTermSystem& A, const double* d_b, double* d_x, const double* d_minv, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_mfs_gmres_solve(m_gmres, A.get(), d_b, d_x, d_minv, &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const MultiTermSystem& A, const double* d_b, double* d_x, const Chebyshev& cheb, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_mfs_gmres_solve_cheb(m_gmres, A.get(), d_b, d_x, cheb.get(), &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const CsrOperator& A, const double* d_b, double* d_x, const double* d_minv, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_csr_gmres_solve(m_gmres, A.get(), d_b, d_x, d_minv, &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const CsrOperator& A, const double* d_b, double* d_x, const Chebyshev& cheb, l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_csr_gmres_solve_cheb(m_gmres, A.get(), d_b, d_x, cheb.get(), &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_info info() const
+    {
+        l3k_gmres_info i{};
+        check(l3k_gmres_info_get(m_gmres, &i));
+        return i;
+    }
+    l3k_gmres* get() const { return m_gmres; }
+
+private:
+    static l3k_gmres_result converged(const l3k_gmres_result& res)
+    {
+        if (!res.converged)
+            throw std::runtime_error{"Solver failed to converge"}; // solve/BelosSolvers.hpp:103
+        return res;
+    }
+    l3k_gmres* m_gmres{};
 };
 
 // The CSR sparsity graph of a mesh over its local dofs, built on the device: computeLocalGraph in front of makeSparsityGraph

@@ -34,6 +34,21 @@ class CgResult(C.Structure):
     _fields_ = [("achieved_tol", C.c_double), ("iterations", C.c_int), ("converged", C.c_int)]
 
 
+class GmresOpts(C.Structure):
+    """l3k_gmres_opts (IterSolverOpts with its restart fields, solve/SolverInterface.hpp:26-37)"""
+    _fields_ = [("tol", C.c_double), ("max_iters", C.c_int), ("residual_scaling", C.c_int), ("check_every", C.c_int),
+                ("max_restarts", C.c_int)]
+
+
+class GmresResult(C.Structure):
+    _fields_ = [("achieved_tol", C.c_double), ("estimate", C.c_double), ("orth_loss", C.c_double), ("iterations", C.c_int),
+                ("restarts", C.c_int), ("converged", C.c_int), ("breakdown", C.c_int)]
+
+
+class GmresInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("ld", C.c_int64), ("restart_length", C.c_int), ("bytes", C.c_size_t)]
+
+
 class ChebOpts(C.Structure):
     """l3k_cheb_opts (Ifpack2ChebyshevPreconditioner::Options, solve/Ifpack2Preconditioners.hpp:107-118)"""
     _fields_ = [("degree", C.c_int), ("cond_est", C.c_double), ("max_power_iters", C.c_int), ("boost_factor", C.c_double),
@@ -399,6 +414,15 @@ SIGNATURES = {
                                     C.POINTER(C.c_size_t)]),
     "l3k_vtk_vtu_header_text": (C.c_int, [C.c_int64, C.c_int64, c_uint64_p, C.c_int, C.POINTER(C.c_char_p), c_int_p, _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
+    "l3k_gmres_create": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_size_t, C.POINTER(_vp)]),
+    "l3k_gmres_info_get": (C.c_int, [_vp, C.POINTER(GmresInfo)]),
+    "l3k_gmres_destroy": (C.c_int, [_vp]),
+    **{name: (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(GmresOpts), C.POINTER(GmresResult)])
+       for name in ("l3k_gmres_solve", "l3k_gmres_solve_cheb", "l3k_gmres_solve_pmg", "l3k_csr_gmres_solve", "l3k_csr_gmres_solve_cheb",
+                    "l3k_mfs_gmres_solve", "l3k_mfs_gmres_solve_cheb")},
+    "l3k_gmres_multi_dot": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),
+    "l3k_gmres_project": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp, _vp]),
+    "l3k_gmres_combine": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

@@ -341,6 +341,19 @@ bool overlap(const double* u, const double* v, int64_t n)
 }
 } // namespace
 
+// the cycle as the preconditioner of the Krylov loops (solver.hpp)
+Precond l3k::solver::pmgPrecond(l3k_pmg* M)
+{
+    PmgLevel& L = M->levels[0];
+    return {M, L.mf, L.smoother->minv, L.n, L.ld,
+            // z <- M^-1 r, then s[2] <- <r, z> in a pass of its own (2 reads) where the loop asks for it
+            [](void* o, const double* r, double* z, double*, double*, double* s) {
+                l3k_pmg* M = static_cast< l3k_pmg* >(o);
+                if (int rc = cycle(M, 0, r, z))
+                    return rc;
+                return s ? l3k::solver::dotInto(M->ctx, r, z, M->levels[0].n, s, 2) : 0;
+            }};
+}
 extern "C" {
 int l3k_pmg_create(l3k_ctx* ctx, int n_levels, const l3k_pmg_level* levels, l3k_pmg** out)
 {
@@ -479,16 +492,7 @@ int l3k_pcg_solve_pmg(l3k_mf* mf, const double* d_b, double* d_x, l3k_pmg* M, co
         setError("l3k_pcg_solve_pmg serves single-rank systems; this mesh has ghost nodes");
         return -1;
     }
-    PmgLevel&     L = M->levels[0];
-    const Precond P{M, L.mf, L.smoother->minv, L.n, L.ld,
-                    // z <- M^-1 r, then s[2] <- <r, z> in a pass of its own (2 reads)
-                    [](void* o, const double* r, double* z, double*, double*, double* s) {
-                        l3k_pmg* M = static_cast< l3k_pmg* >(o);
-                        if (int rc = cycle(M, 0, r, z))
-                            return rc;
-                        return l3k::solver::dotInto(M->ctx, r, z, M->levels[0].n, s, 2);
-                    }};
-    return l3k::solver::pcgSolvePrecond(l3k::solver::mfOp(mf), "l3k_pcg_solve_pmg", d_b, d_x, P, opts, result);
+    return l3k::solver::pcgSolvePrecond(l3k::solver::mfOp(mf), "l3k_pcg_solve_pmg", d_b, d_x, l3k::solver::pmgPrecond(M), opts, result);
 }
 int l3k_pmg_residual(l3k_ctx* ctx, double* d_d, const double* d_r, const double* d_az, const double* d_minv, int64_t n)
 {

@@ -340,16 +340,6 @@ struct CgDriver
 };
 using l3k::solver::LinOp;
 using l3k::solver::Precond;
-LinOp csrOp(l3k_csr* A)
-{
-    return {A->ctx, A->n, A,
-            [](const LinOp& op, const double* x, double* y) {
-                return l3k_csr_apply(static_cast< l3k_csr* >(op.object), x, size_t(op.n), y, size_t(op.n), 1, 1., 0.);
-            },
-            [](const LinOp& op, const double* x, double* y, double* s) {
-                return l3k_csr_apply_energy(static_cast< l3k_csr* >(op.object), x, y, s);
-            }};
-}
 int haloReduce(void* halo, double* d_vals, int count)
 {
     return l3k_halo_allreduce_sum(static_cast< l3k_halo* >(halo), d_vals, count);
@@ -404,6 +394,16 @@ LinOp l3k::solver::mfOp(l3k_mf* mf)
                 return l3k_mf_apply_energy(static_cast< l3k_mf* >(op.object), x, y, s);
             }};
 }
+LinOp l3k::solver::csrOp(l3k_csr* A)
+{
+    return {A->ctx, A->n, A,
+            [](const LinOp& op, const double* x, double* y) {
+                return l3k_csr_apply(static_cast< l3k_csr* >(op.object), x, size_t(op.n), y, size_t(op.n), 1, 1., 0.);
+            },
+            [](const LinOp& op, const double* x, double* y, double* s) {
+                return l3k_csr_apply_energy(static_cast< l3k_csr* >(op.object), x, y, s);
+            }};
+}
 LinOp l3k::solver::mfDistOp(l3k_mf* mf, l3k_halo* halo)
 {
     return {mf->ctx,
@@ -432,6 +432,7 @@ LinOp l3k::solver::csrDistOp(l3k_csr_dist* D)
             &haloReduce,
             l3k::csr::haloOf(D)};
 }
+using l3k::solver::csrOp;
 using l3k::solver::mfOp;
 int l3k::solver::dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, double* d_s, int slot)
 {
@@ -837,15 +838,13 @@ int l3k::solver::pcgSolvePrecond(const LinOp& A, const char* who, const double* 
     cg.report(result);
     return 0;
 }
-namespace
-{
 // the Chebyshev object as the preconditioner of that loop
-Precond chebPrecond(l3k_cheb* c)
+Precond l3k::solver::chebPrecond(l3k_cheb* c)
 {
     return {c, c->op.object, c->minv, c->n, c->ld,
             [](void* o, const double* r, double* z, double* w, double* az, double* s) { return chebApply(static_cast< l3k_cheb* >(o), r, z, w, az, s); }};
 }
-} // namespace
+using l3k::solver::chebPrecond;
 extern "C" {
 int l3k_pcg_solve_cheb(l3k_mf* mf, const double* d_b, double* d_x, l3k_cheb* c, const l3k_cg_opts* opts, l3k_cg_result* result)
 {
@@ -870,10 +869,8 @@ int l3k_csr_pcg_solve_cheb(l3k_csr* A, const double* d_b, double* d_x, l3k_cheb*
 } // extern "C"
 // ------------------------------------------------------------------------------------------------ sums of matrix-free terms
 // The same loops on l3k_mfs (include/l3k.h), single rank
-namespace
-{
 using l3k::solver::mfsOp;
-int mfsSolvable(const l3k_mfs* S, const char* message, const char* who)
+int l3k::solver::mfsSolvable(const l3k_mfs* S, const char* message, const char* who)
 {
     if (!S->finalized)
     {
@@ -887,7 +884,7 @@ int mfsSolvable(const l3k_mfs* S, const char* message, const char* who)
     }
     return 0;
 }
-} // namespace
+using l3k::solver::mfsSolvable;
 extern "C" {
 int l3k_mfs_pcg_solve(l3k_mfs* S, const double* d_b, double* d_x, const double* d_minv, const l3k_cg_opts* opts, l3k_cg_result* result)
 {

@@ -120,8 +120,13 @@ struct l3k_ctx
     // global-memory working sets of the element kernels whose buffers exceed the LDS (ElemArgs::scratch): grown on demand
     double* scratch       = nullptr;
     size_t  scratch_bytes = 0;
+    // partial sums of the GMRES pieces, which are called without a workspace object (l3k_gmres_multi_dot, l3k_gmres_project): grown on demand
+    double* gmres_partials       = nullptr;
+    size_t  gmres_partials_count = 0;
     ~l3k_ctx()
     {
+        if (gmres_partials)
+            (void)hipFree(gmres_partials);
         if (red_ws)
             (void)hipFree(red_ws);
         if (work_counters)

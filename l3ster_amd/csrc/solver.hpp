@@ -51,6 +51,12 @@ struct Precond
 // the iteration of l3k_pcg_solve_cheb / l3k_csr_pcg_solve_cheb / l3k_pcg_solve_pmg (include/l3k.h; `who` in the messages)
 int pcgSolvePrecond(const LinOp& A, const char* who, const double* d_b, double* d_x, const Precond& M, const l3k_cg_opts* opts,
                     l3k_cg_result* result);
+// what api_gmres.hip takes from the PCG's files: the CSR operator value, the Chebyshev object and the p-multigrid cycle as Precond
+// values (apply with d_s == nullptr: no <r, z>), and the test that an l3k_mfs can be solved on one rank (`message` takes `who`)
+LinOp   csrOp(l3k_csr* A);
+Precond chebPrecond(l3k_cheb* c);
+Precond pmgPrecond(l3k_pmg* M);
+int     mfsSolvable(const l3k_mfs* S, const char* message, const char* who);
 // s[slot] <- <u, v> in the fixed order of the PCG's reductions
 int dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, double* d_s, int slot);
 } // namespace l3k::solver

@@ -441,6 +441,105 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
     return _from_c([res], throw_on_fail)[0]
 
 
+class GmresWorkspace:
+    """Handle of l3k_gmres_create: the workspace of restarted GMRES(restart_length) on n rows -- the basis, w, z, u, the Hessenberg
+    matrix, the partial sums -- on the device of `ctx`.  restart_length above n is lowered to n; max_bytes: 0 = no guard, otherwise
+    creation refuses a workspace above it and names the bytes needed.  One workspace serves any number of solves of its n."""
+
+    def __init__(self, ctx, n, restart_length=250, max_bytes=0):
+        from . import capi
+        if int(restart_length) < 1:
+            raise capi.L3KError(f"GmresWorkspace: restart_length = {restart_length} must be at least 1")
+        if int(n) < 1:
+            raise capi.L3KError(f"GmresWorkspace: n = {n} must be at least 1")
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        capi.check(capi.load().l3k_gmres_create(ctx._h, int(n), int(restart_length), int(max_bytes), C.byref(self._h)))
+        i = self.info
+        self.n, self.restart_length = i.n, i.restart_length
+
+    @property
+    def info(self):
+        """n, ld, restart_length, bytes (l3k_gmres_info)"""
+        import types
+        from . import capi
+        i = capi.GmresInfo()
+        capi.check(capi.load().l3k_gmres_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.GmresInfo._fields_})
+
+    def close(self):
+        if getattr(self, "_h", None):
+            from . import capi
+            capi.load().l3k_gmres_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+
+class GmresSolveResult(IterSolveResult):
+    """IterSolveResult with what l3k_gmres_result adds: restarts, breakdown, estimate (the last residual estimate of the
+    recurrence, scaled as tol) and orth_loss (the largest max_j |<v_j, w>| / ||w|| left by the two projections)."""
+
+    def __init__(self, tol, num_iters, converged, restarts, breakdown, estimate, orth_loss):
+        super().__init__(tol, num_iters, converged)
+        self.restarts, self.breakdown, self.estimate, self.orth_loss = restarts, breakdown, estimate, orth_loss
+
+    def __repr__(self):
+        return (f"GmresSolveResult(tol={self.tol:.3e}, num_iters={self.num_iters}, converged={self.converged}, "
+                f"restarts={self.restarts}, breakdown={self.breakdown}, estimate={self.estimate:.3e}, orth_loss={self.orth_loss:.3e})")
+
+
+def gmres(system, b, x, minv=None, precond=None, tol=1e-6, max_iters=10_000, residual_scaling="none", check_every=1,
+          restart_length=250, max_restarts=39, workspace=None, throw_on_fail=True):
+    """Restarted GMRES(restart_length) behind the C ABI (l3k_gmres_solve; the reference's Gmres, solve/BelosSolvers.hpp:124-130, with
+    max_restarts and restart_length of solve/SolverInterface.hpp:26-37): right preconditioning, classical Gram-Schmidt with one
+    re-orthogonalisation, everything on the context's stream.  Single rank.  `system`, b, x, minv and precond as in pcg -- the
+    operator need not be symmetric or definite: this is the Krylov solver for a system.CsrOperator that CG cannot serve.  Rows
+    with minv == 0 (or frozen by the preconditioner's minv) keep x; the reported tol is the true residual over the other rows.
+    `workspace`: a GmresWorkspace over the system's rows to reuse (its restart_length holds); None: one is created for this call
+    with min(restart_length, max_iters, n) basis vectors.  A 2-D b solves its columns one after the other on one workspace.
+    Returns a GmresSolveResult (a list of them for a 2-D b)."""
+    from . import capi
+    if precond is not None and minv is not None:
+        raise capi.L3KError("give minv or precond (which carries its own minv), not both")
+    if precond is not None and precond.system is not system:
+        raise capi.L3KError("the preconditioner was created for another system")
+    if int(restart_length) < 1:
+        raise capi.L3KError(f"restart_length = {restart_length} must be at least 1")
+    name = "gmres_solve" if precond is None else "gmres_solve_pmg" if isinstance(precond, PMultigrid) else "gmres_solve_cheb"
+    from .system import MultiTermSystem
+    if name == "gmres_solve_pmg" and isinstance(system, MultiTermSystem):
+        raise capi.L3KError("p-multigrid is not provided for a MultiTermSystem")
+    entry, n = _entry(system, name)
+    cols = [(b, x)] if b.dim() == 1 else list(zip(b, x))
+    if x.shape != b.shape or any(bc.stride(0) != 1 or xc.stride(0) != 1 or bc.numel() != n for bc, xc in cols):
+        raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")
+    if any(_overlap(bc, xc, n) for bc, xc in cols):
+        raise capi.L3KError("b and x must not share memory")
+    if minv is not None and (minv.numel() != n or not minv.is_contiguous()):
+        raise capi.L3KError("minv must be a contiguous tensor over the owned dofs of the system")
+    if workspace is not None and workspace.n != n:
+        raise capi.L3KError(f"the workspace was created for n = {workspace.n}, the system has {n} rows")
+    opts = capi.GmresOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every), int(max_restarts))
+    ctx = system.ctx if hasattr(system, "ctx") else system.mesh.ctx
+    ws = workspace if workspace is not None else GmresWorkspace(ctx, n, max(1, min(int(restart_length), int(max_iters), n)))
+    res_c = (capi.GmresResult * len(cols))()
+    try:
+        for (bc, xc), res in zip(cols, res_c):
+            capi.check(entry(ws._h, system._h, _vp(bc), _vp(xc), precond._h if precond is not None else _vp(minv), C.byref(opts),
+                             C.byref(res)))
+    finally:
+        if ws is not workspace:
+            ws.close()
+    out = _checked([GmresSolveResult(r.achieved_tol, r.iterations, bool(r.converged), r.restarts, bool(r.breakdown), r.estimate,
+                                     r.orth_loss) for r in res_c], throw_on_fail)
+    return out[0] if b.dim() == 1 else out
+
+
 def pcg_distributed(op, ctx, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="none", group=None,
                     throw_on_fail=True, allreduce=None, check_every=1, precond=None, native=False):
     """The same iteration for a partitioned system: `op.apply(X, Y)` is a DistributedOperator over this rank's owned

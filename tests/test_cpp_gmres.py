@@ -1,0 +1,31 @@
+"""l3k::Gmres, the C++ mirror of l3k_gmres_* (include/l3k/operator.hpp): compiles and links against l3k.h on CPU; on the GPU the
+program solves a non-symmetric tridiagonal system with GMRES(30) and checks the solution, the refusals and the exception."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "gmres_shim.cpp")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def build(out):
+    cmd = [HIPCC, "-std=c++20", "-O1", "--offload-arch=gfx950", f"-I{ROOT}/include", SRC, f"-L{ROOT}/l3ster_amd/lib", "-ll3k",
+           f"-Wl,-rpath,{ROOT}/l3ster_amd/lib", "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return out
+
+
+def test_cpp_gmres_compiles_and_links(tmp_path):
+    build(str(tmp_path / "gmres_shim"))
+
+
+@pytest.mark.gpu
+def test_cpp_gmres_runs(tmp_path):
+    exe = build(str(tmp_path / "gmres_shim"))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
