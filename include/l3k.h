@@ -1508,6 +1508,88 @@ int l3k_gmres_project(l3k_ctx* ctx, const double* d_V, size_t ld, int k, double*
                       double* d_h_out);
 int l3k_gmres_combine(l3k_ctx* ctx, const double* d_V, size_t ld, int k, const double* d_y, const double* d_minv, int64_t n, double* d_x);
 
+/* ---- triangular preconditioners on a CSR operator: symmetric Gauss-Seidel and ILU(0) ------------------------------------------
+ * What the reference reaches through Ifpack2 (solve/Ifpack2Preconditioners.hpp:97-101: Ifpack2SGSOpts, "relaxation: type" =
+ * "Symmetric Gauss-Seidel"; :134-157: Ifpack2IluKOpts with level of fill 0 by default), which its solver test runs under CG and
+ * GMRES (tests/SolverTests.cpp:221-232).  Ifpack2 is not part of the reference tree; the arithmetic is the textbook one, stated
+ * below and restated in numpy by tests/tri_ref.py.  Single rank, one column.
+ *
+ * Symbolic phase (host, once, in l3k_tri_create): the ACTIVE rows are the rows that store an entry, the rule of l3k_csr_diag and
+ * l3k_chol.  Empty rows are frozen: apply writes z = 0 there and a solve keeps x bit for bit; stored entries in the column of an
+ * empty row lie outside the active principal block, and the factorisation and the solves ignore them.  Every active row must store
+ * its diagonal entry.  level(i) = 1 + max level(j) over the stored active j < i of row i (1 without one); for the upper solve the
+ * mirror image over j > i with the rows walked downwards.  The rows are listed level by level, ascending within a level.
+ * Launch plan: consecutive levels of at most fuse_rows rows each form ONE launch in which one workgroup walks the levels with a
+ * barrier between them, at most 4096 levels per launch; every wider level is one launch of a grid.  All are ordinary launches on
+ * the context's stream.  The arithmetic of a row does not depend on the plan: equal bits for every fuse_rows, on any context.
+ *
+ * ILU(0), row-wise IKJ in A's pattern: for row i, for every stored active k < i in ascending order: l_ik = a_ik / u_kk; for every
+ * stored j > k of row k that row i also stores: a_ij -= l_ik u_kj.  L is strictly lower with a unit diagonal implied, U carries its
+ * diagonal.  Before the factorisation a_ii <- sign(a_ii) * absolute_threshold + relative_threshold * a_ii (Ifpack2's "fact:
+ * absolute threshold" / "fact: relative threshold").  z = M^-1 r:  L y = r, then U z = y.
+ * SGS with damping omega is SSOR, M = (D / omega + L) (omega / (2 - omega)) D^-1 (D / omega + U) with D, L, U the diagonal and the
+ * strict triangles of A (omega = 1: (D + L) D^-1 (D + U)); one sweep from a zero start (Ifpack2's "relaxation: sweeps" = 1,
+ * "relaxation: damping factor" = omega).  z = M^-1 r:  (D / omega + L) y = r, then (D / omega + U) z = ((2 - omega) / omega) D y:
+ * the diagonal scaling is folded into the upper solve, which is what l3k_tri_solve_upper computes for this kind.
+ * A row's sum runs over its entries on the wanted side in entry order per lane (lane l of the operator's lanes_per_row takes the
+ * entries l, l + L, ...), combined by the fixed butterfly of the CSR apply; no floating-point atomics, no kernel waits for another
+ * workgroup: results are bitwise reproducible.
+ *
+ * l3k_tri_opts: NULL stands for {L3K_TRI_SGS, 1, 0, 1, 0}; fuse_rows = 0 is the library's choice, 256 / lanes_per_row.
+ * l3k_tri_create: symbolic only; A must outlive the object, its graph must not change, its values may.  One readback of the graph:
+ *   synchronises.  -1 with a message: a null argument, an unknown kind, a damping outside (0, 2), a negative fuse_rows, an active
+ *   row without a stored diagonal entry (the message names the first).
+ * l3k_tri_factor: numeric; the call a time loop repeats after it has assembled again.  SGS: reads A's current diagonal and stores
+ *   omega / a_ii; the solves read A's values live, nothing is copied.  ILU0: copies A's current values, applies the thresholds and
+ *   factors in place.  A pivot (SGS: a diagonal entry) that is zero or not finite is replaced by 1 and counted, nothing faults and
+ *   no NaN or Inf is made of it; one readback at the end (synchronises) returns -2 with n_bad_pivots and first_bad_row in the info.
+ * l3k_tri_apply: z <- M^-1 r on the active rows, 0 on the others; the same bits as solve_upper(solve_lower(r)).
+ * l3k_tri_solve_lower / _upper: the two pieces.  In all three the input and the output must not overlap (-1), and all three and
+ *   both solver entries return -1 unless the last l3k_tri_factor succeeded.
+ * l3k_tri_values: ILU0 only (-1 on SGS): the nnz factor values in A's pattern -- l_ik below the diagonal, u_ij on and above it,
+ *   A's values in the columns of empty rows.
+ * l3k_tri_levels (host only, no context, host arrays): level_out [n]: the level of every row as above, 0 on an empty row;
+ *   upper != 0: for the upper solve.  Validates the graph as l3k_csr_create does.
+ * l3k_csr_pcg_solve_tri / l3k_csr_gmres_solve_tri: the loops of l3k_csr_pcg_solve_cheb / l3k_csr_gmres_solve_cheb with this
+ *   preconditioner; the frozen rows are the empty ones.  -1: a tri made on another operator than A.  An l3k_csr_dist has none. */
+typedef struct l3k_tri l3k_tri;
+enum
+{
+    L3K_TRI_SGS  = 0,
+    L3K_TRI_ILU0 = 1
+};
+typedef struct
+{
+    int    kind;
+    double damping;            /* SGS: omega, 0 < omega < 2; 1 = plain symmetric Gauss-Seidel                          */
+    double absolute_threshold; /* ILU0: a_ii <- sign(a_ii) * absolute_threshold + relative_threshold * a_ii before the */
+    double relative_threshold; /*       factorisation; 0 and 1 change nothing                                          */
+    int    fuse_rows;          /* launch plan; 0 = the library's choice                                                */
+} l3k_tri_opts;
+typedef struct
+{
+    int64_t n, n_active, nnz;
+    int     kind, lanes_per_row;
+    int64_t n_levels_lower, n_levels_upper, max_level_rows;
+    int64_t n_launches_lower, n_launches_upper; /* of one solve each way, after fusing                               */
+    size_t  bytes;                              /* device memory of the object                                       */
+    int64_t n_bad_pivots, first_bad_row;        /* of the last l3k_tri_factor; first_bad_row = -1 if there was none  */
+    int     factored;                           /* the last l3k_tri_factor succeeded                                 */
+} l3k_tri_info;
+/* solve/Ifpack2Preconditioners.hpp:97-101,134-157, tests/SolverTests.cpp:221-232 (all entries of this section) */
+int l3k_tri_create(l3k_csr* A, const l3k_tri_opts* opts, l3k_tri** out);
+int l3k_tri_factor(l3k_tri* T);
+int l3k_tri_apply(l3k_tri* T, const double* d_r, double* d_z);
+int l3k_tri_solve_lower(l3k_tri* T, const double* d_r, double* d_y);
+int l3k_tri_solve_upper(l3k_tri* T, const double* d_y, double* d_z);
+int l3k_tri_values(const l3k_tri* T, double* d_out);
+int l3k_tri_info_get(const l3k_tri* T, l3k_tri_info* out);
+int l3k_tri_destroy(l3k_tri* T);
+int l3k_tri_levels(int64_t n, const int64_t* row_ptr, const int32_t* col_ind, int upper, int32_t* level_out, int64_t* n_levels);
+int l3k_csr_pcg_solve_tri(l3k_csr* A, const double* d_b, double* d_x, l3k_tri* T, const l3k_cg_opts* opts, l3k_cg_result* result);
+int l3k_csr_gmres_solve_tri(l3k_gmres* G, l3k_csr* A, const double* d_b, double* d_x, l3k_tri* T, const l3k_gmres_opts* opts,
+                            l3k_gmres_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -710,6 +710,7 @@ private:
 //   diag             ~ getLocalDiagCopy + NativeJacobiImpl::init          solve/NativePreconditioners.hpp:75-96
 //   applyDirichlet   ~ DirichletBCAlgebraic::apply                        bcs/DirichletBC.hpp:82-150
 //   solve            ~ alg_sys.solve(CG{opts, NativeJacobiOpts{}}) on the assembled matrix
+class TriangularPreconditioner;
 class CsrOperator
 {
 public:
@@ -765,6 +766,9 @@ public:
                 throw std::runtime_error{"Solver failed to converge"};
         return res;
     }
+    // alg_sys.solve(CG{opts, Ifpack2SGSOpts{}}) / Ifpack2IluKOpts: PCG with a factored TriangularPreconditioner of this operator
+    // (defined below it); the rows that store nothing keep x; throws if not converged
+    l3k_cg_result solve(const double* d_b, double* d_x, const TriangularPreconditioner& precond, l3k_cg_opts opts = {1e-6, 10000, 0, 1}) const;
     // the rank-local Dirichlet step with the owner rule on the local matrix of a partitioned system (l3k_csr_dirichlet_dist): mask,
     // values and rhs over the LOCAL dofs [owned | ghost], ghost values imported by the caller; a flagged owned row becomes the
     // identity row with rhs = g, a flagged ghost row an all-zero row with rhs = 0
@@ -888,6 +892,52 @@ private:
     l3k_chol* m_chol{};
 };
 
+// Symmetric Gauss-Seidel or ILU(0) on a single-rank CSR operator (l3k_tri_*), where the reference uses Ifpack2 (Ifpack2SGSOpts,
+// Ifpack2IluKOpts with level of fill 0: solve/Ifpack2Preconditioners.hpp:97-101,134-157; tests/SolverTests.cpp:221-232): level-scheduled
+// sparse triangular solves in the operator's pattern.  The constructor runs the symbolic phase (host) and throws on an active row
+// without a stored diagonal entry; opts as l3k_tri_opts (kind L3K_TRI_SGS or L3K_TRI_ILU0, damping, the two thresholds, fuse_rows).
+// The operator (a CsrOperator, or the l3k_csr of a closed AssembledSystem) must outlive the object.  RAII, move-only.
+//   factor       ~ compute() on the operator's current values; throws on a zero or non-finite pivot (see info)
+//   apply        ~ z <- M^-1 r; r and z distinct; 0 on the rows that store nothing
+//   solveLower, solveUpper ~ the two halves of apply
+//   values       ~ ILU(0): the nnz factor values in the operator's pattern
+//   info         ~ levels, launches, bytes, n_bad_pivots, first_bad_row, factored
+// CsrOperator::solve and Gmres::solve take the factored object as the preconditioner.
+class TriangularPreconditioner
+{
+public:
+    static constexpr l3k_tri_opts sgs{L3K_TRI_SGS, 1., 0., 1., 0}, ilu0{L3K_TRI_ILU0, 1., 0., 1., 0};
+    explicit TriangularPreconditioner(l3k_csr* A, const l3k_tri_opts& opts = ilu0) { check(l3k_tri_create(A, &opts, &m_tri)); }
+    explicit TriangularPreconditioner(const CsrOperator& A, const l3k_tri_opts& opts = ilu0) : TriangularPreconditioner{A.get(), opts} {}
+    TriangularPreconditioner(const TriangularPreconditioner&)            = delete;
+    TriangularPreconditioner& operator=(const TriangularPreconditioner&) = delete;
+    TriangularPreconditioner(TriangularPreconditioner&& o) noexcept : m_tri{o.m_tri} { o.m_tri = nullptr; }
+    ~TriangularPreconditioner() { l3k_tri_destroy(m_tri); }
+    void factor() { check(l3k_tri_factor(m_tri)); }
+    void apply(const double* d_r, double* d_z) const { check(l3k_tri_apply(m_tri, d_r, d_z)); }
+    void solveLower(const double* d_r, double* d_y) const { check(l3k_tri_solve_lower(m_tri, d_r, d_y)); }
+    void solveUpper(const double* d_y, double* d_z) const { check(l3k_tri_solve_upper(m_tri, d_y, d_z)); }
+    void values(double* d_out) const { check(l3k_tri_values(m_tri, d_out)); }
+    l3k_tri_info info() const
+    {
+        l3k_tri_info i{};
+        check(l3k_tri_info_get(m_tri, &i));
+        return i;
+    }
+    l3k_tri* get() const { return m_tri; }
+
+private:
+    l3k_tri* m_tri{};
+};
+inline l3k_cg_result CsrOperator::solve(const double* d_b, double* d_x, const TriangularPreconditioner& precond, l3k_cg_opts opts) const
+{
+    l3k_cg_result res{};
+    check(l3k_csr_pcg_solve_tri(m_csr, d_b, d_x, precond.get(), &opts, &res));
+    if (!res.converged)
+        throw std::runtime_error{"Solver failed to converge"};
+    return res;
+}
+
 // Restarted GMRES(restart_length) on a single-rank operator (l3k_gmres_*): alg_sys.solve(Gmres{opts, precond}), the reference's
 // second Krylov solver (solve/BelosSolvers.hpp:124-130, restart_length = 250 and max_restarts = 39 of solve/SolverInterface.hpp:26-37),
 // for systems that are not symmetric positive definite.  The object is the workspace on n rows (restart_length above n is lowered
@@ -942,6 +992,13 @@ public:
     {
         l3k_gmres_result res{};
         check(l3k_csr_gmres_solve_cheb(m_gmres, A.get(), d_b, d_x, cheb.get(), &opts, &res));
+        return converged(res);
+    }
+    l3k_gmres_result solve(const CsrOperator& A, const double* d_b, double* d_x, const TriangularPreconditioner& precond,
+                           l3k_gmres_opts opts = default_opts) const
+    {
+        l3k_gmres_result res{};
+        check(l3k_csr_gmres_solve_tri(m_gmres, A.get(), d_b, d_x, precond.get(), &opts, &res));
         return converged(res);
     }
     l3k_gmres_info info() const

@@ -93,6 +93,20 @@ class CholInfo(C.Structure):
                 ("n_bad_pivots", C.c_int64), ("first_bad_row", C.c_int64), ("factored", C.c_int)]
 
 
+class TriOpts(C.Structure):
+    """l3k_tri_opts (Ifpack2SGSOpts / Ifpack2IluKOpts, solve/Ifpack2Preconditioners.hpp:97-101,134-157): kind 0 = SGS, 1 = ILU(0)"""
+    _fields_ = [("kind", C.c_int), ("damping", C.c_double), ("absolute_threshold", C.c_double), ("relative_threshold", C.c_double),
+                ("fuse_rows", C.c_int)]
+
+
+class TriInfo(C.Structure):
+    """l3k_tri_info: sizes of the symbolic phase, the launch plan and the outcome of the last l3k_tri_factor"""
+    _fields_ = [("n", C.c_int64), ("n_active", C.c_int64), ("nnz", C.c_int64), ("kind", C.c_int), ("lanes_per_row", C.c_int),
+                ("n_levels_lower", C.c_int64), ("n_levels_upper", C.c_int64), ("max_level_rows", C.c_int64),
+                ("n_launches_lower", C.c_int64), ("n_launches_upper", C.c_int64), ("bytes", C.c_size_t),
+                ("n_bad_pivots", C.c_int64), ("first_bad_row", C.c_int64), ("factored", C.c_int)]
+
+
 class GraphInfo(C.Structure):
     """l3k_graph_info: the statistics of the one readback of l3k_graph_create"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("n_empty_rows", C.c_int64), ("max_row_len", C.c_int64),
@@ -423,6 +437,17 @@ SIGNATURES = {
     "l3k_gmres_multi_dot": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "l3k_gmres_project": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp, _vp]),
     "l3k_gmres_combine": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),
+    "l3k_tri_create": (C.c_int, [_vp, C.POINTER(TriOpts), C.POINTER(_vp)]),
+    "l3k_tri_factor": (C.c_int, [_vp]),
+    "l3k_tri_apply": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_tri_solve_lower": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_tri_solve_upper": (C.c_int, [_vp, _vp, _vp]),
+    "l3k_tri_values": (C.c_int, [_vp, _vp]),
+    "l3k_tri_info_get": (C.c_int, [_vp, C.POINTER(TriInfo)]),
+    "l3k_tri_destroy": (C.c_int, [_vp]),
+    "l3k_tri_levels": (C.c_int, [C.c_int64, c_int64_p, c_int32_p, C.c_int, c_int32_p, c_int64_p]),
+    "l3k_csr_pcg_solve_tri": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(CgOpts), C.POINTER(CgResult)]),
+    "l3k_csr_gmres_solve_tri": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(GmresOpts), C.POINTER(GmresResult)]),
 }
 
 _lib = None

@@ -409,6 +409,16 @@ int l3k_csr_gmres_solve_cheb(l3k_gmres* G, l3k_csr* A, const double* d_b, double
     const Precond P = l3k::solver::chebPrecond(c);
     return gmresSolve(G, l3k::solver::csrOp(A), "l3k_csr_gmres_solve_cheb", d_b, d_x, nullptr, &P, opts, result);
 }
+int l3k_csr_gmres_solve_tri(l3k_gmres* G, l3k_csr* A, const double* d_b, double* d_x, l3k_tri* T, const l3k_gmres_opts* opts,
+                            l3k_gmres_result* result)
+{
+    if (int rc = csrCheck("l3k_csr_gmres_solve_tri", G, A, d_b, d_x, T, true, result))
+        return rc;
+    if (int rc = l3k::solver::triReady(T, "l3k_csr_gmres_solve_tri"))
+        return rc;
+    const Precond P = l3k::solver::triPrecond(T);
+    return gmresSolve(G, l3k::solver::csrOp(A), "l3k_csr_gmres_solve_tri", d_b, d_x, nullptr, &P, opts, result);
+}
 int l3k_mfs_gmres_solve(l3k_gmres* G, l3k_mfs* S, const double* d_b, double* d_x, const double* d_minv, const l3k_gmres_opts* opts,
                         l3k_gmres_result* result)
 {

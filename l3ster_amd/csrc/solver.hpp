@@ -57,6 +57,10 @@ LinOp   csrOp(l3k_csr* A);
 Precond chebPrecond(l3k_cheb* c);
 Precond pmgPrecond(l3k_pmg* M);
 int     mfsSolvable(const l3k_mfs* S, const char* message, const char* who);
+// the triangular preconditioner (api_tri.hip) as a Precond value: the mask is the object's own, 1 on the rows that store an entry;
+// triReady: -1 with a message from `who` unless the object's last l3k_tri_factor succeeded
+Precond triPrecond(l3k_tri* T);
+int     triReady(const l3k_tri* T, const char* who);
 // s[slot] <- <u, v> in the fixed order of the PCG's reductions
 int dotInto(l3k_ctx* ctx, const double* d_u, const double* d_v, int64_t n, double* d_s, int slot);
 } // namespace l3k::solver

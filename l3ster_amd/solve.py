@@ -407,8 +407,9 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
     context's stream, the host only reads 32 bytes per convergence check.  Single rank; `system` is a
     l3ster_amd.system.MatrixFreeSystem or a system.CsrOperator (an assembled or condensed matrix: l3k_csr_pcg_solve, the
     same iteration on the CSR apply), b / x / minv 1-D device tensors over its owned dofs (the operator's rows).  `precond`: a
-    ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb, or a PMultigrid whose finest
-    level is this MatrixFreeSystem (one V-cycle per iteration; rows frozen by its finest smoother keep x) -> l3k_pcg_solve_pmg;
+    ChebyshevPreconditioner of this system (it carries its own minv) -> l3k_pcg_solve_cheb, a PMultigrid whose finest
+    level is this MatrixFreeSystem (one V-cycle per iteration; rows frozen by its finest smoother keep x) -> l3k_pcg_solve_pmg,
+    or a factored TriangularPreconditioner of this CsrOperator (SGS or ILU(0); its empty rows keep x) -> l3k_csr_pcg_solve_tri;
     a multivector b then solves its columns one after the other, as l3k_pcg_solve_cols does."""
     from . import capi
     opts = capi.CgOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every))
@@ -417,7 +418,8 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
             raise capi.L3KError("give minv or precond (which carries its own minv), not both")
         if precond.system is not system:
             raise capi.L3KError("the preconditioner was created for another system")
-        solve_cheb, n = _entry(system, "pcg_solve_pmg" if isinstance(precond, PMultigrid) else "pcg_solve_cheb")
+        solve_cheb, n = _entry(system, "pcg_solve_pmg" if isinstance(precond, PMultigrid) else
+                               "pcg_solve_tri" if isinstance(precond, TriangularPreconditioner) else "pcg_solve_cheb")
         cols = [(b, x)] if b.dim() == 1 else list(zip(b, x))
         if x.shape != b.shape or any(bc.stride(0) != 1 or xc.stride(0) != 1 or bc.numel() != n for bc, xc in cols):
             raise capi.L3KError("b and x must be tensors of one shape over the owned dofs with unit stride along rows")
@@ -510,7 +512,8 @@ def gmres(system, b, x, minv=None, precond=None, tol=1e-6, max_iters=10_000, res
         raise capi.L3KError("the preconditioner was created for another system")
     if int(restart_length) < 1:
         raise capi.L3KError(f"restart_length = {restart_length} must be at least 1")
-    name = "gmres_solve" if precond is None else "gmres_solve_pmg" if isinstance(precond, PMultigrid) else "gmres_solve_cheb"
+    name = ("gmres_solve" if precond is None else "gmres_solve_pmg" if isinstance(precond, PMultigrid) else
+            "gmres_solve_tri" if isinstance(precond, TriangularPreconditioner) else "gmres_solve_cheb")
     from .system import MultiTermSystem
     if name == "gmres_solve_pmg" and isinstance(system, MultiTermSystem):
         raise capi.L3KError("p-multigrid is not provided for a MultiTermSystem")
@@ -854,6 +857,92 @@ class CholeskySolver:
         if getattr(self, "_h", None):
             from . import capi
             capi.load().l3k_chol_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+
+class TriangularPreconditioner:
+    """Handle of l3k_tri_create: symmetric Gauss-Seidel (kind="sgs") or ILU(0) (kind="ilu0") on a single-rank system.CsrOperator,
+    where the reference uses Ifpack2 (Ifpack2SGSOpts / Ifpack2IluKOpts, solve/Ifpack2Preconditioners.hpp:97-101,134-157).  Both are
+    level-scheduled sparse triangular solves in A's pattern; `damping` is the SSOR factor of SGS, the two thresholds modify the
+    diagonal before ILU(0) factors, fuse_rows = 0 leaves the launch plan to the library (include/l3k.h).  Creation is symbolic
+    only; factor() reads A's current values: a time loop assembles again and calls it again.  Rows of A that store nothing are
+    frozen: apply writes 0 there and a solve keeps x.  Pass the factored object as precond= to solve.pcg / solve.gmres.  Results
+    are bitwise reproducible.  A is kept alive here."""
+
+    KINDS = {"sgs": 0, "ilu0": 1}
+
+    def __init__(self, A, kind="ilu0", damping=1.0, absolute_threshold=0.0, relative_threshold=1.0, fuse_rows=0):
+        from . import capi
+        from .system import CsrOperator, DistributedCsrOperator
+        if isinstance(A, DistributedCsrOperator):
+            raise capi.L3KError("TriangularPreconditioner: a DistributedCsrOperator is refused: the triangular solves work on the "
+                                "matrix of one rank")
+        if not isinstance(A, CsrOperator):
+            raise capi.L3KError("TriangularPreconditioner takes a system.CsrOperator (AssembledSystem.end() returns one)")
+        if kind not in self.KINDS:
+            raise capi.L3KError(f"TriangularPreconditioner: kind = {kind!r}; it is 'sgs' or 'ilu0'")
+        self.system, self.n, self.kind = A, A.n, kind
+        self._h = C.c_void_p()
+        opts = capi.TriOpts(self.KINDS[kind], float(damping), float(absolute_threshold), float(relative_threshold), int(fuse_rows))
+        capi.check(capi.load().l3k_tri_create(A._h, C.byref(opts), C.byref(self._h)))
+
+    @property
+    def info(self):
+        """n, n_active, nnz, kind, lanes_per_row, n_levels_lower, n_levels_upper, max_level_rows, n_launches_lower,
+        n_launches_upper, bytes, n_bad_pivots, first_bad_row, factored (l3k_tri_info)"""
+        import types
+        from . import capi
+        i = capi.TriInfo()
+        capi.check(capi.load().l3k_tri_info_get(self._h, C.byref(i)))
+        return types.SimpleNamespace(**{name: getattr(i, name) for name, _ in capi.TriInfo._fields_})
+
+    def factor(self):
+        """The numeric phase on A's current values (l3k_tri_factor); raises with the number of zero or non-finite pivots and the
+        first one's row, which .info keeps"""
+        from . import capi
+        capi.check(capi.load().l3k_tri_factor(self._h))
+        return self
+
+    def _call(self, fn, u, v):
+        from . import capi
+        n = self.n
+        if u.numel() != n or v.numel() != n or not (u.is_contiguous() and v.is_contiguous()) or u.dtype != torch.float64 or v.dtype != torch.float64:
+            raise capi.L3KError("the vectors must be contiguous float64 tensors over the rows of the operator")
+        capi.check(fn(self._h, C.c_void_p(u.data_ptr()), C.c_void_p(v.data_ptr())))
+        return v
+
+    def apply(self, r, z):
+        """z <- M^-1 r (l3k_tri_apply); r, z: distinct 1-D device tensors over the rows"""
+        from . import capi
+        return self._call(capi.load().l3k_tri_apply, r, z)
+
+    def solve_lower(self, r, y):
+        """the first half of apply (l3k_tri_solve_lower)"""
+        from . import capi
+        return self._call(capi.load().l3k_tri_solve_lower, r, y)
+
+    def solve_upper(self, y, z):
+        """the second half of apply, for SGS with the diagonal scaling in front (l3k_tri_solve_upper)"""
+        from . import capi
+        return self._call(capi.load().l3k_tri_solve_upper, y, z)
+
+    def values(self):
+        """ILU(0): the factor in A's pattern, a new device tensor of nnz doubles (l3k_tri_values)"""
+        from . import capi
+        out = torch.empty_like(self.system.values)
+        capi.check(capi.load().l3k_tri_values(self._h, C.c_void_p(out.data_ptr())))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            from . import capi
+            capi.load().l3k_tri_destroy(self._h)
             self._h = None
 
     def __del__(self):
