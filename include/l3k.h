@@ -1057,6 +1057,19 @@ int     l3k_halo_export_add(l3k_halo* halo, const double* d_ghost, size_t ldg, i
  * messages of at most 64 bytes per rank: O(world^2) in all, meant for the ranks of one node.  -1, d_vals untouched: a null
  * argument, count outside [1, 8]. */
 int     l3k_halo_allreduce_sum(l3k_halo* halo, double* d_vals, int count);
+/* The same reduction at any width: what a step of the collective GMRES needs (k + 1 dot products per pass).
+ * l3k_halo_reduce_reserve: LOCAL.  Sets the capacity -- the largest count, and the row stride of a [world][capacity] device block
+ *   of its own (no memory in a world of one), 1 <= capacity <= 65536.  The same capacity again does nothing; another one waits for
+ *   the reductions queued so far and reallocates.  -1: a null halo, a capacity outside the range, or another capacity than the
+ *   present one while a collective solve is writing into the block.  The ranks need not reserve the same capacity.
+ * l3k_halo_allreduce_sum_n: d_vals[0 .. count) <- the sum over ALL ranks, 1 <= count <= capacity, in place, with the scheme, the
+ *   rank order of the additions, the equal bits on every rank and the ordering of l3k_halo_allreduce_sum: one group of
+ *   2 (world - 1) messages of count doubles, then a kernel with one thread per value (ceil(count / 256) workgroups) that adds its
+ *   column down the ranks.  Consecutive reductions of either kind need no host synchronisation between them.  world == 1: nothing
+ *   is enqueued, the values stay.  -1, d_vals untouched, no peer involved: a null argument, no capacity reserved, count < 1 or
+ *   count > capacity.  The message count is still O(world^2). */
+int     l3k_halo_reduce_reserve(l3k_halo* halo, int capacity);
+int     l3k_halo_allreduce_sum_n(l3k_halo* halo, double* d_vals, int count);
 /* HIP events around the three element launches (first interior half, border elements, second interior half) of the next
  * n_applies calls of l3k_mf_apply_dist, on the stream they run on; _get waits for that apply and returns the durations. */
 int     l3k_halo_timing_begin(l3k_halo* halo, int n_applies);
@@ -1453,7 +1466,7 @@ int l3k_vtk_vtu_header_text(int64_t n_points, int64_t n_cells, const uint64_t* e
  * l3k_chol_create does.  One workspace serves any number of solves of its n, one at a time.
  * opts == NULL: {1e-6, 10000, 0, 1, 39}.  -1 with a message naming the call: a null argument; a workspace whose n is not the
  * operator's number of rows; restart_length < 1, or min(restart_length, n) above 2046; b and x overlapping; an l3k_mf with ghost nodes or an l3k_mfs that is not
- * finalized or has ghost nodes (single rank only: there is no collective GMRES); a cheb or pmg made for another system; in the
+ * finalized or has ghost nodes (these entry points are single rank: the collective ones are below the pieces); a cheb or pmg made for another system; in the
  * pieces k < 1 or an ld that is not a multiple of 4. */
 typedef struct l3k_gmres l3k_gmres;
 typedef struct
@@ -1507,6 +1520,39 @@ int l3k_gmres_multi_dot(l3k_ctx* ctx, const double* d_V, size_t ld, int k, const
 int l3k_gmres_project(l3k_ctx* ctx, const double* d_V, size_t ld, int k, double* d_w, const double* d_mask, int64_t n, const double* d_h_in,
                       double* d_h_out);
 int l3k_gmres_combine(l3k_ctx* ctx, const double* d_V, size_t ld, int k, const double* d_y, const double* d_minv, int64_t n, double* d_x);
+/* The collective GMRES of a partitioned system: what alg_sys.solve(Gmres{...}) is on every MPI rank of a run of the reference
+ * (solve/BelosSolvers.hpp:116-131).  The loop is the one above -- the same code -- run with the partitioned applies
+ * (l3k_mf_apply_dist, l3k_csr_dist_apply) and with ONE l3k_halo_allreduce_sum_n wherever a reducing pass has landed:
+ *   <b, b>                            1 value, once (residual_scaling 2)
+ *   <r, r>                            1 value, at the head of every cycle
+ *   h1 = V^T w, <w, w>                k + 2 values   (the multiDot pass of step k)
+ *   h2 = V^T w, <w, w>                k + 2 values   (the first projectRedot pass)
+ *   t  = V^T w, nu^2 = <w, w>         k + 2 values   (the second one)
+ * so a step has three reductions and a cycle one more.  Each pass writes this rank's sums over its OWNED rows straight into its row
+ * of the halo's reduction block, and the sum over the ranks lands where the single-rank pass writes; the Hessenberg column, the
+ * rotations, g, nu, the breakdown test, the triangular solve and the 64 bytes the host reads are computed from reduced values
+ * alone.  These are bit-identical on all ranks, so the replicated small arrays stay identical without further messages and every
+ * rank takes the same decision on convergence, breakdown, the valid columns and the restart, and returns the same result.  In a
+ * world of one nothing is enqueued and the solve is the single-rank one bit for bit.
+ * Vectors hold the OWNED rows.  The workspace is one of n = the owned rows; EVERY RANK'S WORKSPACE MUST HAVE THE SAME
+ * restart_length, and l3k_gmres_create lowers it to n: l3k_gmres_create_dist does not (n is one rank's share) and takes n == 0, the
+ * workspace of a rank that owns nothing -- it brings null vectors and takes part in every reduction.  Frozen rows, options,
+ * residual scalings, check_every and the result are those of l3k_gmres_solve; every rank passes the same options.  cheb: NULL --
+ * Jacobi d_minv, or no preconditioner when d_minv is NULL too -- or an object of l3k_cheb_create_dist / l3k_csr_dist_cheb_create on
+ * this very operator and halo (d_minv then NULL or the array it was created on).  Both calls reserve restart_length + 1 doubles on
+ * the halo (l3k_halo_reduce_reserve) unless it has that capacity already, and hold the block until they return.
+ * COLLECTIVE.  Every refusal (-1) comes before the first collective call: a null argument, a workspace of another context or of
+ * another n than the owned rows, a halo on another context than the system or not matching its mesh, a cheb made by a single-rank
+ * creator or on another operator or halo, a d_minv that is not the cheb's, b and x overlapping.  A rank that returns early from a
+ * collective call for any other reason -- a launch or transport error (-3) -- leaves its peers waiting in the next exchange, as in
+ * the collective PCG.  Not provided: l3k_pmg, l3k_tri and l3k_mfs on a partitioned system, several columns. */
+int l3k_gmres_create_dist(l3k_ctx* ctx, int64_t n_owned, int restart_length, size_t max_bytes, l3k_gmres** out);
+int l3k_gmres_solve_dist(l3k_gmres* G, l3k_mf* mf, l3k_halo* halo, const double* d_b, double* d_x, const double* d_minv,
+                         l3k_cheb* cheb /* NULL: Jacobi, or none when d_minv is NULL too */, const l3k_gmres_opts* opts,
+                         l3k_gmres_result* result);
+int l3k_csr_dist_gmres_solve(l3k_gmres* G, l3k_csr_dist* D, const double* d_b, double* d_x, const double* d_minv,
+                             l3k_cheb* cheb /* NULL: Jacobi, or none when d_minv is NULL too */, const l3k_gmres_opts* opts,
+                             l3k_gmres_result* result);
 
 /* ---- triangular preconditioners on a CSR operator: symmetric Gauss-Seidel and ILU(0) ------------------------------------------
  * What the reference reaches through Ifpack2 (solve/Ifpack2Preconditioners.hpp:97-101: Ifpack2SGSOpts, "relaxation: type" =

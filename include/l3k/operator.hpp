@@ -268,6 +268,9 @@ public:
     }
     // sum of d_vals[0 .. count), count <= 8, over all ranks in ascending rank order, in place: the same bits on every rank
     void allreduceSum(double* d_vals, int count) const { check(l3k_halo_allreduce_sum(m_halo, d_vals, count)); }
+    // the same sum for 1 <= count <= capacity values, behind reduceReserve(capacity) (local; the collective GMRES reserves its own)
+    void reduceReserve(int capacity) const { check(l3k_halo_reduce_reserve(m_halo, capacity)); }
+    void allreduceSumN(double* d_vals, int count) const { check(l3k_halo_allreduce_sum_n(m_halo, d_vals, count)); }
     l3k_halo* get() const { return m_halo; }
 
 private:
@@ -452,6 +455,7 @@ private:
     l3k_cheb* m_cheb{};
 };
 
+class Gmres;
 class MatrixFreeSystem
 {
 public:
@@ -557,6 +561,12 @@ public:
             throw std::runtime_error{"Solver failed to converge"};
         return res;
     }
+    // alg_sys.solve(Gmres{...}) on every rank of an MPI run (solve/BelosSolvers.hpp:124-131): the collective GMRES over the owned rows
+    // with the workspace Gmres::collective(ctx, n_owned, restart_length), the same restart_length on every rank (defined below
+    // Gmres).  cheb == nullptr: Jacobi with d_minv, or no preconditioner when d_minv is nullptr too; else the preconditioner of
+    // chebyshev(halo, ...).  Every rank returns the same result; throws if not converged
+    l3k_gmres_result gmresSolve(const Gmres& workspace, const Halo& halo, const double* d_b, double* d_x, const double* d_minv,
+                                l3k_gmres_opts opts = {1e-6, 10000, 0, 1, 39}, const Chebyshev* cheb = nullptr) const;
     // collective; lambda_max == 0: estimated by the power method on D^-1 A across the ranks
     Chebyshev chebyshev(const Halo& halo, const double* d_minv, l3k_cheb_opts opts = {1, 30., 10, 1.1, 0.}) const
     {
@@ -839,6 +849,12 @@ public:
             throw std::runtime_error{"Solver failed to converge"};
         return res;
     }
+    // alg_sys.solve(Gmres{...}) on every rank (solve/BelosSolvers.hpp:124-131): the collective GMRES over the owned rows with the
+    // workspace Gmres::collective(ctx, n_owned, restart_length), the reductions through the operator's halo (defined below Gmres).
+    // cheb == nullptr: Jacobi with d_minv, or no preconditioner when d_minv is nullptr too.  Every rank returns the same result;
+    // throws if not converged
+    l3k_gmres_result gmresSolve(const Gmres& workspace, const double* d_b, double* d_x, const double* d_minv,
+                                l3k_gmres_opts opts = {1e-6, 10000, 0, 1, 39}, const Chebyshev* cheb = nullptr) const;
     // collective; lambda_max == 0: estimated by the power method on D^-1 A across the ranks
     Chebyshev chebyshev(const double* d_minv, l3k_cheb_opts opts = {1, 30., 10, 1.1, 0.}) const
     {
@@ -954,6 +970,14 @@ public:
     {
         check(l3k_gmres_create(ctx.get(), n, restart_length, max_bytes, &m_gmres));
     }
+    // the workspace of one rank of a collective solve (MatrixFreeSystem::gmresSolve(halo, ...), DistributedCsr::gmresSolve): n_owned
+    // may be 0 and does not lower restart_length, which every rank gives alike (l3k_gmres_create_dist)
+    static Gmres collective(Context& ctx, int64_t n_owned, int restart_length = 250, size_t max_bytes = 0)
+    {
+        l3k_gmres* g = nullptr;
+        check(l3k_gmres_create_dist(ctx.get(), n_owned, restart_length, max_bytes, &g));
+        return Gmres{g};
+    }
     Gmres(const Gmres&)            = delete;
     Gmres& operator=(const Gmres&) = delete;
     Gmres(Gmres&& o) noexcept : m_gmres{o.m_gmres} { o.m_gmres = nullptr; }
@@ -1009,15 +1033,31 @@ public:
     }
     l3k_gmres* get() const { return m_gmres; }
 
-private:
     static l3k_gmres_result converged(const l3k_gmres_result& res)
     {
         if (!res.converged)
             throw std::runtime_error{"Solver failed to converge"}; // solve/BelosSolvers.hpp:103
         return res;
     }
+
+private:
+    explicit Gmres(l3k_gmres* handle) : m_gmres{handle} {}
     l3k_gmres* m_gmres{};
 };
+inline l3k_gmres_result MatrixFreeSystem::gmresSolve(const Gmres& workspace, const Halo& halo, const double* d_b, double* d_x,
+                                                     const double* d_minv, l3k_gmres_opts opts, const Chebyshev* cheb) const
+{
+    l3k_gmres_result res{};
+    check(l3k_gmres_solve_dist(workspace.get(), m_mf, halo.get(), d_b, d_x, d_minv, cheb ? cheb->get() : nullptr, &opts, &res));
+    return Gmres::converged(res);
+}
+inline l3k_gmres_result DistributedCsr::gmresSolve(const Gmres& workspace, const double* d_b, double* d_x, const double* d_minv,
+                                                   l3k_gmres_opts opts, const Chebyshev* cheb) const
+{
+    l3k_gmres_result res{};
+    check(l3k_csr_dist_gmres_solve(workspace.get(), m_dist, d_b, d_x, d_minv, cheb ? cheb->get() : nullptr, &opts, &res));
+    return Gmres::converged(res);
+}
 
 // The CSR sparsity graph of a mesh over its local dofs, built on the device: computeLocalGraph in front of makeSparsityGraph
 // (algsys/SparsityGraph.hpp:26-81, :299) for one rank.  field_inds strictly ascending, empty = all dofs of the node; kind

@@ -434,6 +434,11 @@ SIGNATURES = {
     **{name: (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(GmresOpts), C.POINTER(GmresResult)])
        for name in ("l3k_gmres_solve", "l3k_gmres_solve_cheb", "l3k_gmres_solve_pmg", "l3k_csr_gmres_solve", "l3k_csr_gmres_solve_cheb",
                     "l3k_mfs_gmres_solve", "l3k_mfs_gmres_solve_cheb")},
+    "l3k_halo_reduce_reserve": (C.c_int, [_vp, C.c_int]),
+    "l3k_halo_allreduce_sum_n": (C.c_int, [_vp, _vp, C.c_int]),
+    "l3k_gmres_create_dist": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_size_t, C.POINTER(_vp)]),
+    "l3k_gmres_solve_dist": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(GmresOpts), C.POINTER(GmresResult)]),
+    "l3k_csr_dist_gmres_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(GmresOpts), C.POINTER(GmresResult)]),
     "l3k_gmres_multi_dot": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "l3k_gmres_project": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp, _vp]),
     "l3k_gmres_combine": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp, C.c_int64, _vp]),

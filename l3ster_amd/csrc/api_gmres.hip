@@ -1,6 +1,7 @@
 // api_gmres.hip -- restarted GMRES(m) of libl3k.so (include/l3k.h: l3k_gmres_*; the reference's Gmres, solve/BelosSolvers.hpp:124-130,
 // with the restart options of solve/SolverInterface.hpp:26-37): right preconditioning, classical Gram-Schmidt with one
-// re-orthogonalisation, written once over the operator value (LinOp, solver.hpp) for l3k_mf, l3k_mfs and l3k_csr, single rank.
+// re-orthogonalisation, written once over the operator value (LinOp, solver.hpp) for l3k_mf, l3k_mfs and l3k_csr on one rank and for
+// the partitioned operators (l3k_mf with an l3k_halo, l3k_csr_dist), where every reducing pass is followed by one all-reduce.
 // The kernels are in device/gmres.hpp.
 #include "device/gmres.hpp"
 #include "solver.hpp"
@@ -24,8 +25,7 @@ namespace
 {
 constexpr l3k_gmres_opts gmres_default_opts{1e-6, 10000, 0, 1, 39}; // (opts == NULL, include/l3k.h)
 const char* const        gmres_single_rank =
-    "%s is the single-rank solver; this mesh has ghost nodes, and there is no collective GMRES (a step reduces k + 1 scalars, "
-    "l3k_halo_allreduce_sum carries 8): partitioned systems call l3k_pcg_solve_dist";
+    "%s is the single-rank solver; this mesh has ghost nodes: partitioned systems call l3k_gmres_solve_dist";
 inline int gmGrid(int64_t n)
 {
     const int64_t g = (n + cg_threads - 1) / cg_threads;
@@ -55,7 +55,7 @@ PassPlan passPlan(int nb, int64_t n)
         for (int T = cg_threads; T >= 16; T /= 2)
             if (int64_t(nb) * (T + 1) + 2 * cg_threads + T <= budget)
             {
-                const int64_t tiles = (n + T - 1) / T;
+                const int64_t tiles = n > 0 ? (n + T - 1) / T : 1; // (a rank that owns no row launches one workgroup, which writes 0)
                 return {T, int(tiles < cg_blocks ? tiles : cg_blocks), size_t(int64_t(nb) * (T + 1) + 2 * cg_threads + T) * sizeof(double)};
             }
     return {0, gmGrid(n), 0};
@@ -129,7 +129,27 @@ int checkPiece(const char* who, const l3k_ctx* ctx, const void* V, size_t ld, in
     }
     return 0;
 }
-// The solve (include/l3k.h).  Right preconditioner: P (cheb, pmg), else Jacobi d_minv, else none
+// The collective route (include/l3k.h): the halo's reduction block is held while a solve writes into it
+struct ReduceHold
+{
+    l3k_halo* h;
+    explicit ReduceHold(l3k_halo* halo) : h{halo}
+    {
+        if (h)
+            l3k::halo::reduceHold(h, 1);
+    }
+    ReduceHold(const ReduceHold&)            = delete;
+    ReduceHold& operator=(const ReduceHold&) = delete;
+    ~ReduceHold()
+    {
+        if (h)
+            l3k::halo::reduceHold(h, -1);
+    }
+};
+// The solve (include/l3k.h).  Right preconditioner: P (cheb, pmg), else Jacobi d_minv, else none.  On a partitioned operator
+// (A.halo; its reduce hook is allreduceRow) every reducing pass lands in this rank's row of the halo's block instead of `dst`, and
+// the hook puts the sum over the ranks into `dst`: the kernels behind it read reduced values at the places they read today.  In a
+// world of one there is no row, the passes land in `dst` and the hook enqueues nothing
 int gmresSolve(l3k_gmres* G, const LinOp& A, const char* who, const double* d_b, double* d_x, const double* d_minv, const Precond* P,
                const l3k_gmres_opts* opts, l3k_gmres_result* result)
 {
@@ -165,6 +185,9 @@ int gmresSolve(l3k_gmres* G, const LinOp& A, const char* who, const double* d_b,
     const int            m     = G->m, every = o.check_every > 0 ? o.check_every : 1;
     const double* const  mask  = P ? P->mask : d_minv;
     const int            grid  = gmGrid(n);
+    const ReduceHold     hold{A.halo};
+    double* const        row = A.halo ? l3k::halo::reduceRow(A.halo) : nullptr;
+    const auto           land = [row](double* dst) { return row ? row : dst; };
     double               h[n_slots] = {};
     double               scale = 1., res = 0., est = 0.;
     int                  it = 0, cycles = 0, breakdown = 0;
@@ -175,16 +198,22 @@ int gmresSolve(l3k_gmres* G, const LinOp& A, const char* who, const double* d_b,
     };
     L3K_HIP(hipMemsetAsync(G->sc, 0, sizeof h, st));
     if (o.residual_scaling == 2) // sc[s_bb] = <b, b>
-        if (int rc = launchDots(ctx, G->partial, G->V, size_t(ld), 0, d_b, nullptr, n, G->sc + s_bb, nullptr))
+    {
+        if (int rc = launchDots(ctx, G->partial, G->V, size_t(ld), 0, d_b, nullptr, n, land(G->sc + s_bb), nullptr))
             return rc;
+        if (int rc = A.reduce(G->sc, s_bb, 1))
+            return rc;
+    }
     for (;; ++cycles)
     {
         // r = mask(b - A x) in v_0, beta
         if (int rc = A.apply(d_x, G->V))
             return rc;
         hipLaunchKernelGGL(residualKernel, dim3(grid), dim3(cg_threads), 0, st, G->V, d_b, mask, n, G->partial);
-        hipLaunchKernelGGL(finishKernel, dim3(1), dim3(cg_threads), 0, st, G->partial, grid, G->sc + s_rr, nullptr);
+        hipLaunchKernelGGL(finishKernel, dim3(1), dim3(cg_threads), 0, st, G->partial, grid, land(G->sc + s_rr), nullptr);
         L3K_HIP(hipGetLastError());
+        if (int rc = A.reduce(G->sc, s_rr, 1))
+            return rc;
         if (int rc = read())
             return rc;
         const double beta = std::sqrt(h[s_rr]);
@@ -222,11 +251,17 @@ int gmresSolve(l3k_gmres* G, const LinOp& A, const char* who, const double* d_b,
             if (int rc = A.apply(z, G->w))
                 return rc;
             const int nb = k + 1;
-            if (int rc = launchDots(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, G->h1, G->sc))
+            if (int rc = launchDots(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, land(G->h1), G->sc))
                 return rc;
-            if (int rc = launchProject(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, G->h1, G->h2, G->sc))
+            if (int rc = A.reduce(G->h1, 0, nb + 1))
                 return rc;
-            if (int rc = launchProject(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, G->h2, G->t, G->sc))
+            if (int rc = launchProject(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, G->h1, land(G->h2), G->sc))
+                return rc;
+            if (int rc = A.reduce(G->h2, 0, nb + 1))
+                return rc;
+            if (int rc = launchProject(ctx, G->partial, G->V, size_t(ld), nb, G->w, mask, n, G->h2, land(G->t), G->sc))
+                return rc;
+            if (int rc = A.reduce(G->t, 0, nb + 1))
                 return rc;
             hipLaunchKernelGGL(hessenbergKernel, dim3(1), dim3(cg_threads), 0, st, G->h1, G->h2, G->t, k, G->H, G->ldh, G->cs, G->sn, G->g,
                                G->sc);
@@ -307,25 +342,24 @@ int csrCheck(const char* who, l3k_gmres* G, const l3k_csr* A, const double* d_b,
     }
     return 0;
 }
-} // namespace
-
-extern "C" {
-int l3k_gmres_create(l3k_ctx* ctx, int64_t n, int restart_length, size_t max_bytes, l3k_gmres** out)
+// l3k_gmres_create, and l3k_gmres_create_dist (one_rank == false): n is one rank's share of the rows then -- it may be 0, and it
+// does not bound the restart length, which has to be the same on every rank
+int createWorkspace(const char* who, bool one_rank, l3k_ctx* ctx, int64_t n, int restart_length, size_t max_bytes, l3k_gmres** out)
 {
     if (!ctx || !out)
     {
-        setError("l3k_gmres_create: null argument");
+        setError("%s: null argument", who);
         return -1;
     }
-    if (n < 1 || restart_length < 1)
+    if (n < (one_rank ? 1 : 0) || restart_length < 1)
     {
-        setError("l3k_gmres_create: n = %lld and restart_length = %d must be at least 1", (long long)n, restart_length);
+        setError("%s: n = %lld and restart_length = %d must be at least %s", who, (long long)n, restart_length, one_rank ? "1" : "0 and 1");
         return -1;
     }
-    const int64_t m  = std::min< int64_t >(restart_length, n); // (n rows span no more than n directions)
+    const int64_t m = one_rank ? std::min< int64_t >(restart_length, n) : restart_length; // (n rows span no more than n directions)
     if (m + 2 > hess_lds) // (the Hessenberg column of a step is rotated in LDS)
     {
-        setError("l3k_gmres_create: restart_length = %d above %d", restart_length, hess_lds - 2);
+        setError("%s: restart_length = %d above %d", who, restart_length, hess_lds - 2);
         return -1;
     }
     const int64_t ld = (n + 3) / 4 * 4;
@@ -333,8 +367,8 @@ int l3k_gmres_create(l3k_ctx* ctx, int64_t n, int restart_length, size_t max_byt
     const size_t  count = size_t((m + 1 + 3) * ld) + small;
     if (max_bytes != 0 && count * sizeof(double) > max_bytes)
     {
-        setError("l3k_gmres_create: the workspace of GMRES(%lld) on %lld rows needs %zu bytes, above max_bytes = %zu", (long long)m,
-                 (long long)n, count * sizeof(double), max_bytes);
+        setError("%s: the workspace of GMRES(%lld) on %lld rows needs %zu bytes, above max_bytes = %zu", who, (long long)m, (long long)n,
+                 count * sizeof(double), max_bytes);
         return -1;
     }
     L3K_HIP(hipSetDevice(ctx->device));
@@ -355,6 +389,72 @@ int l3k_gmres_create(l3k_ctx* ctx, int64_t n, int restart_length, size_t max_byt
     G->partial = take(size_t(m + 2) * cg_blocks), G->sc = take(n_slots);
     *out = G.release();
     return 0;
+}
+// The collective solves (include/l3k.h).  Every refusal comes before the first collective call
+int distSolve(l3k_gmres* G, LinOp A, const char* who, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* c,
+              const l3k_gmres_opts* opts, l3k_gmres_result* result)
+{
+    if (A.n > 0 && (!d_b || !d_x))
+    {
+        setError("%s: null vector", who);
+        return -1;
+    }
+    if (l3k::halo::context(A.halo) != A.ctx)
+    {
+        setError("%s: the halo and the system belong to different contexts", who);
+        return -1;
+    }
+    if (c && (c->op.object != A.object || c->op.halo != A.halo))
+    {
+        setError("%s: the preconditioner was created for another system, or by a single-rank creator", who);
+        return -1;
+    }
+    if (c && d_minv && d_minv != c->minv)
+    {
+        setError("%s: d_minv is not the array the preconditioner was created on (pass that one, or NULL)", who);
+        return -1;
+    }
+    if (G->ctx == A.ctx && G->n == A.n && !overlap(d_b, d_x, A.n)) // (else gmresSolve refuses, and nothing is reserved)
+        if (int rc = l3k::halo::reduceEnsure(A.halo, G->m + 1))
+            return rc;
+    A.reduce_fn = [](void* halo, double* d_vals, int count) { return l3k::halo::allreduceRow(static_cast< l3k_halo* >(halo), d_vals, count); };
+    if (!c)
+        return gmresSolve(G, A, who, d_b, d_x, d_minv, nullptr, opts, result);
+    const Precond P = l3k::solver::chebPrecond(c);
+    return gmresSolve(G, A, who, d_b, d_x, nullptr, &P, opts, result);
+}
+} // namespace
+
+extern "C" {
+int l3k_gmres_create(l3k_ctx* ctx, int64_t n, int restart_length, size_t max_bytes, l3k_gmres** out)
+{
+    return createWorkspace("l3k_gmres_create", true, ctx, n, restart_length, max_bytes, out);
+}
+int l3k_gmres_create_dist(l3k_ctx* ctx, int64_t n_owned, int restart_length, size_t max_bytes, l3k_gmres** out)
+{
+    return createWorkspace("l3k_gmres_create_dist", false, ctx, n_owned, restart_length, max_bytes, out);
+}
+int l3k_gmres_solve_dist(l3k_gmres* G, l3k_mf* mf, l3k_halo* halo, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb,
+                         const l3k_gmres_opts* opts, l3k_gmres_result* result)
+{
+    if (!G || !mf || !halo || !result)
+    {
+        setError("l3k_gmres_solve_dist: null argument");
+        return -1;
+    }
+    if (int rc = l3k::solver::haloFitsSystem("l3k_gmres_solve_dist", mf, halo))
+        return rc;
+    return distSolve(G, l3k::solver::mfDistOp(mf, halo), "l3k_gmres_solve_dist", d_b, d_x, d_minv, cheb, opts, result);
+}
+int l3k_csr_dist_gmres_solve(l3k_gmres* G, l3k_csr_dist* D, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* cheb,
+                             const l3k_gmres_opts* opts, l3k_gmres_result* result)
+{
+    if (!G || !D || !result)
+    {
+        setError("l3k_csr_dist_gmres_solve: null argument");
+        return -1;
+    }
+    return distSolve(G, l3k::solver::csrDistOp(D), "l3k_csr_dist_gmres_solve", d_b, d_x, d_minv, cheb, opts, result);
 }
 int l3k_gmres_info_get(const l3k_gmres* G, l3k_gmres_info* out)
 {

@@ -151,6 +151,10 @@ struct l3k_halo
     // what they sent -- and the event behind a reduction's group (world > 1 only)
     DevBuf< double > reduce_rows;
     hipEvent_t       ev_reduce = nullptr;
+    // l3k_halo_allreduce_sum_n: its block [world][reduce_capacity] (l3k_halo_reduce_reserve; no memory in a world of one) and the
+    // number of solves that write their sums into row `rank` right now (the block stays as it is while there is one)
+    DevBuf< double > reduce_rows_n;
+    int              reduce_capacity = 0, reduce_holds = 0;
     // optional timing of the three element launches of the next applies (bench.py's roofline at N > 1): 6 events per apply
     std::vector< hipEvent_t > timing;
     int                       timing_cap = 0, timing_n = 0;
@@ -275,10 +279,75 @@ int unpackAll(l3k_halo* h, double* d_owned, size_t ld, int ncols)
                 return rc;
     return 0;
 }
+// The messages of a reduction (world > 1): row `rank` of the block rows[world][stride], complete on the context's stream, goes to
+// every peer and the peers' rows come in, `count` doubles each; the context's stream then waits for the group.  The ordering
+// contract is stated above l3k_halo_allreduce_sum
+int gatherRows(l3k_halo* h, double* rows, int stride, int count)
+{
+    hipStream_t   s    = h->ctx->stream;
+    double* const mine = rows + size_t(h->rank) * stride;
+    L3K_HIP(hipEventRecord(h->ev_main, s));
+    L3K_HIP(hipStreamWaitEvent(h->comm_stream, h->ev_main, 0));
+    const auto& tp = h->tp;
+    if (int rc = tp.group_begin(tp.user))
+        return rc;
+    int posted = 0; // (as in postImport: the group is closed before an error is reported)
+    for (int peer = 0; peer < h->world && posted == 0; ++peer)
+    {
+        if (peer == h->rank)
+            continue;
+        posted = tp.send(tp.user, mine, size_t(count), peer, h->comm_stream);
+        if (posted == 0)
+            posted = tp.recv(tp.user, rows + size_t(peer) * stride, size_t(count), peer, h->comm_stream);
+    }
+    if (posted != 0)
+    {
+        const std::string first = l3k::dev::lastError();
+        (void)tp.group_end(tp.user, h->comm_stream);
+        setError("%s", first.c_str());
+        return posted;
+    }
+    if (int rc = tp.group_end(tp.user, h->comm_stream))
+        return rc;
+    L3K_HIP(hipEventRecord(h->ev_reduce, h->comm_stream));
+    L3K_HIP(hipStreamWaitEvent(s, h->ev_reduce, 0));
+    return 0;
+}
 } // namespace
 
 namespace l3k::halo
 {
+// (A halo belongs to one rank, and a rank is one host thread: between this call and the hold that the solve takes nobody else can
+// reserve on this halo.  A larger capacity that is there already is kept; the row stride is the halo's capacity, not the solve's)
+int reduceEnsure(l3k_halo* h, int capacity)
+{
+    return h->reduce_capacity >= capacity ? 0 : l3k_halo_reduce_reserve(h, capacity);
+}
+void reduceHold(l3k_halo* h, int delta)
+{
+    h->reduce_holds += delta;
+}
+double* reduceRow(const l3k_halo* h)
+{
+    return h->world > 1 && h->reduce_capacity > 0 ? h->reduce_rows_n.ptr + size_t(h->rank) * h->reduce_capacity : nullptr;
+}
+int allreduceRow(l3k_halo* h, double* d_out, int count)
+{
+    if (h->world == 1)
+        return 0;
+    if (count < 1 || count > h->reduce_capacity)
+    {
+        setError("l3k_halo_allreduce_sum_n: count = %d outside [1, %d], the reserved capacity", count, h->reduce_capacity);
+        return -1;
+    }
+    L3K_HIP(hipSetDevice(h->ctx->device));
+    if (int rc = gatherRows(h, h->reduce_rows_n.ptr, h->reduce_capacity, count))
+        return rc;
+    hipLaunchKernelGGL(allreduceSumRowsNKernel, dim3((count + allreduce_n_threads - 1) / allreduce_n_threads), dim3(allreduce_n_threads), 0,
+                       h->ctx->stream, h->reduce_rows_n.ptr, h->world, h->reduce_capacity, count, d_out);
+    L3K_HIP(hipGetLastError());
+    return 0;
+}
 l3k_ctx* context(const l3k_halo* h)
 {
     return h->ctx;
@@ -753,36 +822,70 @@ int l3k_halo_allreduce_sum(l3k_halo* h, double* d_vals, int count)
     L3K_HIP(hipSetDevice(h->ctx->device));
     hipStream_t   s    = h->ctx->stream;
     double* const rows = h->reduce_rows.ptr;
-    double* const mine = rows + size_t(h->rank) * allreduce_max_count;
-    L3K_HIP(hipMemcpyAsync(mine, d_vals, sizeof(double) * count, hipMemcpyDeviceToDevice, s));
-    L3K_HIP(hipEventRecord(h->ev_main, s));
-    L3K_HIP(hipStreamWaitEvent(h->comm_stream, h->ev_main, 0));
-    const auto& tp = h->tp;
-    if (int rc = tp.group_begin(tp.user))
+    L3K_HIP(hipMemcpyAsync(rows + size_t(h->rank) * allreduce_max_count, d_vals, sizeof(double) * count, hipMemcpyDeviceToDevice, s));
+    if (int rc = gatherRows(h, rows, allreduce_max_count, count))
         return rc;
-    int posted = 0; // (as in postImport: the group is closed before an error is reported)
-    for (int peer = 0; peer < h->world && posted == 0; ++peer)
-    {
-        if (peer == h->rank)
-            continue;
-        posted = tp.send(tp.user, mine, size_t(count), peer, h->comm_stream);
-        if (posted == 0)
-            posted = tp.recv(tp.user, rows + size_t(peer) * allreduce_max_count, size_t(count), peer, h->comm_stream);
-    }
-    if (posted != 0)
-    {
-        const std::string first = l3k::dev::lastError();
-        (void)tp.group_end(tp.user, h->comm_stream);
-        setError("%s", first.c_str());
-        return posted;
-    }
-    if (int rc = tp.group_end(tp.user, h->comm_stream))
-        return rc;
-    L3K_HIP(hipEventRecord(h->ev_reduce, h->comm_stream));
-    L3K_HIP(hipStreamWaitEvent(s, h->ev_reduce, 0));
     hipLaunchKernelGGL(l3k::halo::allreduceSumRowsKernel, dim3(1), dim3(64), 0, s, rows, h->world, count, d_vals);
     L3K_HIP(hipGetLastError());
     return 0;
+}
+
+// The same reduction at any width: count from 1 to the capacity of l3k_halo_reduce_reserve, which is the row stride of a block of
+// its own.  The scheme, the events and the ordering argument are those above; the two blocks never serve one reduction, and the
+// reductions of both kinds follow one another on the context's stream.
+int l3k_halo_reduce_reserve(l3k_halo* h, int capacity)
+{
+    using l3k::halo::allreduce_n_capacity;
+    if (!h || capacity < 1 || capacity > allreduce_n_capacity)
+    {
+        setError("l3k_halo_reduce_reserve: null argument or capacity outside [1, %d]", allreduce_n_capacity);
+        return -1;
+    }
+    if (capacity == h->reduce_capacity)
+        return 0;
+    if (h->reduce_holds > 0)
+    {
+        setError("l3k_halo_reduce_reserve: a solve is writing into the block of %d doubles per rank: it cannot become one of %d",
+                 h->reduce_capacity, capacity);
+        return -1;
+    }
+    if (h->world > 1)
+    {
+        // (the peers have read this rank's row when the context's stream is through: it waits for every reduction's group; the
+        // communication stream has then written the other rows)
+        L3K_HIP(hipSetDevice(h->ctx->device));
+        L3K_HIP(hipStreamSynchronize(h->ctx->stream));
+        L3K_HIP(hipStreamSynchronize(h->comm_stream));
+        h->reduce_rows_n   = DevBuf< double >{};
+        h->reduce_capacity = 0;
+        if (int rc = h->reduce_rows_n.alloc(size_t(h->world) * capacity))
+            return rc;
+    }
+    h->reduce_capacity = capacity;
+    return 0;
+}
+int l3k_halo_allreduce_sum_n(l3k_halo* h, double* d_vals, int count)
+{
+    if (!h || !d_vals)
+    {
+        setError("l3k_halo_allreduce_sum_n: null argument");
+        return -1;
+    }
+    if (h->reduce_capacity == 0)
+    {
+        setError("l3k_halo_allreduce_sum_n: no capacity reserved: call l3k_halo_reduce_reserve first");
+        return -1;
+    }
+    if (count < 1 || count > h->reduce_capacity)
+    {
+        setError("l3k_halo_allreduce_sum_n: count = %d outside [1, %d], the reserved capacity", count, h->reduce_capacity);
+        return -1;
+    }
+    if (h->world == 1)
+        return 0;
+    L3K_HIP(hipSetDevice(h->ctx->device));
+    L3K_HIP(hipMemcpyAsync(l3k::halo::reduceRow(h), d_vals, sizeof(double) * count, hipMemcpyDeviceToDevice, h->ctx->stream));
+    return l3k::halo::allreduceRow(h, d_vals, count);
 }
 
 // HIP events around the three element launches (first interior half, border, second interior half) of the next `n_applies`

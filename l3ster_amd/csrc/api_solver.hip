@@ -932,9 +932,7 @@ int l3k_mfs_pcg_solve_cheb(l3k_mfs* S, const double* d_b, double* d_x, l3k_cheb*
 // ------------------------------------------------------------------------------------------------ collective solves
 // The same loops on a partitioned operator (include/l3k.h; solve/BelosSolvers.hpp:116-122 in an MPI run).  Every refusal comes
 // before the first collective call: a rank that returns -1 here has left no peer waiting inside an exchange
-namespace
-{
-int haloFitsSystem(const char* who, const l3k_mf* mf, const l3k_halo* h)
+int l3k::solver::haloFitsSystem(const char* who, const l3k_mf* mf, const l3k_halo* h)
 {
     if (l3k::halo::context(h) != mf->ctx)
     {
@@ -950,6 +948,9 @@ int haloFitsSystem(const char* who, const l3k_mf* mf, const l3k_halo* h)
     }
     return 0;
 }
+using l3k::solver::haloFitsSystem;
+namespace
+{
 int distSolve(const LinOp& A, const char* who, const double* d_b, double* d_x, const double* d_minv, l3k_cheb* c, const l3k_cg_opts* opts,
               l3k_cg_result* result)
 {

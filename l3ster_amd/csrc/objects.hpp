@@ -473,6 +473,15 @@ hipEvent_t* timingSlot(l3k_halo* h);
 // what the last export of ONE column brought from neighbour k < nNeighbours(h): the owned rows it added into (the neighbour's send
 // list) and the values it added, n of each; valid behind endExport until the next export
 int  nNeighbours(const l3k_halo* h);
+// The block of l3k_halo_allreduce_sum_n for a solve that writes its sums into it.  reduceEnsure: a capacity of at least `capacity`
+// (l3k_halo_reduce_reserve unless there is one).  reduceHold(+1 / -1): a solve is using the block, l3k_halo_reduce_reserve leaves it
+// alone.  reduceRow: this rank's row of the block -- what a reducing kernel may write its finished sums into, no copy in front of
+// the messages -- or nullptr in a world of one, where nothing is reduced.  allreduceRow: d_out[0 .. count) <- the sum over the
+// ranks of the rows' first `count` values, in rank order, behind what the context's stream holds (nothing in a world of one)
+int     reduceEnsure(l3k_halo* h, int capacity);
+void    reduceHold(l3k_halo* h, int delta);
+double* reduceRow(const l3k_halo* h);
+int     allreduceRow(l3k_halo* h, double* d_out, int count);
 void received(const l3k_halo* h, int k, const int32_t** d_rows, const double** d_vals, int64_t* n);
 } // namespace l3k::halo
 // api_csr_dist.hip: what the collective solves (api_solver.hip) need of a distributed CSR operator

@@ -13,7 +13,9 @@ namespace l3k::solver
 // <x, A x>, on the context's stream.  The PCG loops, the power method and the Chebyshev recurrence are written ONCE over this
 // value; mfOp, mfsOp and csrOp make it for one rank, mfDistOp and csrDistOp for a partitioned system.  reduce_fn and its object `halo` are the reduction hook:
 // the loops call reduce(s, first, count) wherever a dot product has landed in s[first .. first + count); the partitioned makers
-// set l3k_halo_allreduce_sum over the halo's ranks, the single-rank makers leave it null and nothing is enqueued
+// set l3k_halo_allreduce_sum over the halo's ranks, the single-rank makers leave it null and nothing is enqueued.  The collective
+// GMRES (api_gmres.hip) puts the wide reduction there: its passes land in the halo's block (l3k::halo::reduceRow) and the hook sums
+// the rows into d_vals (l3k::halo::allreduceRow)
 struct LinOp
 {
     l3k_ctx* ctx;
@@ -36,6 +38,8 @@ LinOp mfsOp(l3k_mfs* S);
 // the partitioned operators: (l3k_mf, l3k_halo) through l3k_mf_apply_dist, l3k_csr_dist through l3k_csr_dist_apply / _apply_energy
 LinOp mfDistOp(l3k_mf* mf, l3k_halo* halo);
 LinOp csrDistOp(l3k_csr_dist* D);
+// -1 with a message from `who` unless the halo is on the system's context and matches its mesh (dofs per node, ghost range)
+int haloFitsSystem(const char* who, const l3k_mf* mf, const l3k_halo* h);
 // The preconditioner of the PCG that keeps r (pcgSolvePrecond): z <- M^-1 r with s[2] <- <r, z> behind it on the stream, the
 // frozen-row mask (rows with mask == 0 keep x and carry r = 0) and the sizes.  w and az are two vectors of the loop's workspace
 // that are free during the application

@@ -311,6 +311,22 @@ class NativeHalo:
         capi.check(capi.load().l3k_halo_allreduce_sum(self._h, C.c_void_p(t.data_ptr()), t.numel()))
         return t
 
+    def reduce_reserve(self, capacity):
+        """The capacity of allreduce_n: the largest number of values of one reduction (l3k_halo_reduce_reserve; local).  The
+        collective GMRES reserves restart_length + 1 by itself."""
+        from . import capi
+        capi.check(capi.load().l3k_halo_reduce_reserve(self._h, int(capacity)))
+
+    def allreduce_n(self, t):
+        """allreduce for 1 to `capacity` doubles (l3k_halo_allreduce_sum_n; collective, queued on the context's stream): the same
+        sum in ascending rank order, one thread per value.  reduce_reserve(capacity) comes first."""
+        import ctypes as C
+        from . import capi
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < 1:
+            raise capi.L3KError("NativeHalo.allreduce_n: a contiguous float64 tensor of at least 1 entry")
+        capi.check(capi.load().l3k_halo_allreduce_sum_n(self._h, C.c_void_p(t.data_ptr()), t.numel()))
+        return t
+
     def __del__(self):
         try:
             from . import capi

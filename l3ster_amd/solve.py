@@ -446,17 +446,20 @@ def pcg(system, b, x, minv=None, tol=1e-6, max_iters=10_000, residual_scaling="n
 class GmresWorkspace:
     """Handle of l3k_gmres_create: the workspace of restarted GMRES(restart_length) on n rows -- the basis, w, z, u, the Hessenberg
     matrix, the partial sums -- on the device of `ctx`.  restart_length above n is lowered to n; max_bytes: 0 = no guard, otherwise
-    creation refuses a workspace above it and names the bytes needed.  One workspace serves any number of solves of its n."""
+    creation refuses a workspace above it and names the bytes needed.  One workspace serves any number of solves of its n.
+    collective=True (l3k_gmres_create_dist): the workspace of one rank of gmres_distributed -- n is the rank's owned rows, may be 0,
+    and does not lower restart_length, which every rank gives alike."""
 
-    def __init__(self, ctx, n, restart_length=250, max_bytes=0):
+    def __init__(self, ctx, n, restart_length=250, max_bytes=0, collective=False):
         from . import capi
         if int(restart_length) < 1:
             raise capi.L3KError(f"GmresWorkspace: restart_length = {restart_length} must be at least 1")
-        if int(n) < 1:
-            raise capi.L3KError(f"GmresWorkspace: n = {n} must be at least 1")
+        if int(n) < (0 if collective else 1):
+            raise capi.L3KError(f"GmresWorkspace: n = {n} must be at least {0 if collective else 1}")
         self.ctx = ctx
         self._h = C.c_void_p()
-        capi.check(capi.load().l3k_gmres_create(ctx._h, int(n), int(restart_length), int(max_bytes), C.byref(self._h)))
+        create = capi.load().l3k_gmres_create_dist if collective else capi.load().l3k_gmres_create
+        capi.check(create(ctx._h, int(n), int(restart_length), int(max_bytes), C.byref(self._h)))
         i = self.info
         self.n, self.restart_length = i.n, i.restart_length
 
@@ -797,6 +800,57 @@ def _pcg_distributed_native(op, b, x, minv, opts, precond, throw_on_fail):
         if cheb is not None and cheb is not precond:
             cheb.close()
     return _from_c([res], throw_on_fail)[0]
+
+
+def gmres_distributed(op, ctx, b, x, minv=None, precond=None, workspace=None, restart_length=250, tol=1e-6, max_iters=10_000,
+                      residual_scaling="none", check_every=1, max_restarts=39, throw_on_fail=True):
+    """gmres for a partitioned system, the whole iteration inside the library (l3k_csr_dist_gmres_solve / l3k_gmres_solve_dist):
+    `op` is a system.DistributedCsrOperator or a distributed.NativeDistributedOperator, b / x / minv this rank's owned rows (empty
+    on a rank that owns nothing).  Every reducing pass -- <b, b>, <r, r> at the head of a cycle, the three passes of a step -- is
+    followed by one l3k_halo_allreduce_sum_n over the ranks of the operator's halo, so every rank takes the same decisions and
+    returns the same GmresSolveResult.  Collective: every rank calls it with the same options and restart_length.  `precond`: None
+    (Jacobi with minv, or no preconditioner without), a DistributedChebyshev of `op`, or a dict of its options (minv required then;
+    the object is made and dropped by the call).  `workspace`: a GmresWorkspace(ctx, n_owned, restart_length, collective=True) to
+    reuse; None: one of min(restart_length, max_iters) basis vectors is created for this call.  The p-multigrid and the triangular
+    preconditioners have no collective form."""
+    from . import capi
+    kind, handles = _native_operator(op)
+    n = b.numel()
+    if x.numel() != n or not (b.is_contiguous() and x.is_contiguous()) or (n and _overlap(b, x, n)):
+        raise capi.L3KError("b and x must be distinct contiguous vectors over the owned dofs")
+    if minv is not None and (minv.numel() != n or not minv.is_contiguous()):
+        raise capi.L3KError("minv must be a contiguous tensor over the owned dofs of the operator")
+    if int(restart_length) < 1:
+        raise capi.L3KError(f"restart_length = {restart_length} must be at least 1")
+    cheb = None
+    if precond is not None:
+        if isinstance(precond, DistributedChebyshev):
+            cheb = precond
+        elif isinstance(precond, dict):
+            if minv is None:
+                raise capi.L3KError("gmres_distributed(precond=dict(...)) needs minv: the preconditioner is a polynomial in D^-1 A")
+            cheb = DistributedChebyshev(op, minv, **_chebyshev_options(precond))
+        else:
+            raise capi.L3KError("gmres_distributed takes a DistributedChebyshev or a dict of its options as precond: the p-multigrid "
+                                "and the triangular preconditioners have no collective form")
+        if minv is not None and minv is not cheb.minv and minv.data_ptr() != cheb.minv.data_ptr():
+            raise capi.L3KError("give the preconditioner's own minv, or none")
+    opts = capi.GmresOpts(float(tol), int(max_iters), _SCALING[residual_scaling], int(check_every), int(max_restarts))
+    ws = workspace
+    res = capi.GmresResult()
+    try:
+        if ws is None:
+            ws = GmresWorkspace(ctx, n, max(1, min(int(restart_length), int(max_iters))), collective=True)
+        solve = capi.load().l3k_csr_dist_gmres_solve if kind == "csr" else capi.load().l3k_gmres_solve_dist
+        capi.check(solve(ws._h, *handles, _vp(b), _vp(x), None if cheb is not None else _vp(minv), cheb._h if cheb is not None else None,
+                         C.byref(opts), C.byref(res)))
+    finally:
+        if ws is not None and ws is not workspace:
+            ws.close()
+        if cheb is not None and cheb is not precond:
+            cheb.close()
+    return _checked([GmresSolveResult(res.achieved_tol, res.iterations, bool(res.converged), res.restarts, bool(res.breakdown),
+                                      res.estimate, res.orth_loss)], throw_on_fail)[0]
 
 
 class CholeskySolver:
